@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — Gibbs tokens sampled per second per sweep (BASELINE.json metric).
 
-  python bench.py --gpus N --steps K --warmup W [--workload C4] [--docs D]
+  python bench.py --gpus N --steps K --warmup W [--workload C4] [--docs D] [--dump-outputs DIR]
 
 A "step" is one full Gibbs sweep (mvhdp_sweep: view weights + F+tree rebuild +
 the sweep kernel + count update) over the synthetic corpus, inputs resident in
@@ -136,6 +136,86 @@ def cpu_baseline(workload, sample_docs, iters, seed):
                       f"{3 * T // 4} sampler + {T // 4} updater threads (PTM:1036-1037 topology)"}
 
 
+DUMP_BUDGET_BYTES = 60 << 20    # --dump-outputs: all files together stay under 64 MB
+STAT_FIELDS = ("tokens", "changed", "new_mass_cnt", "topic_doc_mass_cnt", "word_ftree_mass_cnt", "oov_skipped", "aborted_docs",
+               "exact_fallbacks", "activated_topic", "activated_modality", "activations")
+
+
+def _sample(n, cap, stream):
+    """Sorted fixed seeded sample of `cap` indices of range(n); None when all n fit."""
+    if n <= cap:
+        return None
+    return np.sort(np.random.default_rng([0xD0, stream]).choice(n, cap, replace=False))
+
+
+def dump_outputs(out_dir, s, last, K, M, V, world, rank, dist):
+    """What the timed path hands its caller after its last step, as DIR/<name>.npy in float32 / float64 (rank 0 writes):
+
+      sweep_stats      [ranks][13]  the step's integer statistics (STAT_FIELDS, then activation_key as its high and low 32 bits)
+      alpha, inactive  the hyper-parameters a sweep may change (a topic leaving inActiveTopicIndex)
+      nk_v<m>          [K] topic totals of view m
+      nwk_v<m>         [V_m][K] topic-word counts of view m (float32 while every cell is below 2^24), or a fixed seeded sample of
+                       its word rows (ids in nwk_v<m>_rows)
+      z_v<m>           the assignments of view m, or a fixed seeded sample of them (global token positions in z_v<m>_pos:
+                       all shards in document order, so a dump does not depend on --gpus)
+
+    A view's counts and assignments share (DUMP_BUDGET_BYTES - the small arrays) / M equally.  Returns (files, bytes)."""
+    key = int(last.activation_key)
+    stats = [float(getattr(last, f)) for f in STAT_FIELDS] + [float(key >> 32), float(key & 0xFFFFFFFF)]
+    stats = [stats] if world == 1 else _gather(dist, stats, rank)
+    alpha, inactive = s.get_alpha()
+    arrays = {}
+    if rank == 0:
+        arrays = {"sweep_stats": np.asarray(stats, dtype=np.float64), "alpha": alpha.astype(np.float64), "inactive": inactive.astype(np.float32)}
+    # less alpha, nk_v*, inactive and 64 KB for sweep_stats: the samples must not depend on the number of ranks
+    share = (DUMP_BUDGET_BYTES - 8 * (M * (K + 1) + M * K + K) - (64 << 10)) // (2 * M)
+    for m in range(M):
+        nwk, nk = s.get_counts(m)
+        cell = np.float32 if int(nwk.max(initial=0)) < (1 << 24) else np.float64
+        rows = _sample(V[m], share // (np.dtype(cell).itemsize * K + 8), 2 * m)
+        if rank == 0:
+            arrays[f"nk_v{m}"] = nk.astype(np.float64)
+            if rows is not None:
+                arrays[f"nwk_v{m}_rows"] = rows.astype(np.float64)
+            arrays[f"nwk_v{m}"] = (nwk if rows is None else nwk[rows]).astype(cell)
+        del nwk
+        z = s.get_assignments(m)
+        n_local = [len(z)] if world == 1 else _all_gather(dist, len(z))
+        first = int(sum(n_local[:rank]))
+        pos = _sample(int(sum(n_local)), share // 12, 2 * m + 1)
+        if pos is not None:
+            z = z[pos[(pos >= first) & (pos < first + len(z))] - first]
+        if world > 1:
+            parts = _gather(dist, z, rank)
+            z = np.concatenate(parts) if parts is not None else None
+        if rank == 0:
+            arrays[f"z_v{m}"] = z.astype(np.float32)
+            if pos is not None:
+                arrays[f"z_v{m}_pos"] = pos.astype(np.float64)
+        del z
+    if rank != 0:
+        return 0, 0
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_BUDGET_BYTES, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return len(arrays), total
+
+
+def _all_gather(dist, obj):
+    out = [None] * dist.get_world_size()
+    dist.all_gather_object(out, obj)
+    return out
+
+
+def _gather(dist, obj, rank):
+    """obj of every rank, in rank order, on rank 0 (None elsewhere)."""
+    out = [None] * dist.get_world_size() if rank == 0 else None
+    dist.gather_object(obj, out, dst=0)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -164,7 +244,12 @@ def main():
     ap.add_argument("--rehearse-on-one-gpu", action="store_true",
                     help="N>1 ranks all on cuda:0 with the gloo backend (host-staged all-reduce): exercises the "
                          "sharding logic on a 1-GPU box; not a performance number")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them computed (statistics, counts, assignments; a fixed "
+                         "seeded sample where an array is large) as DIR/<name>.npy, float32 / float64, under 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -347,6 +432,11 @@ def main():
             kernel_ms.append(last.sweep_kernel_ms)
     barrier()
     dt = max_over_ranks(time.perf_counter() - t0)
+    dumped = None
+    if args.dump_outputs:
+        # outside the timed region, before the secondary modes below sweep on
+        files, nbytes = dump_outputs(args.dump_outputs, s, last, K, M, V, world, rank, dist)
+        dumped = {"dir": args.dump_outputs, "files": files, "bytes": nbytes}
 
     value = total_tokens * args.steps / dt
     # roofline of the dominant kernel (sweep_fast_kernel<R>) on this rank: algorithmic bytes per launch /
@@ -406,6 +496,8 @@ def main():
     # order-independent fingerprint of the final global counts: must not depend on the number of shards
     nk_fp = [int(np.asarray(s.get_counts(m)[1], dtype=np.int64).dot(np.arange(1, K + 1, dtype=np.int64))) for m in range(M)]
     out["final_nk_fingerprint"] = nk_fp
+    if dumped:
+        out["dumped_outputs"] = dumped
     eq = out["reference_sweep_equivalent"]["gpu_sweeps_per_reference_sweep"]
     main_mode = "live" if args.live else "deferred"
     out["value_in_reference_sweeps"] = {main_mode: [value / eq[main_mode][1], value / eq[main_mode][0]]} if eq.get(main_mode) else {}

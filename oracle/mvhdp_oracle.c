@@ -3,7 +3,7 @@
  * See mvhdp_oracle.h for the scope statement.  Plain C; build with
  * -ffp-contract=off so that no a*b+c is fused (Java never fuses).
  *
- * Reference aliases (all under /root/reference/src/main/java/org/madgik/):
+ * Reference aliases (all under the reference's src/main/java/org/madgik/):
  *   WRK = MVTopicModel/FastQMVWVWorkerRunnable.java
  *   UPD = MVTopicModel/FastQMVWVUpdaterRunnable.java
  *   PTM = MVTopicModel/FastQMVWVParallelTopicModel.java

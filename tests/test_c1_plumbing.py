@@ -1,7 +1,7 @@
 """BASELINE config C1 (SampleData/SMSSpamCollection2.txt, one view, K = 20): CPU plumbing, SURVEY §8d.  The corpus is
 the committed integer fixture tests/golden/c1_smsspam.npz made by tools/c1_smsspam.py from the reference's data file
-(token ids, document offsets, vocabulary -- data, no code); where /root/reference is present the loader is re-run
-and must reproduce the fixture.  Vocabulary parity with a Java run is not claimed (no reference test pins MALLET's
+(token ids, document offsets, vocabulary -- data, no code); the loader is re-run on that data file and the stoplist,
+both stored beside the fixture, and must reproduce it.  Vocabulary parity with a Java run is not claimed (no reference test pins MALLET's
 tokeniser); what is checked is the plumbing: text -> alphabet -> CSR -> addInstances -> sweeps -> counts, LL, top words."""
 import os
 import sys
@@ -25,10 +25,9 @@ def test_fixture_shape_and_loader():
     assert np.all(np.diff(first) > 0)
     assert c1_smsspam.simple_tokenize("Free entry in 2 a wkly comp, T&C's apply 0845x", {"in", "a"}) == ["free", "entry", "wkly", "comp", "apply"]
     assert c1_smsspam.simple_tokenize("re_use co-op naïve 4ever", set()) == ["re_use", "naïve", "ever"]      # '_' extends, '-' ends, digits vanish
-    if os.path.exists(os.path.join(c1_smsspam.REF, "SampleData", "SMSSpamCollection2.txt")):
-        d2, t2, w2, names, labels = c1_smsspam.load()
-        assert np.array_equal(d2, doc_off) and np.array_equal(t2, tokens) and w2.tolist() == words.tolist()
-        assert set(labels.tolist()) == {"ham", "spam"} and names[0] == "1"
+    d2, t2, w2, names, labels = c1_smsspam.load()
+    assert np.array_equal(d2, doc_off) and np.array_equal(t2, tokens) and w2.tolist() == words.tolist()
+    assert set(labels.tolist()) == {"ham", "spam"} and names[0] == "1"
 
 
 def test_c1_restated_reference_run():

@@ -10,12 +10,16 @@ a token in the stoplist is dropped), plus the build's own rule of dropping token
 reference test pins the tokenisation: vocabulary parity with a Java run is NOT claimed.  What C1 checks is the plumbing:
 text -> alphabet -> CSR -> addInstances rule -> sweeps -> counts / log-likelihood / top words.
 
-  python tools/c1_smsspam.py --make-fixture      # /root/reference -> tests/golden/c1_smsspam.npz (integers + vocabulary)
+  python tools/c1_smsspam.py --make-fixture      # the stored text -> tests/golden/c1_smsspam.npz (integers + vocabulary)
   python tools/c1_smsspam.py --iterations 50     # restated reference (oracle/ref_threaded.c) on the fixture: LL/token, top words
+
+The reference's data files are stored as test data: tests/golden/c1_smsspam_text.txt.gz (SampleData/SMSSpamCollection2.txt,
+gzipped) and tests/golden/c1_stoplist_en.txt (stoplists/en.txt, MALLET's English stoplist).
 
 Measurement / test tooling: it uses the oracle, it is not product code.
 """
 import argparse
+import gzip
 import os
 import sys
 import unicodedata
@@ -24,8 +28,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-REF = "/root/reference"
-FIXTURE = os.path.join(ROOT, "tests", "golden", "c1_smsspam.npz")
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+FIXTURE = os.path.join(GOLDEN, "c1_smsspam.npz")
+TEXT = os.path.join(GOLDEN, "c1_smsspam_text.txt.gz")
+STOPLIST = os.path.join(GOLDEN, "c1_stoplist_en.txt")
 
 _EXTEND = {"Lu", "Ll", "Lt", "Lm", "Lo", "Mn", "Me", "Mc"}
 _END = {"Zs", "Zl", "Zp", "Pd", "Ps", "Pe", "Pc", "Po", "Pi", "Pf"}
@@ -52,13 +58,13 @@ def simple_tokenize(text, stop, min_len=3):
     return out
 
 
-def load(path=os.path.join(REF, "SampleData", "SMSSpamCollection2.txt"), stoplist=os.path.join(REF, "stoplists", "en.txt")):
+def load(path=TEXT, stoplist=STOPLIST):
     stop = set()
     with open(stoplist, encoding="utf-8", errors="replace") as f:
         for line in f:
             stop.update(line.split())
     vocab, names, labels, docs = {}, [], [], []
-    with open(path, encoding="utf-8", errors="replace") as f:
+    with (gzip.open if path.endswith(".gz") else open)(path, "rt", encoding="utf-8", errors="replace") as f:
         for line in f:
             parts = line.rstrip("\n").split("\t", 2)
             if len(parts) < 3:
