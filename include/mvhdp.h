@@ -85,7 +85,9 @@ typedef struct {
                                      LIVE sweep on stored trees activates one per segment border (up to its segment count); a LIVE sweep in its
                                      live-rows form gives birth chunk by chunk (any number: see MVHDP_SWEEP_LIVE); activated_topic is the FIRST of them
                                      -- a host pulls alpha / inActiveTopicIndex with mvhdp_get_alpha whenever activated_topic >= 0;
-                                     0 with MVHDP_SWEEP_NO_APPLY / FROZEN (the caller activates) */
+                                     0 with MVHDP_SWEEP_NO_APPLY / FROZEN (the caller activates: mvhdp_apply_delta, or mvhdp_activate_births
+                                     behind a MVHDP_SWEEP_SHARD_BIRTHS sweep); a group sweep reports what it activated on every member:
+                                     with SHARD_BIRTHS the number of topics born in the step, activated_topic the lowest-index newborn */
     int32_t reserved;
 } mvhdp_sweep_stats;
 
@@ -148,7 +150,8 @@ typedef struct {
  * its live-rows form does it chunk by chunk: a new-topic draw takes the first inactive topic no delta has reached yet, a chunk whose
  * deltas reach it moves the samplers on to the next, and the segment's end activates every topic that was reached, in index order
  * (mvhdp_sweep_stats.activations can exceed the segment count).  With NO_APPLY nothing is activated here (the caller reduces the
- * key first). */
+ * key first) and new-topic draws all go to the first inactive index -- unless MVHDP_SWEEP_SHARD_BIRTHS asks for the births of a
+ * document shard (below). */
 #define MVHDP_SWEEP_LIVE        0x20u
 #define MVHDP_SWEEP_LIVE_SEGMENTS(n) (((uint32_t)(n) & 0xffu) << 16)
 
@@ -179,10 +182,25 @@ typedef struct {
  * applying its deltas) give the integers of one MVHDP_SWEEP_SEGMENT_APPLY call with n segments.  Not with LIVE or SEGMENT_APPLY. */
 #define MVHDP_SWEEP_ONLY_SEGMENT(s) ((((uint32_t)(s) + 1u) & 0xffu) << 24)
 
+/* Births of a truncated HDP on a document shard (UPD:263-270, WRK:522-526).  Only with MVHDP_SWEEP_LIVE; MVHDP_ERR_INVALID_ARG
+ * without it, with FROZEN, and with ONLY_SEGMENT.  With NO_APPLY, over a model with inactive topics, in the live-rows form: the
+ * sweep gives birth chunk by chunk as a live sweep without NO_APPLY does (one list of the inactive topics for the whole call: nothing
+ * restarts at a segment border) but activates nothing -- a topic it reached keeps its zero coefficient until the caller activates it.
+ * Without NO_APPLY, or without inactive topics, the flag changes nothing.  Every shard starts from the same replicated list and only
+ * moves forward along it, so what each reaches is a prefix of the list and so is the union over the shards: the caller MIN-reduces
+ * the per-topic table MVHDP_BUF_BIRTH_KEYS over all shards (RCCL ncclMin over K int64, in place) and every replica calls
+ * mvhdp_activate_births with the result.  In the stored-tree form (mvhdp_tuning.live_rows = 0, or wherever the generic kernel
+ * serves) topics are not born chunk by chunk: the table then holds at most the sweep's activation key, at its own topic.
+ * mvhdp_group_sweep takes the flag with LIVE (the same on every rank, as every flag): the K-wide MIN-reduce replaces the 8-byte
+ * one, and a step activates every topic any shard reached. */
+#define MVHDP_SWEEP_SHARD_BIRTHS 0x200u
+
 /* device buffers a host may hand to a collective (RCCL through torch.distributed or directly) */
 typedef enum {
     MVHDP_BUF_COUNTS = 0,  /* int32 [sumV*K + M*K]: n_wk rows of every view, then n_k */
-    MVHDP_BUF_DELTA  = 1   /* int32 [sumV*K + M*K]: the last sweep's deltas, same layout */
+    MVHDP_BUF_DELTA  = 1,  /* int32 [sumV*K + M*K]: the last sweep's deltas, same layout */
+    MVHDP_BUF_BIRTH_KEYS = 2  /* int64 [K]: written by every NO_APPLY sweep: keys[k] = the first delta (MVHDP_ACT_KEY) that reached topic k
+                                 if k was inactive and was reached, MVHDP_ACT_KEY_NONE otherwise (see MVHDP_SWEEP_SHARD_BIRTHS) */
 } mvhdp_buffer;
 
 /* ---- lifetime ---- */
@@ -290,7 +308,16 @@ int mvhdp_apply_delta(mvhdp_handle h, int32_t activated_topic, int32_t activated
 int mvhdp_apply_delta_begin(mvhdp_handle h);
 int mvhdp_apply_delta_rows(mvhdp_handle h, int64_t row_begin, int64_t row_end);
 int mvhdp_apply_delta_end(mvhdp_handle h, int32_t activated_topic, int32_t activated_modality);
-int mvhdp_trees_current(mvhdp_handle h);    /* 1: the F+trees match the counts and hyper-parameters, 0: not, < 0: error */
+/* The births of a MVHDP_SWEEP_SHARD_BIRTHS sweep over document shards (UPD:263-270: a topic leaves inActiveTopicIndex with the first
+ * delta that reaches it; WRK:522-526: the samplers then draw the next inactive index).  get: a host copy of MVHDP_BUF_BIRTH_KEYS after a
+ * NO_APPLY sweep.  activate: after mvhdp_apply_delta(h, -1, -1) or mvhdp_apply_delta_end(h, -1, -1), every topic k whose key is not
+ * MVHDP_ACT_KEY_NONE is activated in index order -- alpha[view(key)][k] takes alpha[view(key)][K], k leaves inActiveTopicIndex -- and the
+ * F+trees are invalidated if anything was born.  keys: [K] host memory (the MIN over all shards' tables), or NULL for MVHDP_BUF_BIRTH_KEYS
+ * as it stands on the device.  The whole table is checked first: a key whose topic field is not its index, a view >= M, a key on an active
+ * topic, or births that are not a prefix of the inactive topics in index order return MVHDP_ERR_INVALID_ARG with the model untouched. */
+int mvhdp_get_birth_keys(mvhdp_handle h, int64_t* keys /*[K]*/);
+int mvhdp_activate_births(mvhdp_handle h, const int64_t* keys /*[K] or NULL*/);
+int mvhdp_trees_current(mvhdp_handle h);   /* 1: the F+trees match the counts and hyper-parameters, 0: not, < 0: error */
 /* the per-document view weights used by the last sweep */
 int mvhdp_get_view_weights(mvhdp_handle h, double* p /*[D][M][M]*/);
 
@@ -364,7 +391,8 @@ int mvhdp_tuner_probe(int32_t num_modalities, const double* tree_branch_share /*
  * One mvhdp_group_sweep = every member samples its entities against the same snapshot; the int32 deltas are summed over all
  * members (on the device where members share a GPU, by RCCL all-reduce over xGMI between GPUs: the only collective of the
  * path), pipelined in row ranges with the update and F+tree rebuild of the rows that have arrived; with inactive topics the
- * activation key (MVHDP_ACT_KEY) is MIN-reduced so that every replica activates the same topic (UPD:263-270).  Results are
+ * activation key (MVHDP_ACT_KEY) is MIN-reduced so that every replica activates the same topic (UPD:263-270) -- or, with
+ * MVHDP_SWEEP_SHARD_BIRTHS, the per-topic table of birth keys, so that every replica activates the same topics.  Results are
  * bit-identical to one handle holding every entity.  RCCL is opened at run time (a copy already mapped into the process, else the
  * file MVHDP_RCCL_LIB names, else librccl.so.1; MVHDP_RCCL_LIB_FIRST=1 tries the named file before a mapped copy -- tests): a single-GPU host never loads it.  A handle belongs to at most one group; destroy
  * the group before its members (a group call on a group whose member is gone returns MVHDP_ERR_STATE).  Group calls leave the
@@ -395,7 +423,11 @@ int mvhdp_group_get_info(mvhdp_group g, mvhdp_group_info* info);
 int mvhdp_group_set_exchange_chunks(mvhdp_group g, int32_t chunks /* 1..64 */);
 /* buildInitialTypeTopicCounts PTM:600-652 over all shards: every member counts its entities, the counts are summed over the group */
 int mvhdp_group_build_counts(mvhdp_group g);
-/* flags: MVHDP_SWEEP_LIVE (+ LIVE_SEGMENTS), SEGMENT_APPLY (+ LIVE_SEGMENTS), EXACT_CHAIN, GENERIC_KERNEL; stats: one per local member, or NULL.
+/* flags: MVHDP_SWEEP_LIVE (+ LIVE_SEGMENTS, + SHARD_BIRTHS), SEGMENT_APPLY (+ LIVE_SEGMENTS), EXACT_CHAIN, GENERIC_KERNEL; stats: one per
+ * local member, or NULL.  Every rank passes the same flags (the collectives a step enters depend on them).
+ * With LIVE | SHARD_BIRTHS and inactive topics every member gives birth chunk by chunk along the same list, the members' birth tables are
+ * MIN-merged and MIN-all-reduced (K int64 instead of the one activation key) and every replica activates what any shard reached
+ * (mvhdp_activate_births): births in index order, any number per exchange.  Births stay one per exchange in the deterministic modes.
  * Failure (one process per GPU): every rank enters the same collectives whatever happens locally; a rank whose sweep failed contributes
  * zero deltas and raises a status word that is reduced with the tokensPerTopic part, so ALL ranks return an error from the same call
  * (the failing rank its own, the others MVHDP_ERR_STATE) and none waits inside a collective for a rank that has given up.  After such

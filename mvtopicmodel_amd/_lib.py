@@ -18,6 +18,7 @@ ABI_SYMBOLS = [
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_sweep", "mvhdp_sweep_many", "mvhdp_get_tuning", "mvhdp_set_tuning", "mvhdp_plan_probe", "mvhdp_tuner_probe",
     "mvhdp_apply_delta", "mvhdp_apply_delta_begin", "mvhdp_apply_delta_rows", "mvhdp_apply_delta_end",
+    "mvhdp_get_birth_keys", "mvhdp_activate_births",
     "mvhdp_trees_current", "mvhdp_get_view_weights",
     "mvhdp_device_buffer", "mvhdp_counts_written", "mvhdp_set_stream", "mvhdp_synchronize",
     "mvhdp_group_create", "mvhdp_group_unique_id", "mvhdp_group_create_rank", "mvhdp_group_destroy", "mvhdp_group_last_error",
@@ -216,6 +217,8 @@ def load_library():
     L.mvhdp_apply_delta_begin.argtypes = [vp]
     L.mvhdp_apply_delta_rows.argtypes = [vp, i64, i64]
     L.mvhdp_apply_delta_end.argtypes = [vp, i32, i32]
+    L.mvhdp_get_birth_keys.argtypes = [vp, vp]
+    L.mvhdp_activate_births.argtypes = [vp, vp]
     L.mvhdp_trees_current.argtypes = [vp]
     L.mvhdp_get_view_weights.argtypes = [vp, vp]
     L.mvhdp_device_buffer.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]

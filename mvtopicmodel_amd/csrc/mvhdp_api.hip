@@ -161,6 +161,11 @@ extern "C" int mvhdp_create(const mvhdp_config* cfg, mvhdp_handle* out)
     CREATE_HIP(hipMalloc(&h->d_births, (size_t)(2 + 2 * K) * sizeof(int32_t)));
     CREATE_HIP(hipMemset(h->d_births, 0, (size_t)(2 + 2 * K) * sizeof(int32_t)));
     CREATE_HIP(hipMalloc(&h->d_birth_keys, (size_t)K * sizeof(long long)));
+    CREATE_HIP(hipMalloc(&h->d_birth_table, (size_t)K * sizeof(long long)));
+    {
+        const std::vector<long long> none((size_t)K, LLONG_MAX);                       // MVHDP_BUF_BIRTH_KEYS before any sweep: nothing born
+        CREATE_HIP(hipMemcpy(h->d_birth_table, none.data(), (size_t)K * sizeof(long long), hipMemcpyHostToDevice));
+    }
     CREATE_HIP(hipMalloc(&h->d_ctl, CTL_WORDS * sizeof(unsigned long long)));
     CREATE_HIP(hipMemset(h->d_ctl, 0, CTL_WORDS * sizeof(unsigned long long)));
     h->d_stats = h->d_ctl;
@@ -189,7 +194,7 @@ static void release_device_resources(mvhdp_ctx* h)
     if (h->stream) hipStreamSynchronize(h->stream);
     auto fr = [](auto*& p) { if (p) { hipFree((void*)p); p = nullptr; } };
     for (int m = 0; m < MVHDP_MAXM; m++) { fr(h->d_doc_off[m]); fr(h->d_tok[m]); fr(h->d_z[m]); fr(h->d_carry[m]); fr(h->d_present[m]); }
-    fr(h->mm.counts); fr(h->mm.delta16); fr(h->mm.counts16); fr(h->mm.heavy); fr(h->mm.delta); fr(h->mm.trees); fr(h->mm.root); fr(h->mm.coef); fr(h->mm.mass0); fr(h->d_births); fr(h->d_birth_keys); fr(h->mm.dtab); fr(h->mm.p);
+    fr(h->mm.counts); fr(h->mm.delta16); fr(h->mm.counts16); fr(h->mm.heavy); fr(h->mm.delta); fr(h->mm.trees); fr(h->mm.root); fr(h->mm.coef); fr(h->mm.mass0); fr(h->d_births); fr(h->d_birth_keys); fr(h->d_birth_table); fr(h->mm.dtab); fr(h->mm.p);
     fr(h->d_alpha); fr(h->d_inactive); fr(h->d_ctl);
     if (h->h_ctl) { hipHostFree(h->h_ctl); h->h_ctl = nullptr; }
     h->d_stats = nullptr; h->d_act_key = nullptr; h->d_doc_counter = nullptr; h->d_ovf_meta = nullptr;
@@ -604,6 +609,28 @@ static hipError_t births_begin(mvhdp_ctx* h, hipStream_t s)
     if (e == hipSuccess) e = hipMemcpyAsync(h->d_birth_keys, h->h_birth_keys.data(), (size_t)K * sizeof(long long), hipMemcpyHostToDevice, s);
     return e;
 }
+// The activation itself, shared by a single handle's births (births_end) and a shard's (mvhdp_activate_births): every (topic, key) of
+// `born` -- checked by the caller, in index order -- leaves inActiveTopicIndex and its alpha[view(key)][k] takes alpha[view(key)][K]
+// (UPD:263-270); the F+trees of the old alpha are no longer current.
+static int activate_born(mvhdp_ctx* h, const std::vector<std::pair<int32_t, long long>>& born, SweepOutcome& oc)
+{
+    if (born.empty()) return MVHDP_OK;
+    MvModel& mm = h->mm;
+    const int K = mm.K;
+    for (const auto& b : born) {
+        const int t = b.first, mv = MVHDP_ACT_KEY_VIEW(b.second);
+        h->h_inactive[t] = 0;
+        h->h_alpha[(size_t)mv * (K + 1) + t] = h->h_alpha[(size_t)mv * (K + 1) + K];
+        if (oc.n_activations++ == 0) oc.first_act = b.second;
+    }
+    mm.first_inactive = -1;
+    for (int k = 0; k < K; k++) if (h->h_inactive[k]) { mm.first_inactive = k; break; }
+    h->have_trees = false;
+    HIPC(h, hipMemcpy(h->d_alpha, h->h_alpha.data(), h->h_alpha.size() * sizeof(double), hipMemcpyHostToDevice));
+    HIPC(h, hipMemcpy(h->d_inactive, h->h_inactive.data(), (size_t)K, hipMemcpyHostToDevice));
+    return MVHDP_OK;
+}
+
 static int births_end(mvhdp_ctx* h, hipStream_t s, SweepOutcome& oc)
 {
     MvModel& mm = h->mm;
@@ -614,25 +641,79 @@ static int births_end(mvhdp_ctx* h, hipStream_t s, SweepOutcome& oc)
     const int n = std::min(head[0], std::min(head[1], K));
     if (n <= 0) return MVHDP_OK;
     HIPC(h, hipMemcpy(h->h_birth_keys.data(), h->d_birth_keys, (size_t)n * sizeof(long long), hipMemcpyDeviceToHost));
-    bool any = false;
+    std::vector<std::pair<int32_t, long long>> born;
     for (int r = 0; r < n; r++) {
         const int t = h->h_births[(size_t)2 + r];
         const long long key = h->h_birth_keys[(size_t)r];
         if (t < 0 || t >= K || key == LLONG_MAX || !h->h_inactive[t]) continue;          // (cannot happen: position r is passed only by a delta that reached it)
         const int mv = MVHDP_ACT_KEY_VIEW(key);
         if (mv < 0 || mv >= mm.M) FAIL(h, MVHDP_ERR_STATE, "births: bad activation key");
-        h->h_inactive[t] = 0;
-        h->h_alpha[(size_t)mv * (K + 1) + t] = h->h_alpha[(size_t)mv * (K + 1) + K];
-        if (oc.n_activations++ == 0) oc.first_act = key;
-        any = true;
+        born.emplace_back(t, key);
     }
-    if (any) {
-        mm.first_inactive = -1;
-        for (int k = 0; k < K; k++) if (h->h_inactive[k]) { mm.first_inactive = k; break; }
-        HIPC(h, hipMemcpy(h->d_alpha, h->h_alpha.data(), h->h_alpha.size() * sizeof(double), hipMemcpyHostToDevice));
-        HIPC(h, hipMemcpy(h->d_inactive, h->h_inactive.data(), (size_t)K, hipMemcpyHostToDevice));
+    return activate_born(h, born, oc);
+}
+
+// MVHDP_BUF_BIRTH_KEYS after a NO_APPLY sweep of a document shard, MIN-reduced over the shards: every replica activates the same
+// topics.  The table is checked whole before anything changes (see include/mvhdp.h).
+int mvhdp_activate_births_ex(mvhdp_ctx* h, const int64_t* keys, int* n_born, long long* first_key)
+{
+    MvModel& mm = h->mm;
+    const int K = mm.K;
+    if (n_born) *n_born = 0;
+    if (first_key) *first_key = LLONG_MAX;
+    if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "activate_births before set_hyper");
+    if (h->rows_applied >= 0) FAIL(h, MVHDP_ERR_STATE, "activate_births inside an mvhdp_apply_delta_begin bracket (call mvhdp_apply_delta_end first)");
+    if (h->delta_pending) FAIL(h, MVHDP_ERR_STATE, "activate_births: the NO_APPLY sweep's deltas have not been applied (mvhdp_apply_delta first)");
+    std::vector<long long> tab((size_t)K);
+    HIPC(h, hipSetDevice(h->device));
+    if (keys) std::copy(keys, keys + K, tab.begin());
+    else {
+        HIPC(h, hipMemcpyAsync(tab.data(), h->d_birth_table, (size_t)K * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, hipStreamSynchronize(h->stream));
     }
+    std::vector<std::pair<int32_t, long long>> born;
+    for (int k = 0; k < K; k++) {
+        const long long key = tab[(size_t)k];
+        if (key == LLONG_MAX) continue;
+        if (key < 0 || MVHDP_ACT_KEY_TOPIC(key) != k) FAIL(h, MVHDP_ERR_INVALID_ARG, "activate_births: a key's topic field is not its index");
+        if (MVHDP_ACT_KEY_VIEW(key) >= mm.M) FAIL(h, MVHDP_ERR_INVALID_ARG, "activate_births: a key's view is beyond the model's views");
+        if (!h->h_inactive[k]) FAIL(h, MVHDP_ERR_INVALID_ARG, "activate_births: a key on a topic that is already active");
+        born.emplace_back(k, key);
+    }
+    // every shard moves forward along the same list of inactive topics: what any of them reached is a prefix of it
+    size_t i = 0;
+    for (int k = 0; k < K && i < born.size(); k++)
+        if (h->h_inactive[k]) { if (born[i].first != k) FAIL(h, MVHDP_ERR_INVALID_ARG, "activate_births: the births are not a prefix of the inactive topics"); i++; }
+    SweepOutcome oc;
+    const int rc = activate_born(h, born, oc);
+    if (rc) return rc;
+    if (n_born) *n_born = oc.n_activations;
+    if (first_key) *first_key = oc.first_act;
     return MVHDP_OK;
+}
+
+extern "C" int mvhdp_activate_births(mvhdp_handle h, const int64_t* keys)
+{
+    CHECK_H(h);
+    return mvhdp_activate_births_ex(h, keys, nullptr, nullptr);
+}
+
+extern "C" int mvhdp_get_birth_keys(mvhdp_handle h, int64_t* keys)
+{
+    CHECK_H(h);
+    if (!keys) FAIL(h, MVHDP_ERR_INVALID_ARG, "get_birth_keys: null");
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipMemcpyAsync(keys, h->d_birth_table, (size_t)h->mm.K * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    return MVHDP_OK;
+}
+
+// Does this sweep give birth chunk by chunk (SweepLaunch::births)?  A live sweep in its live-rows form over a truncated HDP that applies
+// its own deltas; with NO_APPLY only when a document shard asks for it (MVHDP_SWEEP_SHARD_BIRTHS)
+static bool sweep_births(const SweepPlan& p, uint32_t flags, const MvModel& mm)
+{
+    const bool shard = (flags & MVHDP_SWEEP_SHARD_BIRTHS) != 0;
+    return p.live_rows && (!(flags & MVHDP_SWEEP_NO_APPLY) || shard) && mm.first_inactive >= 0 && p.only_seg < 0;
 }
 
 extern "C" int mvhdp_apply_delta(mvhdp_handle h, int32_t activated_topic, int32_t activated_modality)
@@ -1119,7 +1200,8 @@ static int enqueue_sweep(mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_idx, u
     sl.stats = d_stats;
     sl.act_key = h->d_act_key;
     // a live sweep in its live-rows form over a truncated HDP: topics are born chunk by chunk (births_begin / births_end), not one per segment
-    const bool births = p.live_rows && !(flags & MVHDP_SWEEP_NO_APPLY) && mm.first_inactive >= 0 && p.only_seg < 0;
+    // (with NO_APPLY only for a document shard that asks for it, MVHDP_SWEEP_SHARD_BIRTHS: one list for the whole call, nothing activated here)
+    const bool births = sweep_births(p, flags, mm);
     if (births) { sl.births = h->d_births; sl.birth_keys = h->d_birth_keys; }
     sl.slot_hist = (unsigned long long*)h->d_ovf_meta + META_HIST;
     if (db) {
@@ -1207,7 +1289,7 @@ static int enqueue_sweep(mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_idx, u
             // index (WRK:523-526): a sweep whose counts are kept current does the same at every segment border -- the
             // segment's first such delta (by entity, view, position) activates its topic before the next segment starts.
             // Not with MVHDP_SWEEP_NO_APPLY: there the caller reduces the key over all document shards first.
-            if (births && e == hipSuccess) {
+            if (births && !(flags & MVHDP_SWEEP_NO_APPLY) && e == hipSuccess) {
                 const int rc = births_end(h, s, oc);                                     // every topic the segment's deltas reached
                 if (rc != MVHDP_OK) return rc;
                 mk.first_inactive = mm.first_inactive;
@@ -1345,6 +1427,9 @@ static void debug_print_plan(const mvhdp_ctx* h, const SweepPlan& p, uint32_t sw
 
 static int sweep_preconditions(mvhdp_ctx* h, uint32_t flags)
 {
+    // (before the state checks: a flag combination that can never run is an argument error, whatever the handle's state)
+    if ((flags & MVHDP_SWEEP_SHARD_BIRTHS) && (!(flags & MVHDP_SWEEP_LIVE) || (flags & MVHDP_SWEEP_FROZEN) || (flags >> 24) != 0))
+        FAIL(h, MVHDP_ERR_INVALID_ARG, "sweep: SHARD_BIRTHS goes with LIVE, not with FROZEN or ONLY_SEGMENT");
     int rc = require_corpus(h); if (rc) return rc;
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "sweep before set_hyper");
     if (!h->have_counts) FAIL(h, MVHDP_ERR_STATE, "sweep before build_counts/set_counts");
@@ -1379,9 +1464,14 @@ int mvhdp_sweep_begin(mvhdp_ctx* h, uint32_t sweep_idx, uint64_t seed, uint32_t 
     if (h->dbg_env) debug_print_plan(h, ps.p, sweep_idx);
     if (ps.debug) { rc = alloc_debug(h, dbg, ps.db); if (rc) return rc; }
     HIPC(h, hipEventRecord(h->ev[0], s));
-    ps.births = ps.p.live_rows && !(flags & MVHDP_SWEEP_NO_APPLY) && h->mm.first_inactive >= 0 && ps.p.only_seg < 0;   // (as enqueue_sweep decides it)
+    ps.births = sweep_births(ps.p, flags, h->mm);                    // (as enqueue_sweep decides it)
     rc = enqueue_sweep(h, ps.p, sweep_idx, seed, p_override, ps.debug ? &ps.db : nullptr, h->d_stats, h->ev[1], h->ev[2], ps.oc);
     if (rc) { ps.db.release(); return rc; }
+    if ((flags & MVHDP_SWEEP_NO_APPLY) && !ps.p.frozen) {
+        // MVHDP_BUF_BIRTH_KEYS: what this shard's deltas reached, by topic, for the MIN-reduce over the shards (mvhdp_activate_births)
+        hipError_t e = mvhdp_launch_birth_table(ps.births ? h->d_births : nullptr, h->d_birth_keys, h->d_act_key, h->mm.K, h->d_birth_table, s);
+        if (e != hipSuccess) { ps.db.release(); HIPC(h, e); }
+    }
     // counters | activation key | histograms: one copy into the handle's pinned buffer, in stream order behind the kernels
     hipError_t e = hipMemcpyAsync(h->h_ctl, h->d_ctl, (ST_COUNT + 1 + META_WORDS64) * sizeof(unsigned long long), hipMemcpyDeviceToHost, s);
     if (e != hipSuccess) { ps.db.release(); HIPC(h, e); }
@@ -1680,6 +1770,7 @@ extern "C" int mvhdp_device_buffer(mvhdp_handle h, mvhdp_buffer which, void** de
     size_t b = (size_t)counts_len(h) * sizeof(int32_t);
     if (which == MVHDP_BUF_COUNTS) { *dev_ptr = h->mm.counts; *bytes = b; return MVHDP_OK; }
     if (which == MVHDP_BUF_DELTA) { *dev_ptr = h->mm.delta; *bytes = b; return MVHDP_OK; }
+    if (which == MVHDP_BUF_BIRTH_KEYS) { *dev_ptr = h->d_birth_table; *bytes = (size_t)h->mm.K * sizeof(long long); return MVHDP_OK; }
     FAIL(h, MVHDP_ERR_INVALID_ARG, "device_buffer: unknown buffer");
 }
 

@@ -58,6 +58,7 @@ struct mvhdp_ctx {
     long long* d_act_key = nullptr;          //   = d_ctl + ST_COUNT
     int32_t* d_births = nullptr;             // [2 + 2K] births of a live sweep (SweepLaunch::births)
     long long* d_birth_keys = nullptr;       // [K]
+    long long* d_birth_table = nullptr;      // [K] MVHDP_BUF_BIRTH_KEYS: a NO_APPLY sweep's births by topic (mvhdp_activate_births)
     std::vector<int32_t> h_births;           // host copies of the two (the list a segment starts with; what it ended with)
     std::vector<long long> h_birth_keys;
     unsigned long long* d_doc_counter = nullptr;
@@ -159,6 +160,8 @@ struct PendingSweep {
 };
 int mvhdp_sweep_begin(mvhdp_ctx* h, uint32_t sweep_idx, uint64_t seed, uint32_t flags, const double* p_override, const mvhdp_debug* dbg, PendingSweep& ps);
 int mvhdp_sweep_finish(mvhdp_ctx* h, PendingSweep& ps, mvhdp_sweep_stats* stats);
+// mvhdp_activate_births, and what it did: *n_born topics, the lowest-index one's key in *first_key (MVHDP_ACT_KEY_NONE if none)
+int mvhdp_activate_births_ex(mvhdp_ctx* h, const int64_t* keys, int* n_born, long long* first_key);
 // pieces of the statistics either side of the sweep that a group of document shards composes (mvhdp_api.hip; see there)
 int mvhdp_view_overlap_accumulate(mvhdp_ctx* h, double* acc /*[M*M], continued*/);
 int mvhdp_ll_doc_accumulate(mvhdp_ctx* h, int m, double* ll, int64_t* cnt);

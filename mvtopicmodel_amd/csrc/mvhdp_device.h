@@ -169,6 +169,8 @@ hipError_t mvhdp_launch_delay(int microseconds, hipStream_t s);
 // zeroes the given counter arrays (any may be null) and sets *act_key to "none", in one launch
 hipError_t mvhdp_launch_ctl_reset(unsigned long long* stats, int n_stats, long long* act_key, unsigned long long* meta, int n_meta,
                                   unsigned int* class_counts, unsigned long long* qheads, hipStream_t s);
+// MVHDP_BUF_BIRTH_KEYS [K] from a NO_APPLY sweep's births (births / birth_keys of SweepLaunch, births null: its activation key alone)
+hipError_t mvhdp_launch_birth_table(const int32_t* births, const long long* birth_keys, const long long* act_key, int K, long long* keys, hipStream_t s);
 // MVHDP_SWEEP_LIVE helpers: 0 = delta <- -counts, 1 = delta <- counts + delta (after - before), counts <- snapshot, 2 = count negatives
 hipError_t mvhdp_launch_live_helper(const MvModel& mm, int which, unsigned long long* stats, hipStream_t s);
 hipError_t mvhdp_launch_doc_topic_hist(const MvModel& mm, int m, int32_t* hist, int32_t hist_len,

@@ -93,6 +93,22 @@ hipError_t launch_add_into(int32_t* dst, const int32_t* src, int64_t n, hipStrea
 
 __global__ void set_word_kernel(int32_t* p, int32_t v) { *p = v; }
 
+// the birth tables of the members on one device (MVHDP_BUF_BIRTH_KEYS), MIN-merged into the leader's exchange table; src null: dst = NONE
+// (a rank whose sweep failed contributes no births)
+__global__ __launch_bounds__(256) void min_births_kernel(long long* __restrict__ dst, const long long* __restrict__ src, int K, int first)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    const long long v = src ? src[k] : 0x7fffffffffffffffLL;
+    dst[k] = first ? v : (v < dst[k] ? v : dst[k]);
+}
+
+hipError_t launch_min_births(long long* dst, const long long* src, int K, bool first, hipStream_t s)
+{
+    hipLaunchKernelGGL(min_births_kernel, dim3((K + 255) / 256), dim3(256), 0, s, dst, src, K, first ? 1 : 0);
+    return hipGetLastError();
+}
+
 // ---- the exchange at half width ----
 // A row whose type holds at most 32767 tokens in the whole corpus (MvModel::heavy == 0: decided from the replicated counts whenever the
 // row's tree is built) cannot collect a delta beyond +-32767 in one sweep, summed over ALL ranks: a delta of a cell is bounded by the
@@ -161,6 +177,7 @@ struct mvhdp_group_ctx {
     std::vector<hipEvent_t> ev_swept;         // per member: its sweep (or count build) is on its stream
     std::vector<hipEvent_t> ev_reduced;       // per leader: the reduced buffer is complete
     std::vector<long long*> d_key;            // per leader: 8 bytes for the MIN-reduce of the activation key
+    std::vector<long long*> d_btab;           // per leader: [K] the MIN-reduce of the members' birth tables (MVHDP_SWEEP_SHARD_BIRTHS)
     hipEvent_t ev_x0 = nullptr, ev_x1 = nullptr;   // around the exchange on leader 0's stream
     int nranks = 1, rank0 = 0;                // ranks over all processes, rank of this process's first leader
     bool multi_process = false;
@@ -265,6 +282,9 @@ static int group_common_init(mvhdp_group_ctx* g, int32_t n, const mvhdp_handle* 
         g->ev_reduced.push_back(ev);
         GHIP(g, hipMalloc(&k, sizeof(long long)));
         g->d_key.push_back(k);
+        long long* bt = nullptr;
+        GHIP(g, hipMalloc(&bt, (size_t)std::max(1, g->members[0]->mm.K) * sizeof(long long)));
+        g->d_btab.push_back(bt);
     }
     GHIP(g, hipSetDevice(g->members[g->leaders[0]]->device));
     GHIP(g, hipEventCreate(&g->ev_x0));
@@ -287,6 +307,7 @@ static void group_release(mvhdp_group_ctx* g)
     for (size_t i = 0; i < g->ev_swept.size(); i++) if (g->ev_swept[i]) hipEventDestroy(g->ev_swept[i]);
     for (size_t l = 0; l < g->ev_reduced.size(); l++) if (g->ev_reduced[l]) hipEventDestroy(g->ev_reduced[l]);
     for (size_t l = 0; l < g->d_key.size(); l++) if (g->d_key[l]) hipFree(g->d_key[l]);
+    for (size_t l = 0; l < g->d_btab.size(); l++) if (g->d_btab[l]) hipFree(g->d_btab[l]);
     for (int32_t* b : g->xbuf) if (b) hipFree(b);
     for (int32_t* b : g->sbuf) if (b) hipFree(b);
     for (hipStream_t st : g->comm) if (st) hipStreamDestroy(st);
@@ -704,7 +725,40 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
     // 3. UPD:263-270 across shards: the first activating delta in (entity, view, position) order wins on every replica alike
     long long key = LLONG_MAX;
     const bool has_inactive = g->members[0]->mm.first_inactive >= 0;       // the hyper-parameters are replicated: every rank answers alike
-    if (has_inactive) {
+    // MVHDP_SWEEP_SHARD_BIRTHS: per topic (the members' birth tables), so that every replica activates every topic any shard reached
+    const bool shard_births = has_inactive && (flags & MVHDP_SWEEP_SHARD_BIRTHS);
+    std::vector<int64_t> btab;
+    if (shard_births) {
+        const int Kb = (int)K;
+        for (size_t l = 0; l < g->leaders.size(); l++) {
+            const int li = g->leaders[l];
+            mvhdp_ctx* L = g->members[li];
+            x.hip(hipSetDevice(L->device), "hipSetDevice");
+            bool first = true;
+            for (int i = 0; i < n; i++) {
+                if (g->leader_of[i] != li) continue;
+                x.hip(hipStreamWaitEvent(L->stream, g->ev_swept[i], 0), "hipStreamWaitEvent");
+                x.hip(launch_min_births(g->d_btab[l], local_err == MVHDP_OK ? g->members[i]->d_birth_table : nullptr, Kb, first, L->stream), "min_births_kernel");
+                first = false;
+            }
+        }
+        if (!g->comms.empty() && g->nranks > 1) {                          // (entered whatever the local status: a failed rank's table is all NONE)
+            Rccl* r = &g_rccl;
+            if (g->comms.size() > 1) x.nccl(r->GroupStart(), "ncclGroupStart");
+            for (size_t l = 0; l < g->leaders.size(); l++) {
+                mvhdp_ctx* L = g->members[g->leaders[l]];
+                x.hip(hipSetDevice(L->device), "hipSetDevice");
+                x.nccl(r->AllReduce(g->d_btab[l], g->d_btab[l], (size_t)Kb, ncclInt64, ncclMin, g->comms[l], L->stream), "birth table all-reduce");
+            }
+            if (g->comms.size() > 1) x.nccl(r->GroupEnd(), "ncclGroupEnd");
+        }
+        g->last_exchange_bytes += (long long)Kb * (long long)sizeof(long long);
+        // every leader holds the reduced table; every replica activates from the same host copy of leader 0's
+        btab.assign((size_t)Kb, LLONG_MAX);
+        x.hip(hipSetDevice(L0->device), "hipSetDevice");
+        x.hip(hipMemcpyAsync(btab.data(), g->d_btab[0], (size_t)Kb * sizeof(long long), hipMemcpyDeviceToHost, L0->stream), "hipMemcpyAsync");
+        x.hip(hipStreamSynchronize(L0->stream), "hipStreamSynchronize");
+    } else if (has_inactive) {
         if (local_err == MVHDP_OK) for (int i = 0; i < n; i++) key = std::min<long long>(key, (long long)st[i].activation_key);
         if (!g->comms.empty() && g->nranks > 1) {
             Rccl* r = &g_rccl;
@@ -736,11 +790,16 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
     const int32_t failed_ranks = tail[0];
     // (the test of the proposals: made from the reduced words alone, so every rank decides alike; a failed sweep decides nothing)
     if (!g->pack_on && failed_ranks == 0 && tail[1] > 0 && (long long)g->nranks * tail[2] == (long long)tail[1] * tail[1]) g->pack_on = true;
+    int born = 0;
+    if (shard_births) {                                                     // (what the step reports: the lowest-index newborn, as a single handle does)
+        for (int k = 0; k < (int)K; k++) if (btab[(size_t)k] != LLONG_MAX) { if (born++ == 0) key = (long long)btab[(size_t)k]; }
+    }
     const int32_t topic = key == LLONG_MAX ? -1 : MVHDP_ACT_KEY_TOPIC(key), view = key == LLONG_MAX ? -1 : MVHDP_ACT_KEY_VIEW(key);
     for (int i = 0; i < n; i++) {
         mvhdp_ctx* h = g->members[i];
         if (applying) {
-            const int rc2 = mvhdp_apply_delta_end(h, topic, view);
+            int rc2 = mvhdp_apply_delta_end(h, shard_births ? -1 : topic, shard_births ? -1 : view);
+            if (rc2 == MVHDP_OK && shard_births) rc2 = mvhdp_activate_births_ex(h, btab.data(), nullptr, nullptr);
             if (rc2 != MVHDP_OK) note(rc2, "member " + std::to_string(i) + ": " + h->err);
         } else {
             hipSetDevice(h->device); hipStreamSynchronize(h->stream);
@@ -750,7 +809,7 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
             h->counts_stale = true; h->delta_pending = false; h->delta_clean = false;
         }
         st[i].activation_key = key; st[i].activated_topic = topic; st[i].activated_modality = view;
-        st[i].activations = topic >= 0 ? 1 : 0;
+        st[i].activations = shard_births ? born : topic >= 0 ? 1 : 0;
     }
     float ms = 0;
     hipSetDevice(L0->device);
@@ -952,6 +1011,7 @@ extern "C" int mvhdp_group_sweep(mvhdp_group g, uint32_t sweep_idx, uint64_t see
     if (flags & (MVHDP_SWEEP_NO_APPLY | MVHDP_SWEEP_REUSE_TREES | MVHDP_SWEEP_FROZEN | MVHDP_SWEEP_SEGMENT_OVERLAP | 0xff000000u))
         GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_sweep: NO_APPLY, REUSE_TREES and ONLY_SEGMENT are set by the group itself; FROZEN is a single-handle mode");
     if ((flags & MVHDP_SWEEP_SEGMENT_APPLY) && (flags & MVHDP_SWEEP_LIVE)) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_sweep: SEGMENT_APPLY excludes LIVE");
+    if ((flags & MVHDP_SWEEP_SHARD_BIRTHS) && !(flags & MVHDP_SWEEP_LIVE)) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_sweep: SHARD_BIRTHS goes with LIVE");
     if ((flags & MVHDP_SWEEP_ASYNC_EXCHANGE) && !(flags & MVHDP_SWEEP_LIVE)) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_sweep: ASYNC_EXCHANGE goes with LIVE (a deferred sweep is the parity contract: every replica must hold the global counts)");
     DeviceGuard dg;
     const int n = (int)g->members.size();

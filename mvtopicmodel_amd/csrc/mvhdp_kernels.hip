@@ -1164,6 +1164,32 @@ hipError_t mvhdp_launch_ctl_reset(unsigned long long* stats, int n_stats, long l
     return hipGetLastError();
 }
 
+// MVHDP_BUF_BIRTH_KEYS, written at the end of a NO_APPLY sweep: the births of a document shard as a per-topic table that the shards
+// MIN-reduce (UPD:263-270 across shards; mvhdp_activate_births).  births (SweepLaunch::births of the sweep, or null): keys[k] = the first
+// delta that reached topic k if its list position is below the head; without births the sweep's activation key at its own topic.
+__global__ __launch_bounds__(256) void birth_table_kernel(const int32_t* __restrict__ births, const long long* __restrict__ birth_keys,
+                                                          const long long* __restrict__ act_key, int K, long long* __restrict__ keys)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= K) return;
+    long long v = 0x7fffffffffffffffLL;                           // MVHDP_ACT_KEY_NONE
+    if (births) {
+        const int head = births[0], n = births[1], r = births[2 + K + k];
+        if (r >= 0 && r < head && r < n && r < K) v = birth_keys[r];
+    } else {
+        const long long a = *act_key;
+        if (a != 0x7fffffffffffffffLL && MVHDP_ACT_KEY_TOPIC(a) == k) v = a;
+    }
+    keys[k] = v;
+}
+
+hipError_t mvhdp_launch_birth_table(const int32_t* births, const long long* birth_keys, const long long* act_key, int K, long long* keys, hipStream_t s)
+{
+    if (K <= 0) return hipSuccess;
+    hipLaunchKernelGGL(birth_table_kernel, dim3((K + 255) / 256), dim3(256), 0, s, births, birth_keys, act_key, K, keys);
+    return hipGetLastError();
+}
+
 // Holds a stream for about `microseconds` (one wave, s_sleep against the constant 100 MHz counter; always terminates).  An experiment
 // (PlanTuning::fork_delay_us, off by default): put between the fork event and the primary kernel it lets the wider class kernels --
 // which wait for that event on side streams, ~16 us longer than the next launch on the same stream takes -- become resident first

@@ -315,7 +315,10 @@ static inline void plan_sweep(const PlanIn& in, const PlanTuning& tu, WalkTuner&
     uint32_t flags = in.flags;
     if (flags & MVHDP_SWEEP_FROZEN) flags |= MVHDP_SWEEP_REUSE_TREES | MVHDP_SWEEP_NO_APPLY;   // nut == 0: the model is read-only
     if (flags & ~(MVHDP_SWEEP_REUSE_TREES | MVHDP_SWEEP_NO_APPLY | MVHDP_SWEEP_EXACT_CHAIN | MVHDP_SWEEP_GENERIC_KERNEL | MVHDP_SWEEP_FROZEN |
-                  MVHDP_SWEEP_LIVE | MVHDP_SWEEP_LIVE_SEGMENTS(0xff) | MVHDP_SWEEP_SEGMENT_APPLY | MVHDP_SWEEP_SEGMENT_OVERLAP | 0xff000000u)) return fail(MVHDP_ERR_INVALID_ARG, "sweep: unknown flag");
+                  MVHDP_SWEEP_LIVE | MVHDP_SWEEP_LIVE_SEGMENTS(0xff) | MVHDP_SWEEP_SEGMENT_APPLY | MVHDP_SWEEP_SEGMENT_OVERLAP | MVHDP_SWEEP_SHARD_BIRTHS |
+                  0xff000000u)) return fail(MVHDP_ERR_INVALID_ARG, "sweep: unknown flag");
+    if ((flags & MVHDP_SWEEP_SHARD_BIRTHS) && (!(flags & MVHDP_SWEEP_LIVE) || (flags & MVHDP_SWEEP_FROZEN) || (flags >> 24) != 0))
+        return fail(MVHDP_ERR_INVALID_ARG, "sweep: SHARD_BIRTHS goes with LIVE, not with FROZEN or ONLY_SEGMENT");
     p.flags = flags;
     p.live = (flags & MVHDP_SWEEP_LIVE) != 0;
     p.seg_apply = (flags & MVHDP_SWEEP_SEGMENT_APPLY) != 0;

@@ -24,7 +24,9 @@ import time
 import torch
 import torch.distributed as dist
 
-from .native import BUF_COUNTS, BUF_DELTA, SWEEP_NO_APPLY
+import numpy as np
+
+from .native import BUF_BIRTH_KEYS, BUF_COUNTS, BUF_DELTA, SWEEP_NO_APPLY, SWEEP_SHARD_BIRTHS
 
 KEY_NONE = (1 << 63) - 1   # MVHDP_ACT_KEY_NONE: "no activation"
 # include/mvhdp.h MVHDP_ACT_*: doc << 34 | view << 31 | position << 11 | topic (pinned by tests/test_abi.py)
@@ -35,15 +37,22 @@ ACT_TOPIC_MASK, ACT_VIEW_MASK = 0x7FF, 0x7
 class _DevArray:
     """Minimal __cuda_array_interface__ exporter for a raw device pointer."""
 
-    def __init__(self, ptr, n_int32):
+    def __init__(self, ptr, n, typestr="<i4"):
         self.__cuda_array_interface__ = {
-            "shape": (int(n_int32),), "typestr": "<i4", "data": (int(ptr), False), "version": 3, "strides": None,
+            "shape": (int(n),), "typestr": typestr, "data": (int(ptr), False), "version": 3, "strides": None,
         }
 
 
 def device_int32_tensor(ptr, nbytes, device):
     """torch.int32 tensor aliasing library-owned HBM (no copy)."""
     t = torch.as_tensor(_DevArray(ptr, nbytes // 4), device=device)
+    assert t.data_ptr() == ptr, "torch copied the buffer instead of aliasing it"
+    return t
+
+
+def device_int64_tensor(ptr, nbytes, device):
+    """torch.int64 tensor aliasing library-owned HBM (no copy)."""
+    t = torch.as_tensor(_DevArray(ptr, nbytes // 8, "<i8"), device=device)
     assert t.data_ptr() == ptr, "torch copied the buffer instead of aliasing it"
     return t
 
@@ -58,6 +67,8 @@ class GpuShard:
         self._counts_dev = device_int32_tensor(p, n, self.device)
         p, n = sampler.device_buffer(BUF_DELTA)
         self._delta_dev = device_int32_tensor(p, n, self.device)
+        p, n = sampler.device_buffer(BUF_BIRTH_KEYS)
+        self._birth_keys_dev = device_int64_tensor(p, n, self.device)
         # host_staged: the collective runs on CPU copies (gloo rehearsal of the N>1 path on one GPU)
         self.host_staged = host_staged
         self._counts_host = self._delta_host = None
@@ -93,6 +104,16 @@ class GpuShard:
         """inActiveTopicIndex non-empty (PTM:95)?  Every replica holds the same hyper-parameters, so every rank
         answers alike."""
         return bool(self.s.get_alpha()[1].any())
+
+    @property
+    def birth_keys(self):
+        """MVHDP_BUF_BIRTH_KEYS of the last NO_APPLY sweep (int64 [K]; a host copy when host-staged): MIN-reduced over the shards."""
+        return self._birth_keys_dev.cpu() if self.host_staged else self._birth_keys_dev
+
+    def activate_births(self, keys):
+        """Every replica activates the topics any shard reached (keys: the reduced table, host)."""
+        self.s.activate_births(keys)
+        return _births_summary(keys)
 
     def build_counts_local(self):
         self.s.build_counts()
@@ -151,6 +172,21 @@ def decode_activation(key):
     return int(key & ACT_TOPIC_MASK), int((key >> ACT_VIEW_SHIFT) & ACT_VIEW_MASK)
 
 
+def _births_summary(keys):
+    """(number of topics born, the lowest-index newborn's key) of a reduced birth table."""
+    keys = np.asarray(keys, dtype=np.int64)
+    born = np.flatnonzero(keys != KEY_NONE)
+    return int(born.size), (int(keys[born[0]]) if born.size else KEY_NONE)
+
+
+def _report_births(st, keys):
+    """The step's births in the statistics, as the native group reports them: every rank alike."""
+    n, first = _births_summary(keys)
+    st.activations = n
+    st.activation_key = first
+    st.activated_topic, st.activated_modality = decode_activation(first)
+
+
 def build_counts_all_reduce(shard, group=None):
     """buildInitialTypeTopicCounts PTM:600-652 over every shard: local counts, then a sum all-reduce."""
     shard.build_counts_local()
@@ -176,6 +212,9 @@ def sweep_all_reduce(shard, sweep_idx, seed, group=None, flags=0, timings=None, 
     When inActiveTopicIndex is non-empty the first activating delta in (entity, view, position)
     order must win on every replica alike (UPD:263-270): the 8-byte activation key is
     MIN-all-reduced -- decided from the replicated hyper-parameters, never by the caller.
+    With SWEEP_SHARD_BIRTHS (and SWEEP_LIVE) in `flags` every shard gives birth chunk by chunk
+    instead, and the per-topic table MVHDP_BUF_BIRTH_KEYS (K int64) is MIN-all-reduced in place of
+    the key: every replica activates every topic any shard reached (mvhdp_activate_births).
 
     timings: optional dict, accumulates milliseconds per phase: "sweep_call" (host wall time of
     mvhdp_sweep: view weights + trees + kernels + statistics read-back), "sweep_kernel" (device),
@@ -197,6 +236,7 @@ def sweep_all_reduce(shard, sweep_idx, seed, group=None, flags=0, timings=None, 
     t1 = time.perf_counter()
     topic, modality = st.activated_topic, st.activated_modality
     ev = None
+    births = None
     if multi:
         need_key = shard.has_inactive()
         shard.sync()
@@ -206,16 +246,25 @@ def sweep_all_reduce(shard, sweep_idx, seed, group=None, flags=0, timings=None, 
                 ev[0].record()
             t = shard.delta
             dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-            if need_key:
+            if need_key and (flags & SWEEP_SHARD_BIRTHS):
+                bk = shard.birth_keys
+                dist.all_reduce(bk, op=dist.ReduceOp.MIN, group=group)
+                births = bk.cpu().numpy()
+            elif need_key:
                 key = torch.tensor([st.activation_key], dtype=torch.int64, device=t.device)
                 dist.all_reduce(key, op=dist.ReduceOp.MIN, group=group)
             if ev is not None:
                 ev[1].record()
-            if need_key:
+            if need_key and births is None:
                 topic, modality = decode_activation(int(key.item()))
         shard.sync()
     t2 = time.perf_counter()
-    shard.apply(topic, modality)
+    if births is not None:
+        shard.apply(-1, -1)
+        shard.activate_births(births)
+        _report_births(st, births)
+    else:
+        shard.apply(topic, modality)
     t3 = time.perf_counter()
     if timings is not None:
         timings["sweep_call"] = timings.get("sweep_call", 0.0) + (t1 - t0) * 1e3
@@ -241,6 +290,7 @@ def _sweep_pipelined(shard, sweep_idx, seed, group, flags, timings, t0):
     st = shard.sweep_local(sweep_idx, seed, flags | reuse)
     t1 = time.perf_counter()
     need_key = shard.has_inactive()
+    births = need_key and bool(flags & SWEEP_SHARD_BIRTHS)     # the per-topic birth table instead of the one key
     chunks, nk_off = shard.row_chunks(PIPELINE_CHUNKS)
     K = shard.s.K
     ev = None
@@ -260,11 +310,19 @@ def _sweep_pipelined(shard, sweep_idx, seed, group, flags, timings, t0):
             else:
                 shard.s.apply_delta_rows(*chunks[i - 1])
         topic, modality = st.activated_topic, st.activated_modality
-        if need_key:
-            key = torch.tensor([st.activation_key], dtype=torch.int64)
-            dist.all_reduce(key, op=dist.ReduceOp.MIN, group=group)
-            topic, modality = decode_activation(int(key.item()))
-        shard.s.apply_delta_end(topic, modality)
+        if births:
+            bk = shard.birth_keys
+            dist.all_reduce(bk, op=dist.ReduceOp.MIN, group=group)
+            keys = bk.numpy()
+            shard.s.apply_delta_end(-1, -1)
+            shard.activate_births(keys)
+            _report_births(st, keys)
+        else:
+            if need_key:
+                key = torch.tensor([st.activation_key], dtype=torch.int64)
+                dist.all_reduce(key, op=dist.ReduceOp.MIN, group=group)
+                topic, modality = decode_activation(int(key.item()))
+            shard.s.apply_delta_end(topic, modality)
         if timings is not None:
             timings["sweep_call"] = timings.get("sweep_call", 0.0) + (t1 - t0) * 1e3
             timings["sweep_kernel"] = timings.get("sweep_kernel", 0.0) + st.sweep_kernel_ms
@@ -279,7 +337,10 @@ def _sweep_pipelined(shard, sweep_idx, seed, group, flags, timings, t0):
         for r0, r1 in chunks:
             works.append(dist.all_reduce(t[r0 * K:r1 * K], op=dist.ReduceOp.SUM, group=group, async_op=True))
         key = None
-        if need_key:
+        if births:
+            key = shard.birth_keys
+            works.append(dist.all_reduce(key, op=dist.ReduceOp.MIN, group=group, async_op=True))
+        elif need_key:
             key = torch.tensor([st.activation_key], dtype=torch.int64, device=t.device)
             works.append(dist.all_reduce(key, op=dist.ReduceOp.MIN, group=group, async_op=True))
         works[0].wait()                                   # the stream waits, the host does not
@@ -288,13 +349,21 @@ def _sweep_pipelined(shard, sweep_idx, seed, group, flags, timings, t0):
             w.wait()
             shard.s.apply_delta_rows(r0, r1)
         topic, modality = st.activated_topic, st.activated_modality
-        if need_key:
+        keys = None
+        if births:
+            works[-1].wait()
+            keys = key.cpu().numpy()
+            topic, modality = -1, -1
+        elif need_key:
             works[-1].wait()
             topic, modality = decode_activation(int(key.item()))
         if ev is not None:
             ev[1].record()
     t2 = time.perf_counter()
     shard.s.apply_delta_end(topic, modality)
+    if keys is not None:
+        shard.activate_births(keys)
+        _report_births(st, keys)
     t3 = time.perf_counter()
     if timings is not None:
         timings["sweep_call"] = timings.get("sweep_call", 0.0) + (t1 - t0) * 1e3

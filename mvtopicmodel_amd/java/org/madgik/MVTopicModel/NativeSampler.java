@@ -24,6 +24,7 @@ public final class NativeSampler implements AutoCloseable {
     public static final int SWEEP_SEGMENT_APPLY = 0x40; // deterministic: segments sampled one after the other, deltas applied in between
     public static final int SWEEP_ASYNC_EXCHANGE = 0x100;  // Group.sweep with SWEEP_LIVE: the all-reduce of sweep t beside sweep t+1 (then Group.drain())
     public static final int SWEEP_SEGMENT_OVERLAP = 0x80; // with SEGMENT_APPLY: the deltas of segment s are applied while segment s+1 samples (s+2 sees them)
+    public static final int SWEEP_SHARD_BIRTHS = 0x200;  // Group.sweep with SWEEP_LIVE over a truncated HDP: every shard gives birth chunk by chunk, every replica activates what any reached
     public static int sweepLiveSegments(int n) { return (n & 0xff) << 16; }
     public static int sweepOnlySegment(int s) { return ((s + 1) & 0xff) << 24; }   // only segment s of the n segments
 
@@ -158,7 +159,10 @@ public final class NativeSampler implements AutoCloseable {
         /** buildInitialTypeTopicCounts (lines 600-652) over all shards. */
         public void buildCounts() { nGroupBuildCounts(g); }
 
-        /** One sweep of the whole model; flags: SWEEP_LIVE / SWEEP_SEGMENT_APPLY (+ sweepLiveSegments), SWEEP_EXACT_CHAIN. */
+        /** One sweep of the whole model; flags: SWEEP_LIVE / SWEEP_SEGMENT_APPLY (+ sweepLiveSegments), SWEEP_EXACT_CHAIN.  A host that shards
+         *  a truncated HDP passes SWEEP_LIVE | SWEEP_SHARD_BIRTHS: topics are born on every shard chunk by chunk (UPD:263-270, WRK:522-526) and the
+         *  exchange carries a table of K birth keys instead of one, so a step activates any number of topics (stats: activations, the lowest-index
+         *  newborn in activatedTopic).  Every rank passes the same flags. */
         public SweepStats[] sweep(int sweepIdx, long seed, int flags) {
             long[] flat = new long[members * 8];
             int[] act = new int[3];

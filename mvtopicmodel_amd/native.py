@@ -22,6 +22,7 @@ SWEEP_LIVE = 0x20
 SWEEP_SEGMENT_APPLY = 0x40
 SWEEP_SEGMENT_OVERLAP = 0x80
 SWEEP_ASYNC_EXCHANGE = 0x100
+SWEEP_SHARD_BIRTHS = 0x200
 
 
 def SWEEP_LIVE_SEGMENTS(n):
@@ -33,6 +34,8 @@ def SWEEP_ONLY_SEGMENT(s):
 
 BUF_COUNTS = 0
 BUF_DELTA = 1
+BUF_BIRTH_KEYS = 2
+ACT_KEY_NONE = (1 << 63) - 1
 
 
 def _ptr(a):
@@ -358,6 +361,22 @@ class NativeSampler:
 
     def apply_delta_end(self, activated_topic=-1, activated_modality=-1):
         self._ck(self.L.mvhdp_apply_delta_end(self.h, int(activated_topic), int(activated_modality)))
+
+    def get_birth_keys(self):
+        """MVHDP_BUF_BIRTH_KEYS after a NO_APPLY sweep: int64 [K], the first delta that reached each topic that was inactive (SWEEP_SHARD_BIRTHS:
+        every topic the shard gave birth to), ACT_KEY_NONE elsewhere."""
+        keys = np.empty(self.K, dtype=np.int64)
+        self._ck(self.L.mvhdp_get_birth_keys(self.h, _ptr(keys)))
+        return keys
+
+    def activate_births(self, keys=None):
+        """Activates every topic whose key is not ACT_KEY_NONE (after apply_delta(-1, -1)); keys: int64 [K] (the MIN over all shards' tables),
+        or None for MVHDP_BUF_BIRTH_KEYS as it stands on the device."""
+        if keys is not None:
+            keys = np.ascontiguousarray(keys, dtype=np.int64)
+            if keys.shape != (self.K,):
+                raise ValueError(f"activate_births: keys must have shape ({self.K},)")
+        self._ck(self.L.mvhdp_activate_births(self.h, _ptr(keys)))
 
     def trees_current(self):
         rc = self.L.mvhdp_trees_current(self.h)

@@ -21,6 +21,7 @@ import argparse
 import json
 import os
 import sys
+import time
 
 import numpy as np
 
@@ -135,12 +136,12 @@ def run_group(args):
     """LL curve of a live chain over N document shards on ONE device, synchronous exchange against MVHDP_SWEEP_ASYNC_EXCHANGE."""
     from mvtopicmodel_amd import NativeGroup, NativeSampler, synth
     from mvtopicmodel_amd.java_init import init_assignments
-    from mvtopicmodel_amd.native import SWEEP_ASYNC_EXCHANGE, SWEEP_LIVE, SWEEP_LIVE_SEGMENTS
+    from mvtopicmodel_amd.native import SWEEP_ASYNC_EXCHANGE, SWEEP_LIVE, SWEEP_LIVE_SEGMENTS, SWEEP_SHARD_BIRTHS
     c, hy, K_init = load(args.workload, args.docs)
     z0 = init_assignments(K_init, c.doc_off, seed=1)
     ntok = np.array([int(c.doc_off[m][-1]) for m in range(c.M)], dtype=np.float64)
     tot = sum(np.diff(c.doc_off[m]) for m in range(c.M))
-    runs = {}
+    runs, cost = {}, {}
     for asyn in ((0,) if args.no_async else (0, 1)):          # (ASYNC_EXCHANGE is refused while a topic is inactive: a truncated HDP runs --no-async)
         shards = []
         for lo, hi in synth.shard_bounds(tot, args.shards):
@@ -152,19 +153,33 @@ def run_group(args):
             shards.append(s)
         g = NativeGroup(shards)
         g.build_counts()
-        flags = SWEEP_LIVE | SWEEP_LIVE_SEGMENTS(args.segments) | (SWEEP_ASYNC_EXCHANGE if asyn else 0)
+        flags = SWEEP_LIVE | SWEEP_LIVE_SEGMENTS(args.segments) | (SWEEP_ASYNC_EXCHANGE if asyn else 0) | (SWEEP_SHARD_BIRTHS if args.births else 0)
         name = f"gpu live over {args.shards} shards, {args.segments} segments, " + ("exchange one sweep behind (ASYNC_EXCHANGE)" if asyn else "exchange after every sweep")
+        if args.births:
+            name += ", shard births (SHARD_BIRTHS)"
         curve = [{"sweep": 0, "ll_per_token": (g.model_log_likelihood() / ntok).tolist()}]
+        # the cost of a sweep (host wall time of the group call: sampling + exchange + activation), the topics born in it
+        step_ms, births, all_active_at = [], [], None
+        inactive0 = int(np.count_nonzero(hy.inactive)) if hy.inactive is not None else 0
         for it in range(1, args.sweeps + 1):
-            g.sweep(it, args.seed, flags=flags)
+            t0 = time.perf_counter()
+            st = g.sweep(it, args.seed, flags=flags)
+            step_ms.append((time.perf_counter() - t0) * 1e3)
+            births.append(int(st[0].activations))
+            if all_active_at is None and sum(births) >= inactive0:
+                all_active_at = it
             if it % args.every == 0 or it == args.sweeps:
                 curve.append({"sweep": it, "ll_per_token": (g.model_log_likelihood() / ntok).tolist()})
-        print(f"{name}: final LL/token {curve[-1]['ll_per_token']}", flush=True)
+        print(f"{name}: final LL/token {curve[-1]['ll_per_token']}; {np.median(step_ms):.2f} ms per sweep (median); "
+              f"{inactive0} inactive topics, all active after sweep {all_active_at}", flush=True)
         runs[name] = curve
+        cost[name] = {"ms_per_sweep_median": float(np.median(step_ms)), "ms_per_sweep_mean": float(np.mean(step_ms)),
+                      "ms_per_sweep_first10_mean": float(np.mean(step_ms[:10])), "births_per_sweep": births,
+                      "inactive_at_start": inactive0, "all_active_after_sweep": all_active_at}
         g.close()
         for s in shards:
             s.close()
-    json.dump({"runs": runs, "workload": args.workload, "docs": c.D, "tokens": c.total_tokens}, open(args.out, "w"), indent=1)
+    json.dump({"runs": runs, "cost": cost, "workload": args.workload, "docs": c.D, "tokens": c.total_tokens}, open(args.out, "w"), indent=1)
 
 
 def table(args):
@@ -334,6 +349,7 @@ def main():
     p.add_argument("--seed", type=int, default=20260101); p.add_argument("--out", required=True)
     p.add_argument("--shards", type=int, default=8); p.add_argument("--segments", type=int, default=4)
     p.add_argument("--no-async", action="store_true", help="only the synchronous exchange")
+    p.add_argument("--births", action="store_true", help="MVHDP_SWEEP_SHARD_BIRTHS: every shard gives birth chunk by chunk, the exchange MIN-reduces the K birth keys")
     p = sub.add_parser("table")
     p.add_argument("files", nargs="+")
     p = sub.add_parser("equivalents")
