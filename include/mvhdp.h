@@ -276,6 +276,66 @@ int mvhdp_antoniak_draws(mvhdp_handle h, int32_t n, const int32_t* items /*[n]*/
  * len[m] of the last earlier entity of this handle that had it (zeros before the first). */
 int mvhdp_doc_topic_proportions(mvhdp_handle h, const double* view_weights /*[M]*/, int64_t d0, int64_t d1, double* out /*[d1-d0][K]*/);
 
+/* ---- topic diagnostics: the step after training (FastQMVWVTopicModelDiagnostics, DIAG = MVTopicModel/FastQMVWVTopicModelDiagnostics.java;
+ * SciTopicFlow builds it with N = 20 right after the save, whose saveExperiment / saveTopicsandExperiment call
+ * calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230 from PTM:1370 / PTM:1507 and getSortedWords PTM:1792-1811 per view).
+ * Preconditions as mvhdp_model_log_likelihood: counts current, no pending NO_APPLY delta (else MVHDP_ERR_STATE).  Integer outputs
+ * are exact; fp64 outputs follow the reference's formulas; every sum is taken in a fixed order (no floating-point atomics), so two
+ * calls give the same bits.  Outputs are written only when the call succeeds.  DIAG reads view 0 only (alpha[0], gamma[0], beta[0],
+ * tokensPerTopic[0], the view-0 tokens), even for an M-view model; so does mvhdp_diagnostics. ---- */
+#define MVHDP_DIAG_MAX_TOP_WORDS 64
+#define MVHDP_DIAG_PROPORTIONS   7       /* DEFAULT_DOC_PROPORTIONS {0.01, 0.02, 0.05, 0.1, 0.2, 0.3, 0.5}, DIAG:27 */
+/* score rows, the order of DIAG:104-116 */
+#define MVHDP_DIAG_TOKENS             0  /* tokensPerTopic[0][k]                                DIAG:242-250 */
+#define MVHDP_DIAG_DOCUMENT_ENTROPY   1  /* -sumCountTimesLogCount[k] / T + log T               DIAG:252-260 */
+#define MVHDP_DIAG_WORD_LENGTH        2  /* mean length of the top N words, / N always          DIAG:462-483 (NaN without word_length) */
+#define MVHDP_DIAG_COHERENCE          3  /* log((D(i,j) + beta0) / (D(j,j) + beta0)) over j < i  DIAG:544-571 */
+#define MVHDP_DIAG_NORM_DISCR_WEIGHT  4  /* discrWeight / |log10 alpha0[k] - log10 avg alpha0|  DIAG:313-338 (avg over K+1 entries, zeros not counted) */
+#define MVHDP_DIAG_DISCR_WEIGHT       5  /* calcDiscrWeightWithinTopics(.., true)[0][k]          DIAG:297-311, PTM:2233-2270 */
+#define MVHDP_DIAG_UNIFORM_DIST       6  /*                                                     DIAG:262-295 */
+#define MVHDP_DIAG_CORPUS_DIST        7  /*                                                     DIAG:368-404 */
+#define MVHDP_DIAG_EFF_NUM_WORDS      8  /*                                                     DIAG:340-363 */
+#define MVHDP_DIAG_TOKEN_DOC_DIFF     9  /*                                                     DIAG:406-457 */
+#define MVHDP_DIAG_RANK_1_DOCS       10  /* rank-1 documents / non-zero documents               DIAG:573-581 */
+#define MVHDP_DIAG_ALLOCATION_RATIO  11  /* documents at 50 % / documents at 2 %                DIAG:583-598 */
+#define MVHDP_DIAG_ALLOCATION_COUNT  12  /* documents at 30 % / non-zero documents              DIAG:600-613 */
+#define MVHDP_DIAG_ROWS              13
+typedef struct {
+    int32_t num_top_words;               /* N, 1..MVHDP_DIAG_MAX_TOP_WORDS (DIAG uses 20, saveTopicsandExperiment 49) */
+    const int32_t* word_length;          /* [V_0] String.length() of every view-0 type (UTF-16 code units), or NULL: the word-length row is NaN */
+} mvhdp_diag_args;
+typedef struct {                         /* caller-owned; every pointer but `scores` may be NULL (not wanted) */
+    double*  scores;                     /* [MVHDP_DIAG_ROWS][K] TopicScores.scores; a row left alone by DIAG stays 0 (discrWeight rows of alpha0[k] == 0) */
+    double*  word_scores;                /* [MVHDP_DIAG_ROWS][K][N] TopicScores.topicWordScores (0 for the rows that define none) */
+    int32_t* codoc;                      /* [K][N][N] topicCodocumentMatrices DIAG:122,209-221 */
+    int32_t* top_types;                  /* [K][N] view-0 top words as mvhdp_top_words(h, 0, N, ..) */
+    int32_t* top_counts;                 /* [K][N] */
+    int32_t* nonzero;                    /* [K] */
+    int32_t* num_rank1_docs;             /* [K] DIAG:228-230 */
+    int32_t* num_nonzero_docs;           /* [K] DIAG:189 */
+    int32_t* num_docs_at_proportions;    /* [K][MVHDP_DIAG_PROPORTIONS] DIAG:199-204 */
+    double*  sum_count_log_count;        /* [K] DIAG:196 */
+    int32_t* word_type_counts;           /* [V_0] DIAG:171 */
+    int64_t* num_tokens;                 /* [1] DIAG:170 */
+    double*  discr_weight_per_view;      /* [M] as mvhdp_discr_weights */
+} mvhdp_diag_out;
+/* getSortedWords(m) PTM:1792-1811 cut at n (1..64): per topic the types with n_wk > 0 by count descending, equal counts by DESCENDING
+ * type id (IDSorter.compareTo); types/counts [K][n], unfilled slots -1 / 0; nonzero[k] = sortedWords.size(). */
+int mvhdp_top_words(mvhdp_handle h, int32_t m, int32_t n, int32_t* types /*[K][n]*/, int32_t* counts /*[K][n]*/, int32_t* nonzero /*[K]*/);
+/* calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230: per_view[v] = skewSum / nonZeroSkewCnt with BOTH accumulators carried across
+ * views and nonZeroSkewCnt starting at 1 (the reference's running mean over views 0..v) -- discrWeightPerModality, the view weight
+ * factor of printDocumentTopics / the inferencer (PTM:2890-2898, INF:402-411; mvhdp_doc_topic_proportions).  type_weight: [V_m]
+ * typeDiscrWeight[m][w] = sum_k n_wk^2 / (sum_k n_wk)^2 (0 for an empty row), or NULL. */
+int mvhdp_discr_weights(mvhdp_handle h, double* per_view /*[M]*/, int32_t m, double* type_weight /*[V_m] or NULL*/);
+/* The diagnostics of DIAG:53-117: getSortedWords of view 0 cut at N, collectDocumentStatistics DIAG:120-236 over the view-0 tokens,
+ * the thirteen score rows.  Quirks kept: the top-N position of a topic with fewer than N words holds type 0 (DIAG:132,146-150), so it
+ * counts as present in a document whenever type 0 is one of the topic's real top words and occurs with it there; the rank-1 topic is
+ * the lowest index among equal counts; proportions (gamma0 alpha0[k] + c) / (gamma0 alphaSum0 + len) unfused; empty or inactive topics
+ * give the NaN / Inf Java gives.  wordTypeCounts are the view-0 row sums of n_wk (equal to the token counts when the counts are current;
+ * checked against tokensPerTopic[0]).  A view-0 token that is unassigned (-1) or out of the vocabulary is refused (DIAG:171-173 throws):
+ * MVHDP_ERR_STATE, outputs untouched. */
+int mvhdp_diagnostics(mvhdp_handle h, const mvhdp_diag_args* args, mvhdp_diag_out* out);
+
 /* ---- the hot path ---- */
 /* One Gibbs sweep over every entity: replaces "submit updaters + submit
  * workers + barrier.await()" PTM:1213-1239, i.e. WRK:186-233 x nst threads and
@@ -459,6 +519,11 @@ int mvhdp_group_doc_topic_hist(mvhdp_group g, int32_t m, int32_t* hist /*[K][his
 int mvhdp_group_count_histogram(mvhdp_group g, int32_t m, int32_t* hist, int32_t len);
 int mvhdp_group_view_overlap_sums(mvhdp_group g, double* sums /*[M][M]*/);
 int mvhdp_group_gamma_doc_statistics(mvhdp_group g, int32_t m, double gamma_m, uint64_t seed, uint32_t round, double* qs, double* qw);
+/* mvhdp_diagnostics of the whole model.  Top words, typeDiscrWeight / discrWeightPerModality and the column reductions are statistics
+ * of the replicated counts: any member's (so the group has no mvhdp_top_words / mvhdp_discr_weights of its own: call them on any
+ * member).  The document pass runs on every member over its own entities; its integer accumulators are summed over the group, the
+ * per-topic sums of c log c added member by member (ascending doc_id_base) and rank by rank.  Collective across processes. */
+int mvhdp_group_diagnostics(mvhdp_group g, const mvhdp_diag_args* args, mvhdp_diag_out* out);
 
 /* ---- interop for collectives and stream sharing ---- */
 int mvhdp_device_buffer(mvhdp_handle h, mvhdp_buffer which, void** dev_ptr, size_t* bytes);

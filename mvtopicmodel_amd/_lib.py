@@ -16,6 +16,7 @@ ABI_SYMBOLS = [
     "mvhdp_get_counts", "mvhdp_set_counts", "mvhdp_get_tree", "mvhdp_get_doc_topic_hist",
     "mvhdp_get_count_histogram", "mvhdp_view_overlap_sums", "mvhdp_model_log_likelihood", "mvhdp_doc_topic_proportions",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
+    "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_sweep", "mvhdp_sweep_many", "mvhdp_get_tuning", "mvhdp_set_tuning", "mvhdp_plan_probe", "mvhdp_tuner_probe",
     "mvhdp_apply_delta", "mvhdp_apply_delta_begin", "mvhdp_apply_delta_rows", "mvhdp_apply_delta_end",
     "mvhdp_get_birth_keys", "mvhdp_activate_births",
@@ -24,7 +25,7 @@ ABI_SYMBOLS = [
     "mvhdp_group_create", "mvhdp_group_unique_id", "mvhdp_group_create_rank", "mvhdp_group_destroy", "mvhdp_group_last_error",
     "mvhdp_group_get_info", "mvhdp_group_set_exchange_chunks", "mvhdp_group_build_counts", "mvhdp_group_sweep", "mvhdp_group_abort", "mvhdp_group_drain",
     "mvhdp_group_set_hyper", "mvhdp_group_log_likelihood", "mvhdp_group_doc_topic_hist", "mvhdp_group_count_histogram",
-    "mvhdp_group_view_overlap_sums", "mvhdp_group_gamma_doc_statistics",
+    "mvhdp_group_view_overlap_sums", "mvhdp_group_gamma_doc_statistics", "mvhdp_group_diagnostics",
 ]
 
 UNIQUE_ID_BYTES = 128
@@ -94,6 +95,24 @@ class PlanOutputC(C.Structure):
                 ("class_grid", C.c_int32 * 6), ("class_walk", C.c_int32 * 6), ("class_narrow", C.c_int32 * 6),
                 ("class_register_resident", C.c_int32 * 6), ("class_lds_bytes", C.c_int64 * 6), ("class_theta0", C.c_double * 6),
                 ("delta16", C.c_int32), ("live_rows", C.c_int32)]
+
+
+DIAG_MAX_TOP_WORDS = 64
+DIAG_PROPORTIONS = 7
+# the score rows of mvhdp_diagnostics, in the order of DIAG:104-116 (MVHDP_DIAG_* of include/mvhdp.h)
+DIAG_ROWS = ["tokens", "document_entropy", "word-length", "coherence", "normDiscrWeight", "discrWeight", "uniform_dist",
+             "corpus_dist", "eff_num_words", "token-doc-diff", "rank_1_docs", "allocation_ratio", "allocation_count"]
+
+
+class DiagArgsC(C.Structure):
+    _fields_ = [("num_top_words", C.c_int32), ("word_length", C.c_void_p)]
+
+
+class DiagOutC(C.Structure):
+    _fields_ = [("scores", C.c_void_p), ("word_scores", C.c_void_p), ("codoc", C.c_void_p), ("top_types", C.c_void_p),
+                ("top_counts", C.c_void_p), ("nonzero", C.c_void_p), ("num_rank1_docs", C.c_void_p), ("num_nonzero_docs", C.c_void_p),
+                ("num_docs_at_proportions", C.c_void_p), ("sum_count_log_count", C.c_void_p), ("word_type_counts", C.c_void_p),
+                ("num_tokens", C.c_void_p), ("discr_weight_per_view", C.c_void_p)]
 
 
 _lib = None
@@ -207,6 +226,9 @@ def load_library():
     L.mvhdp_gamma_doc_statistics.argtypes = [vp, i32, C.c_double, u64, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mvhdp_dp_table_statistics.argtypes = [vp, i32, vp, i32, vp, u64, u32, vp, vp]
     L.mvhdp_antoniak_draws.argtypes = [vp, i32, vp, vp, u64, u32, vp]
+    L.mvhdp_top_words.argtypes = [vp, i32, i32, vp, vp, vp]
+    L.mvhdp_discr_weights.argtypes = [vp, vp, i32, vp]
+    L.mvhdp_diagnostics.argtypes = [vp, C.POINTER(DiagArgsC), C.POINTER(DiagOutC)]
     L.mvhdp_sweep.argtypes = [vp, u32, u64, u32, vp, C.POINTER(DebugC), C.POINTER(SweepStatsC)]
     L.mvhdp_sweep_many.argtypes = [vp, u32, i32, u64, u32, vp]
     L.mvhdp_get_tuning.argtypes = [vp, C.POINTER(TuningC)]
@@ -242,6 +264,7 @@ def load_library():
     L.mvhdp_group_count_histogram.argtypes = [vp, i32, vp, i32]
     L.mvhdp_group_view_overlap_sums.argtypes = [vp, vp]
     L.mvhdp_group_gamma_doc_statistics.argtypes = [vp, i32, C.c_double, u64, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+    L.mvhdp_group_diagnostics.argtypes = [vp, C.POINTER(DiagArgsC), C.POINTER(DiagOutC)]
     for name in ABI_SYMBOLS:
         f = getattr(L, name)  # raises AttributeError if the symbol is not exported
         if name not in ("mvhdp_last_error", "mvhdp_version", "mvhdp_group_last_error"):

@@ -7,6 +7,7 @@
 
 #include <algorithm>
 #include <functional>
+#include <limits>
 #include <climits>
 #include <mutex>
 #include <set>
@@ -166,3 +167,28 @@ int mvhdp_activate_births_ex(mvhdp_ctx* h, const int64_t* keys, int* n_born, lon
 int mvhdp_view_overlap_accumulate(mvhdp_ctx* h, double* acc /*[M*M], continued*/);
 int mvhdp_ll_doc_accumulate(mvhdp_ctx* h, int m, double* ll, int64_t* cnt);
 int mvhdp_ll_model_finish(mvhdp_ctx* h, int m, double ll_doc, int64_t modalityCnt, double* out);
+
+// the topic diagnostics (mvhdp_diag.hip), in the pieces a group of document shards composes (mvhdp_group_diagnostics):
+//   the model part -- top N words of view 0, typeDiscrWeight, wordTypeCounts, the counts' tokensPerTopic[0] -- from the replicated counts;
+//   the document part (collectDocumentStatistics DIAG:120-236), entity by entity, ADDED into a DiagAcc;
+//   the finish: the column reductions on one handle and the thirteen score rows, then the caller's arrays.
+struct DiagModel {
+    int N = 0;
+    std::vector<int32_t> types, counts, nonzero, nk;        // [K][N], [K][N], [K], [K]
+    std::vector<int64_t> word_type_counts;                  // [V_0] = sum_k n_wk of view 0 (the view-0 tokens per type when the counts are current)
+    std::vector<double> type_weight, per_view;              // [V_0] typeDiscrWeight[0], [M] discrWeightPerModality
+};
+struct DiagAcc {
+    std::vector<int32_t> codoc, rank1_docs, nonzero_docs, at_proportions;   // [K][N][N], [K], [K], [K][MVHDP_DIAG_PROPORTIONS]
+    std::vector<double> sum_count_log_count;                                // [K]
+    int64_t num_tokens = 0;
+    void reset(int K, int N)
+    {
+        codoc.assign((size_t)K * N * N, 0); rank1_docs.assign((size_t)K, 0); nonzero_docs.assign((size_t)K, 0);
+        at_proportions.assign((size_t)K * MVHDP_DIAG_PROPORTIONS, 0); sum_count_log_count.assign((size_t)K, 0.0); num_tokens = 0;
+    }
+};
+int mvhdp_diag_check_args(mvhdp_ctx* h, const mvhdp_diag_args* args, const mvhdp_diag_out* out);
+int mvhdp_diag_model(mvhdp_ctx* h, int N, DiagModel& dm);
+int mvhdp_diag_docs(mvhdp_ctx* h, const DiagModel& dm, DiagAcc& acc);
+int mvhdp_diag_finish(mvhdp_ctx* h, const DiagModel& dm, const DiagAcc& acc, const mvhdp_diag_args* args, const mvhdp_diag_out* out);

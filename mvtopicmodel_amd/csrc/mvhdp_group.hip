@@ -1298,3 +1298,72 @@ extern "C" int mvhdp_group_gamma_doc_statistics(mvhdp_group g, int32_t m, double
     *qs = a; *qw = b;
     return MVHDP_OK;
 }
+
+// The topic diagnostics of the whole model (DIAG:53-117): the model part (top words of view 0, typeDiscrWeight, wordTypeCounts) and
+// the column reductions from the replicated counts on the first member; the document pass (DIAG:120-236) on every member over its own
+// entities -- integer accumulators summed (in one process by the host, across processes by xrank_sum_i32), the per-topic sums of
+// c log c added member by member in ascending doc_id_base and then rank by rank.
+extern "C" int mvhdp_group_diagnostics(mvhdp_group g, const mvhdp_diag_args* args, mvhdp_diag_out* out)
+{
+    CHECK_G(g);
+    DeviceGuard dg;
+    mvhdp_ctx* h0 = g->members[0];
+    { const int rc = mvhdp_diag_check_args(h0, args, out); if (rc) { g->err = "member 0: " + h0->err; return rc; } }
+    int lst = MVHDP_OK;
+    { const int rcd = land_before_statistics(g, &lst); if (rcd) return rcd; }
+    const bool multi = g->multi_process && g->nranks > 1;
+    const int K = h0->mm.K, N = args->num_top_words;
+    std::string keep;
+    DiagModel dm;
+    DiagAcc acc;
+    acc.reset(K, N);
+    if (lst == MVHDP_OK) {
+        const int rc = mvhdp_diag_model(h0, N, dm);
+        if (rc != MVHDP_OK) { lst = rc; g->err = keep = "member 0: " + h0->err; if (!multi) return rc; }
+    }
+    for (int i : g->by_entity) {
+        if (lst != MVHDP_OK) break;
+        DiagAcc mine;
+        mine.reset(K, N);
+        const int rc = mvhdp_diag_docs(g->members[i], dm, mine);
+        if (rc != MVHDP_OK) { lst = rc; g->err = keep = "member " + std::to_string(i) + ": " + g->members[i]->err; if (!multi) return rc; break; }
+        for (size_t q = 0; q < acc.codoc.size(); q++) acc.codoc[q] += mine.codoc[q];
+        for (int k = 0; k < K; k++) {
+            acc.rank1_docs[k] += mine.rank1_docs[k]; acc.nonzero_docs[k] += mine.nonzero_docs[k];
+            acc.sum_count_log_count[k] += mine.sum_count_log_count[k];
+        }
+        for (size_t q = 0; q < acc.at_proportions.size(); q++) acc.at_proportions[q] += mine.at_proportions[q];
+        acc.num_tokens += mine.num_tokens;
+    }
+    if (multi) {
+        // one int32 vector [codoc | rank-1 | non-zero | proportions], one f64 vector [c log c | numTokens]
+        std::vector<int32_t> iv;
+        iv.reserve(acc.codoc.size() + (size_t)K * (2 + MVHDP_DIAG_PROPORTIONS));
+        iv.insert(iv.end(), acc.codoc.begin(), acc.codoc.end());
+        iv.insert(iv.end(), acc.rank1_docs.begin(), acc.rank1_docs.end());
+        iv.insert(iv.end(), acc.nonzero_docs.begin(), acc.nonzero_docs.end());
+        iv.insert(iv.end(), acc.at_proportions.begin(), acc.at_proportions.end());
+        std::vector<double> fv(acc.sum_count_log_count);
+        fv.push_back((double)acc.num_tokens);
+        int f1 = 0, f2 = 0;
+        std::vector<double> all;
+        const int rc1 = xrank_sum_i32(g, iv.data(), iv.size(), lst, &f1);
+        const int rc2 = xrank_gather_f64(g, fv.data(), (int)fv.size(), lst, all, &f2);
+        if (lst != MVHDP_OK) { if (!keep.empty()) g->err = keep; return lst; }
+        if (rc1) return rc1;
+        if (rc2) return rc2;
+        if (f1 || f2) XFAILED(g, std::max(f1, f2));
+        size_t o = 0;
+        std::copy(iv.begin() + o, iv.begin() + o + acc.codoc.size(), acc.codoc.begin()); o += acc.codoc.size();
+        std::copy(iv.begin() + o, iv.begin() + o + K, acc.rank1_docs.begin()); o += K;
+        std::copy(iv.begin() + o, iv.begin() + o + K, acc.nonzero_docs.begin()); o += K;
+        std::copy(iv.begin() + o, iv.begin() + o + acc.at_proportions.size(), acc.at_proportions.begin());
+        const size_t nf = fv.size();
+        double tok = 0;
+        for (int k = 0; k < K; k++) { double a = 0; for (int r = 0; r < g->nranks; r++) a += all[(size_t)r * nf + k]; acc.sum_count_log_count[k] = a; }
+        for (int r = 0; r < g->nranks; r++) tok += all[(size_t)r * nf + K];
+        acc.num_tokens = (int64_t)tok;
+    }
+    GMEM(g, 0, mvhdp_diag_finish(h0, dm, acc, args, out));
+    return MVHDP_OK;
+}

@@ -638,4 +638,98 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupGammaDoc
     env->SetDoubleArrayRegion(out, 0, 2, v);
 }
 
+// ---- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / mvhdp_discr_weights / mvhdp_diagnostics) ----
+// getSortedWords(m) PTM:1792-1811 cut at n: typesFlat / counts [K*n] (unfilled: -1 / 0), nonzero [K]
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nTopWords(JNIEnv* env, jclass, jlong p, jint m, jint n, jintArray types, jintArray counts, jintArray nonzero)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (n < 1 || n > MVHDP_DIAG_MAX_TOP_WORDS) { throw_msg(env, "java/lang/IllegalArgumentException", "topWords: n must be 1..64"); return; }
+    if (bad_len(env, types, (jlong)s->K * n, "topWords types") || bad_len(env, counts, (jlong)s->K * n, "topWords counts") || bad_len(env, nonzero, s->K, "topWords nonzero")) return;
+    Ints t(env, types, 0), c(env, counts, 0), z(env, nonzero, 0);
+    if (t.failed() || c.failed() || z.failed()) return;
+    int rc = mvhdp_top_words(s->h, m, n, t.p, c.p, z.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_top_words");
+}
+
+// calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230: perView [M] = discrWeightPerModality; typeWeight [V_m] or null
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDiscrWeights(JNIEnv* env, jclass, jlong p, jdoubleArray perView, jint m, jdoubleArray typeWeight)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (m < 0 || m >= s->M) { throw_msg(env, "java/lang/IllegalArgumentException", "discrWeights: bad view"); return; }
+    if (bad_len(env, perView, s->M, "discrWeights perView") || (typeWeight && bad_len(env, typeWeight, s->V[m], "discrWeights typeWeight"))) return;
+    Doubles pv(env, perView, 0), tw(env, typeWeight, 0);
+    if (pv.failed() || tw.failed()) return;
+    int rc = mvhdp_discr_weights(s->h, pv.p, m, tw.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_discr_weights");
+}
+
+// the arrays of one mvhdp_diag_out, checked against the shape: scores [13*K], wordScores [13*K*n], codoc [K*n*n], topTypes / topCounts
+// [K*n], nonzero / rank1Docs / nonzeroDocs [K], atProportions [K*7], sumCountLogCount [K], wordTypeCounts [V_0], numTokens [1], perView [M]
+struct DiagArrays {
+    Doubles scores, wordScores; Ints codoc, topTypes, topCounts, nonzero, rank1, nzDocs, props; Doubles scl; Ints wtc; Longs ntok; Doubles perView;
+    Ints wl;
+    bool failed() const
+    {
+        return scores.failed() || wordScores.failed() || codoc.failed() || topTypes.failed() || topCounts.failed() || nonzero.failed() || rank1.failed() ||
+               nzDocs.failed() || props.failed() || scl.failed() || wtc.failed() || ntok.failed() || perView.failed() || wl.failed();
+    }
+    void fill(mvhdp_diag_args& a, mvhdp_diag_out& o, jint n) const
+    {
+        a.num_top_words = n; a.word_length = wl.p;
+        o.scores = scores.p; o.word_scores = wordScores.p; o.codoc = codoc.p; o.top_types = topTypes.p; o.top_counts = topCounts.p;
+        o.nonzero = nonzero.p; o.num_rank1_docs = rank1.p; o.num_nonzero_docs = nzDocs.p; o.num_docs_at_proportions = props.p;
+        o.sum_count_log_count = scl.p; o.word_type_counts = wtc.p; o.num_tokens = (int64_t*)ntok.p; o.discr_weight_per_view = perView.p;
+    }
+};
+
+static bool bad_diag(JNIEnv* env, jint K, jint M, jint V0, jint n, jintArray wordLength, jdoubleArray scores, jdoubleArray wordScores, jintArray codoc,
+                     jintArray topTypes, jintArray topCounts, jintArray nonzero, jintArray rank1, jintArray nzDocs, jintArray props, jdoubleArray scl,
+                     jintArray wtc, jlongArray ntok, jdoubleArray perView)
+{
+    if (n < 1 || n > MVHDP_DIAG_MAX_TOP_WORDS) { throw_msg(env, "java/lang/IllegalArgumentException", "diagnostics: numTopWords must be 1..64"); return true; }
+    const jlong k = K, nn = n;
+    return (wordLength && bad_len(env, wordLength, V0, "diagnostics wordLength")) || bad_len(env, scores, MVHDP_DIAG_ROWS * k, "diagnostics scores") ||
+           bad_len(env, wordScores, MVHDP_DIAG_ROWS * k * nn, "diagnostics wordScores") || bad_len(env, codoc, k * nn * nn, "diagnostics codoc") ||
+           bad_len(env, topTypes, k * nn, "diagnostics topTypes") || bad_len(env, topCounts, k * nn, "diagnostics topCounts") ||
+           bad_len(env, nonzero, k, "diagnostics nonzero") || bad_len(env, rank1, k, "diagnostics rank1Docs") || bad_len(env, nzDocs, k, "diagnostics nonzeroDocs") ||
+           bad_len(env, props, k * MVHDP_DIAG_PROPORTIONS, "diagnostics atProportions") || bad_len(env, scl, k, "diagnostics sumCountLogCount") ||
+           bad_len(env, wtc, V0, "diagnostics wordTypeCounts") || bad_len(env, ntok, 1, "diagnostics numTokens") || bad_len(env, perView, M, "diagnostics perView");
+}
+
+#define DIAG_PARAMS jint n, jintArray wordLength, jdoubleArray scores, jdoubleArray wordScores, jintArray codoc, jintArray topTypes, jintArray topCounts, \
+    jintArray nonzero, jintArray rank1, jintArray nzDocs, jintArray props, jdoubleArray scl, jintArray wtc, jlongArray ntok, jdoubleArray perView
+#define DIAG_ARRAYS DiagArrays da{{env, scores, 0}, {env, wordScores, 0}, {env, codoc, 0}, {env, topTypes, 0}, {env, topCounts, 0}, {env, nonzero, 0}, \
+    {env, rank1, 0}, {env, nzDocs, 0}, {env, props, 0}, {env, scl, 0}, {env, wtc, 0}, {env, ntok, 0}, {env, perView, 0}, {env, wordLength, JNI_ABORT}}
+
+// FastQMVWVTopicModelDiagnostics(model, n) DIAG:53-117 on the device (getSortedWords + collectDocumentStatistics + the score rows)
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDiagnostics(JNIEnv* env, jclass, jlong p, DIAG_PARAMS)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (bad_diag(env, s->K, s->M, s->V[0], n, wordLength, scores, wordScores, codoc, topTypes, topCounts, nonzero, rank1, nzDocs, props, scl, wtc, ntok, perView)) return;
+    DIAG_ARRAYS;
+    if (da.failed()) return;
+    mvhdp_diag_args a{}; mvhdp_diag_out o{};
+    da.fill(a, o, n);
+    int rc = mvhdp_diagnostics(s->h, &a, &o);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_diagnostics");
+}
+
+// the same for the sharded model (mvhdp_group_diagnostics; collective across processes)
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupDiagnostics(JNIEnv* env, jclass, jlong p, DIAG_PARAMS)
+{
+    GroupPin gpin_(p); Group* gr = gpin_.s;
+    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    if (gr->shards.empty()) { throw_msg(env, "java/lang/IllegalStateException", "group has no member"); return; }
+    if (bad_diag(env, gr->K, gr->M, gr->shards[0]->V[0], n, wordLength, scores, wordScores, codoc, topTypes, topCounts, nonzero, rank1, nzDocs, props, scl, wtc, ntok, perView)) return;
+    DIAG_ARRAYS;
+    if (da.failed()) return;
+    mvhdp_diag_args a{}; mvhdp_diag_out o{};
+    da.fill(a, o, n);
+    int rc = mvhdp_group_diagnostics(gr->g, &a, &o);
+    if (rc) throw_group(env, gr->g, rc, "mvhdp_group_diagnostics");
+}
+
 }  // extern "C"

@@ -104,6 +104,38 @@ public final class NativeSampler implements AutoCloseable {
      * library's walk-threshold search has found -- read them from one sampler and hand them to another (a document shard, a
      * resumed chain) and it does not search again.
      */
+    /** getSortedWords(m) PTM:1792-1811 cut at n (1..64): typesFlat / counts [K*n] (unfilled slots -1 / 0), nonzero [K] = sortedWords.size(). */
+    public void topWords(int m, int n, int[] typesFlat, int[] counts, int[] nonzero) { nTopWords(handle, m, n, typesFlat, counts, nonzero); }
+    /** calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230: discrWeightPerModality [M]; typeWeight [V_m] = typeDiscrWeight[m], or null. */
+    public double[] discrWeights(int numModalities, int m, double[] typeWeight) { double[] w = new double[numModalities]; nDiscrWeights(handle, w, m, typeWeight); return w; }
+
+    /** What FastQMVWVTopicModelDiagnostics(model, numTopWords) computes (DIAG:53-236): scores [13*K] in the row order of DIAG:104-116
+     *  (TopicScores.scores), wordScores [13*K*N] (topicWordScores), the co-document matrices [K*N*N], the view-0 top words and the
+     *  accumulators of collectDocumentStatistics, discrWeightPerModality. */
+    public static final class Diagnostics {
+        public static final String[] ROWS = {"tokens", "document_entropy", "word-length", "coherence", "normDiscrWeight", "discrWeight", "uniform_dist",
+                                             "corpus_dist", "eff_num_words", "token-doc-diff", "rank_1_docs", "allocation_ratio", "allocation_count"};
+        public final int numTopics, numTopWords;
+        public final double[] scores, wordScores, sumCountLogCount, discrWeightPerModality;
+        public final int[] codoc, topTypes, topCounts, nonzero, numRank1Documents, numNonZeroDocuments, numDocumentsAtProportions, wordTypeCounts;
+        public final long[] numTokens = new long[1];
+        Diagnostics(int K, int N, int V0, int M) {
+            numTopics = K; numTopWords = N;
+            scores = new double[ROWS.length * K]; wordScores = new double[ROWS.length * K * N]; sumCountLogCount = new double[K];
+            discrWeightPerModality = new double[M]; codoc = new int[K * N * N]; topTypes = new int[K * N]; topCounts = new int[K * N];
+            nonzero = new int[K]; numRank1Documents = new int[K]; numNonZeroDocuments = new int[K]; numDocumentsAtProportions = new int[K * 7];
+            wordTypeCounts = new int[V0];
+        }
+        public double score(int row, int topic) { return scores[row * numTopics + topic]; }
+    }
+    /** wordLength: String.length() of every view-0 type (alphabet[0]), or null (the word-length row is then NaN). */
+    public Diagnostics diagnostics(int numTopics, int numTypes0, int numModalities, int numTopWords, int[] wordLength) {
+        Diagnostics d = new Diagnostics(numTopics, numTopWords, numTypes0, numModalities);
+        nDiagnostics(handle, numTopWords, wordLength, d.scores, d.wordScores, d.codoc, d.topTypes, d.topCounts, d.nonzero, d.numRank1Documents,
+                     d.numNonZeroDocuments, d.numDocumentsAtProportions, d.sumCountLogCount, d.wordTypeCounts, d.numTokens, d.discrWeightPerModality);
+        return d;
+    }
+
     public static final class Tuning {
         public int forcePrimary, narrow = -1, walkFixed, singleStream, live16 = -1;
         public int[] learntWalkStep = {-1, -1, -1};
@@ -190,6 +222,13 @@ public final class NativeSampler implements AutoCloseable {
         public void getCountHistogram(int m, int[] hist) { nGroupGetCountHistogram(g, m, hist); }
         public double[] viewOverlapSums(int numModalities) { double[] s = new double[numModalities * numModalities]; nGroupViewOverlapSums(g, s); return s; }
         public double[] gammaDocStatistics(int m, double gammaM, long seed, int round) { double[] o = new double[2]; nGroupGammaDocStatistics(g, m, gammaM, seed, round, o); return o; }
+        /** the diagnostics of the whole sharded model; top words and discrimination weights are any member's (topWords / discrWeights there) */
+        public Diagnostics diagnostics(int numTopics, int numTypes0, int numModalities, int numTopWords, int[] wordLength) {
+            Diagnostics d = new Diagnostics(numTopics, numTopWords, numTypes0, numModalities);
+            nGroupDiagnostics(g, numTopWords, wordLength, d.scores, d.wordScores, d.codoc, d.topTypes, d.topCounts, d.nonzero, d.numRank1Documents,
+                              d.numNonZeroDocuments, d.numDocumentsAtProportions, d.sumCountLogCount, d.wordTypeCounts, d.numTokens, d.discrWeightPerModality);
+            return d;
+        }
 
         @Override
         public void close() { if (g != 0) { nGroupDestroy(g); g = 0; } }
@@ -240,4 +279,12 @@ public final class NativeSampler implements AutoCloseable {
     private static native void nGroupGetCountHistogram(long g, int m, int[] hist);
     private static native void nGroupViewOverlapSums(long g, double[] sums);
     private static native void nGroupGammaDocStatistics(long g, int m, double gammaM, long seed, int round, double[] out);
+    private static native void nTopWords(long h, int m, int n, int[] typesFlat, int[] counts, int[] nonzero);
+    private static native void nDiscrWeights(long h, double[] perView, int m, double[] typeWeight);
+    private static native void nDiagnostics(long h, int n, int[] wordLength, double[] scores, double[] wordScores, int[] codoc, int[] topTypes,
+                                            int[] topCounts, int[] nonzero, int[] rank1Docs, int[] nonzeroDocs, int[] atProportions,
+                                            double[] sumCountLogCount, int[] wordTypeCounts, long[] numTokens, double[] perView);
+    private static native void nGroupDiagnostics(long g, int n, int[] wordLength, double[] scores, double[] wordScores, int[] codoc, int[] topTypes,
+                                                 int[] topCounts, int[] nonzero, int[] rank1Docs, int[] nonzeroDocs, int[] atProportions,
+                                                 double[] sumCountLogCount, int[] wordTypeCounts, long[] numTokens, double[] perView);
 }

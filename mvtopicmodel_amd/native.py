@@ -11,7 +11,8 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (MAX_M, UNIQUE_ID_BYTES, Config, DebugC, GroupInfoC, HyperC, MvhdpError, SweepStatsC, TuningC, load_library)
+from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
+                   GroupInfoC, HyperC, MvhdpError, SweepStatsC, TuningC, load_library)
 
 SWEEP_REUSE_TREES = 0x1
 SWEEP_NO_APPLY = 0x2
@@ -100,6 +101,61 @@ class SweepStats:
     reserved: int = 0
     dbg: list = field(default=None, repr=False)
     trace: np.ndarray = field(default=None, repr=False)
+
+
+def java_string_lengths(vocabulary):
+    """String.length() of every word: UTF-16 code units (a character outside the BMP counts twice)."""
+    return np.array([len(str(w).encode("utf-16-le")) // 2 for w in vocabulary], dtype=np.int32)
+
+
+@dataclass
+class Diagnostics:
+    """What mvhdp_diagnostics returns (FastQMVWVTopicModelDiagnostics, DIAG:53-236): the thirteen score rows by name (DIAG:104-116),
+    the topic-word scores of the same rows ([K][N]; zero for the rows that define none), the co-document matrices and the
+    accumulators of collectDocumentStatistics, the view-0 top words and discrWeightPerModality (PTM:2181-2230)."""
+    scores: dict
+    word_scores: dict
+    codoc: np.ndarray                   # [K][N][N]
+    top_words: np.ndarray               # [K][N] view-0 type ids, -1 where a topic has fewer than N words
+    top_counts: np.ndarray              # [K][N]
+    nonzero: np.ndarray                 # [K] words with n_wk > 0
+    num_rank1_docs: np.ndarray          # [K]
+    num_nonzero_docs: np.ndarray        # [K]
+    num_docs_at_proportions: np.ndarray  # [K][7]
+    sum_count_log_count: np.ndarray     # [K]
+    word_type_counts: np.ndarray        # [V_0]
+    num_tokens: int
+    discr_weight_per_view: np.ndarray   # [M]
+
+
+def _run_diagnostics(L, fn, handle, K, V0, M, num_top_words, vocabulary, word_length):
+    N = int(num_top_words)
+    if word_length is None and vocabulary is not None:
+        if len(vocabulary) != V0:
+            raise ValueError(f"vocabulary has {len(vocabulary)} words, view 0 has {V0} types")
+        word_length = java_string_lengths(vocabulary)
+    wl = None if word_length is None else np.ascontiguousarray(word_length, dtype=np.int32)
+    if wl is not None and wl.shape != (V0,):
+        raise ValueError("word_length must be [V_0]")
+    nn = max(N, 1)
+    R = len(DIAG_ROWS)
+    a = dict(scores=np.zeros((R, K)), word_scores=np.zeros((R, K, nn)), codoc=np.zeros((K, nn, nn), np.int32),
+             top_types=np.zeros((K, nn), np.int32), top_counts=np.zeros((K, nn), np.int32), nonzero=np.zeros(K, np.int32),
+             num_rank1_docs=np.zeros(K, np.int32), num_nonzero_docs=np.zeros(K, np.int32),
+             num_docs_at_proportions=np.zeros((K, DIAG_PROPORTIONS), np.int32), sum_count_log_count=np.zeros(K),
+             word_type_counts=np.zeros(V0, np.int32), num_tokens=np.zeros(1, np.int64), discr_weight_per_view=np.zeros(M))
+    args = DiagArgsC(N, None if wl is None else wl.ctypes.data)
+    out = DiagOutC(**{f: a[f].ctypes.data for f, _ in DiagOutC._fields_})
+    rc = fn(handle, C.byref(args), C.byref(out))
+    if rc != 0:
+        return rc, None
+    return 0, Diagnostics(scores={n: a["scores"][i] for i, n in enumerate(DIAG_ROWS)},
+                          word_scores={n: a["word_scores"][i] for i, n in enumerate(DIAG_ROWS)},
+                          codoc=a["codoc"], top_words=a["top_types"], top_counts=a["top_counts"], nonzero=a["nonzero"],
+                          num_rank1_docs=a["num_rank1_docs"], num_nonzero_docs=a["num_nonzero_docs"],
+                          num_docs_at_proportions=a["num_docs_at_proportions"], sum_count_log_count=a["sum_count_log_count"],
+                          word_type_counts=a["word_type_counts"], num_tokens=int(a["num_tokens"][0]),
+                          discr_weight_per_view=a["discr_weight_per_view"])
 
 
 class NativeSampler:
@@ -271,6 +327,31 @@ class NativeSampler:
         out = np.zeros((max(d1 - int(d0), 0), self.K), dtype=np.float64)
         self._ck(self.L.mvhdp_doc_topic_proportions(self.h, _ptr(w), int(d0), d1, _ptr(out)))
         return out
+
+    # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
+    def top_words(self, m, n):
+        """getSortedWords(m) PTM:1792-1811 cut at n: (types [K][n] (-1 unfilled), counts [K][n], nonzero [K])."""
+        n = int(n)
+        nn = max(n, 1)
+        t = np.zeros((self.K, nn), np.int32)
+        c = np.zeros((self.K, nn), np.int32)
+        z = np.zeros(self.K, np.int32)
+        self._ck(self.L.mvhdp_top_words(self.h, int(m), n, _ptr(t), _ptr(c), _ptr(z)))
+        return t, c, z
+
+    def discr_weights(self, m=None):
+        """calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230: discrWeightPerModality [M]; with a view m also typeDiscrWeight[m] [V_m]."""
+        pv = np.zeros(self.M, dtype=np.float64)
+        tw = None if m is None else np.zeros(self.V[int(m)], dtype=np.float64)
+        self._ck(self.L.mvhdp_discr_weights(self.h, _ptr(pv), 0 if m is None else int(m), _ptr(tw)))
+        return pv if m is None else (pv, tw)
+
+    def diagnostics(self, num_top_words=20, vocabulary=None, word_length=None):
+        """FastQMVWVTopicModelDiagnostics(model, num_top_words) DIAG:53-117 on the device.  vocabulary: the view-0 words (their Java
+        String.length() feeds the word-length row), or word_length [V_0] directly; neither: that row is NaN."""
+        rc, d = _run_diagnostics(self.L, self.L.mvhdp_diagnostics, self.h, self.K, self.V[0], self.M, num_top_words, vocabulary, word_length)
+        self._ck(rc)
+        return d
 
     # -- the hot path ---------------------------------------------------------
     def sweep(self, sweep_idx, seed, flags=0, p=None, want_dbg=False, trace=None) -> SweepStats:
@@ -514,6 +595,14 @@ class NativeGroup:
         qs, qw = C.c_double(), C.c_double()
         self._ck(self.L.mvhdp_group_gamma_doc_statistics(self.g, int(m), float(gamma_m), int(seed), int(round_idx), C.byref(qs), C.byref(qw)))
         return qs.value, qw.value
+
+    def diagnostics(self, num_top_words=20, vocabulary=None, word_length=None):
+        """NativeSampler.diagnostics of the whole sharded model (mvhdp_group_diagnostics).  Top words and discrimination weights of a
+        group are those of any member: NativeSampler.top_words / discr_weights on one of them."""
+        s0 = self.members[0]
+        rc, d = _run_diagnostics(self.L, self.L.mvhdp_group_diagnostics, self.g, s0.K, s0.V[0], s0.M, num_top_words, vocabulary, word_length)
+        self._ck(rc)
+        return d
 
     def sweep(self, sweep_idx, seed, flags=0):
         """One sweep of the whole model; the list of the local members' statistics."""
