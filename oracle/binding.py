@@ -87,6 +87,9 @@ def lib():
     L.orc_get_doc_topic_hist.argtypes = [vp, C.c_int, vp, i32, vp, i32]
     L.orc_draw_p_mallet.argtypes = [vp, P(JRand), vp]
     L.orc_draw_p_philox.argtypes = [vp, u64, u32, i64, vp]
+    L.orc_gamma_doc_stats_philox.argtypes = [vp, C.c_int, dbl, u64, u32, i64, P(dbl), P(dbl), vp, vp]
+    L.orc_dp_tables_philox.argtypes = [vp, i32, C.c_int, C.c_int, vp, u64, u32, vp, vp]
+    L.orc_antoniak_draws_philox.argtypes = [i32, vp, vp, u64, u32, vp]
     L.orc_sweep.argtypes = [vp, u32, u64, i64, vp, u32, P(Stats), vp, vp, vp, C.c_int, vp, vp, vp, vp]
     L.orc_sweep.restype = C.c_int
     L.orc_sweep_list.argtypes = [vp, u32, u64, i64, vp, u32, P(Stats), vp, vp, vp, i64]
@@ -232,6 +235,18 @@ class Oracle:
         self.L.orc_draw_p_philox(self.h, int(seed), int(sweep), int(doc_id_base), _ptr(p))
         return p
 
+    def gamma_doc_stats_philox(self, m, gamma_m, seed, round_idx, doc_id_base=0, per_entity=False):
+        """mvhdp_gamma_doc_statistics's contract: (qs, qw) in the device's summation order, and with per_entity the
+        per-entity Bernoulli bits [D] (uint8) and qw terms [D] (0 where the entity is skipped)."""
+        qs, qw = C.c_double(), C.c_double()
+        eb = np.zeros(max(self.D, 1), dtype=np.uint8) if per_entity else None
+        ew = np.zeros(max(self.D, 1), dtype=np.float64) if per_entity else None
+        self.L.orc_gamma_doc_stats_philox(self.h, int(m), float(gamma_m), int(seed), int(round_idx), int(doc_id_base),
+                                          C.byref(qs), C.byref(qw), _ptr(eb), _ptr(ew))
+        if per_entity:
+            return qs.value, qw.value, eb[: self.D], ew[: self.D]
+        return qs.value, qw.value
+
     def sweep(self, sweep_idx, seed, p=None, flags=0, doc_id_base=0, want_delta=False,
               want_dbg=False, trace=None):
         """Returns dict(stats=..., delta_nwk, delta_nk, dbg=[per-view (N,4)], trace=(n,K+1))."""
@@ -318,3 +333,27 @@ class Oracle:
         st = Stats()
         secs = self.L.orc_threaded_estimate(self.h, int(num_threads), int(iters), int(seed), C.byref(st))
         return secs, st.as_dict()
+
+
+def dp_tables_philox(hist, conc, m, seed, round_idx):
+    """mvhdp_dp_table_statistics's contract: hist [K][hist_len] int32, conc [K] -> (mk [K] float64, active [K] uint8)."""
+    L = lib()
+    hist = np.ascontiguousarray(hist, dtype=np.int32)
+    conc = np.ascontiguousarray(conc, dtype=np.float64)
+    K, hist_len = hist.shape
+    assert conc.shape == (K,)
+    mk = np.zeros(K, dtype=np.float64)
+    act = np.zeros(K, dtype=np.uint8)
+    L.orc_dp_tables_philox(_ptr(hist), int(hist_len), int(K), int(m), _ptr(conc), int(seed), int(round_idx), _ptr(mk), _ptr(act))
+    return mk, act
+
+
+def antoniak_draws_philox(items, conc, seed, round_idx):
+    """mvhdp_antoniak_draws's contract: tables [n] int32."""
+    L = lib()
+    items = np.ascontiguousarray(items, dtype=np.int32)
+    conc = np.ascontiguousarray(conc, dtype=np.float64)
+    assert items.shape == conc.shape and items.ndim == 1
+    out = np.zeros(len(items), dtype=np.int32)
+    L.orc_antoniak_draws_philox(len(items), _ptr(items), _ptr(conc), int(seed), int(round_idx), _ptr(out))
+    return out

@@ -550,6 +550,127 @@ void orc_draw_p_philox(const orc_model* o, uint64_t seed, uint32_t sweep, int64_
 }
 
 /* ------------------------------------------------------------------------ */
+/* the optimize steps' device streams (mvhdp_stats.hip: gamma_doc_stats_kernel, */
+/* dp_tables_kernel, antoniak_draws_kernel), restated from their contract     */
+/* ------------------------------------------------------------------------ */
+
+/* PhiloxStream::uniform: one Philox call gives two uniforms, x0,x1 first, then x2,x3; c0 counts the calls. */
+typedef struct { uint32_t ctr[4], key[2], x[4]; int have; } orc_pstream;
+
+static double ps_uniform(orc_pstream* r)
+{
+    if (r->have == 0) { orc_philox4x32_10(r->ctr, r->key, r->x); r->ctr[0]++; r->have = 2; }
+    r->have--;
+    return r->have == 1 ? bits_to_unit(r->x[0], r->x[1]) : bits_to_unit(r->x[2], r->x[3]);
+}
+
+/* Marsaglia & Tsang (2000), a >= 1, normals by Box-Muller: the kernel's loop, expression for expression */
+static double ps_mt_gamma(orc_pstream* r, double a)
+{
+    const double d = a - 1.0 / 3.0, c = 1.0 / sqrt(9.0 * d);
+    for (;;) {
+        double u1 = ps_uniform(r), u2 = ps_uniform(r);
+        if (u1 <= 0.0) u1 = 0x1.0p-53;
+        const double n = sqrt(-2.0 * log(u1)) * cos(2.0 * M_PI * u2);
+        const double t = 1.0 + c * n;
+        if (t <= 0.0) continue;
+        const double v = t * t * t;
+        double u = ps_uniform(r);
+        if (u <= 0.0) u = 0x1.0p-53;
+        if (u < 1.0 - 0.0331 * (n * n) * (n * n)) return d * v;
+        if (log(u) < 0.5 * n * n + d * (1.0 - v + log(v))) return d * v;
+    }
+}
+
+/* the fixed-order reduction of a 256-thread block: sh[t] += sh[t + s] for s = 128, 64, ..., 1 */
+static double block_tree_sum(double* sh)
+{
+    for (int s = 128; s >= 1; s >>= 1)
+        for (int t = 0; t < s; t++) sh[t] += sh[t + s];
+    return sh[0];
+}
+
+#define ORC_GAMMA_NB 1024   /* mvhdp_gamma_doc_statistics: 1024 blocks of 256 threads, partials summed on the host in block order */
+
+void orc_gamma_doc_stats_philox(const orc_model* o, int m, double gamma_m, uint64_t seed, uint32_t round, int64_t doc_id_base,
+                                double* qs, double* qw, uint8_t* ent_qs, double* ent_qw)
+{
+    const int64_t nthr = (int64_t)ORC_GAMMA_NB * 256;
+    double* acc = (double*)calloc((size_t)nthr * 2, sizeof(double));     /* [thread][qs, qw] */
+    for (int64_t d = 0; d < o->D; d++) {                                  /* thread d % nthr visits its entities in order */
+        const int64_t j = o->doc_off[m][d + 1] - o->doc_off[m][d];
+        if (ent_qs) ent_qs[d] = 0;
+        if (ent_qw) ent_qw[d] = 0.0;
+        if (j <= 0) continue;                                             /* no view, or present but empty */
+        const int64_t dg = doc_id_base + d;
+        orc_pstream r;
+        r.ctr[0] = 0; r.ctr[1] = 0x200u + (uint32_t)m; r.ctr[2] = (uint32_t)dg; r.ctr[3] = round;
+        r.key[0] = (uint32_t)seed; r.key[1] = (uint32_t)(seed >> 32) ^ (uint32_t)((uint64_t)dg >> 32); r.have = 0;
+        const int bit = ps_uniform(&r) < (double)j / ((double)j + gamma_m);
+        const double ga = ps_mt_gamma(&r, gamma_m + 1.0), gb = ps_mt_gamma(&r, (double)j);
+        const double w = log(ga / (ga + gb));
+        double* a = acc + 2 * (d % nthr);
+        a[0] += bit ? 1.0 : 0.0;
+        a[1] += w;
+        if (ent_qs) ent_qs[d] = (uint8_t)bit;
+        if (ent_qw) ent_qw[d] = w;
+    }
+    double sh0[256], sh1[256], s0 = 0, s1 = 0;
+    for (int b = 0; b < ORC_GAMMA_NB; b++) {
+        for (int t = 0; t < 256; t++) { sh0[t] = acc[2 * ((int64_t)b * 256 + t)]; sh1[t] = acc[2 * ((int64_t)b * 256 + t) + 1]; }
+        s0 += block_tree_sum(sh0);
+        s1 += block_tree_sum(sh1);
+    }
+    *qs = s0; *qw = s1;
+    free(acc);
+}
+
+/* one CRP(a) of i > 1 items from the stream of cell (view m, topic t, count i): table l + 1 opens with probability a / (a + l) */
+void orc_dp_tables_philox(const int32_t* hist, int32_t hist_len, int K, int m, const double* conc, uint64_t seed, uint32_t round,
+                          double* mk, uint8_t* active)
+{
+    double sh[256];
+    for (int t = 0; t < K; t++) {
+        const double a = conc[t];
+        int any = 0;
+        for (int x = 0; x < 256; x++) sh[x] = 0.0;
+        for (int i = 1; i < hist_len; i++) {                              /* thread (i - 1) % 256 takes count i */
+            const int32_t n = hist[(int64_t)t * hist_len + i];
+            if (n <= 0) continue;
+            any = 1;
+            double* acc = &sh[(i - 1) % 256];
+            if (i == 1) { *acc += (double)n; continue; }
+            int tables = 1;
+            if (a > 0.0) {
+                orc_pstream r;
+                r.ctr[0] = 0; r.ctr[1] = 0x300u + (uint32_t)m; r.ctr[2] = (uint32_t)t; r.ctr[3] = (uint32_t)i;
+                r.key[0] = (uint32_t)seed ^ round; r.key[1] = (uint32_t)(seed >> 32); r.have = 0;
+                for (int l = 1; l < i; l++) tables += (ps_uniform(&r) * (a + (double)l) < a) ? 1 : 0;
+            }
+            *acc += (double)n * (double)tables;
+        }
+        mk[t] = block_tree_sum(sh);
+        active[t] = (uint8_t)any;
+    }
+}
+
+void orc_antoniak_draws_philox(int32_t n, const int32_t* items, const double* conc, uint64_t seed, uint32_t round, int32_t* tables)
+{
+    for (int32_t j = 0; j < n; j++) {
+        const int32_t it = items[j];
+        const double a = conc[j];
+        int32_t t = it <= 0 ? 0 : 1;
+        if (it > 1 && it <= 20000 && a > 0.0) {                          /* MAXSTIRLING: beyond it the reference falls back to 1 */
+            orc_pstream r;
+            r.ctr[0] = 0; r.ctr[1] = 0x400u; r.ctr[2] = (uint32_t)j; r.ctr[3] = round;
+            r.key[0] = (uint32_t)seed; r.key[1] = (uint32_t)(seed >> 32); r.have = 0;
+            for (int l = 1; l < it; l++) t += (ps_uniform(&r) * (a + (double)l) < a) ? 1 : 0;
+        }
+        tables[j] = t;
+    }
+}
+
+/* ------------------------------------------------------------------------ */
 /* the sweep                                                                 */
 /* ------------------------------------------------------------------------ */
 

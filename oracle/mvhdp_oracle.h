@@ -116,6 +116,26 @@ void orc_draw_p_mallet(const orc_model* o, orc_jrand* r, double* p);
  * Philox uniform stream (no state carried between docs). */
 void orc_draw_p_philox(const orc_model* o, uint64_t seed, uint32_t sweep, int64_t doc_id_base, double* p);
 
+/* The optimize steps' device streams (mvhdp_stats.hip), restated from their contract -- not from the
+ * reference's samplers, whose streams cannot be seeded.  Each entity / cell / draw owns a Philox stream;
+ * one call gives two uniforms (words 0,1 then 2,3), c0 counts the calls.
+ * optimizeGamma's document level (PTM:2415-2433): entity d with j = len > 0 of view m, dg = doc_id_base + d,
+ * ctr (c0, 0x200+m, dg_lo, round), key (seed_lo, seed_hi ^ dg_hi); Bernoulli u < j/(j+gamma), then
+ * Marsaglia-Tsang Gamma(gamma+1) and Gamma(j), qw term log(ga/(ga+gb)).  qs/qw are summed in the device's
+ * order (1024 blocks x 256 threads, grid stride, block tree, blocks in order on the host); ent_qs/ent_qw
+ * (optional, [D]) get the per-entity Bernoulli bit and qw term (0 where the entity is skipped). */
+void orc_gamma_doc_stats_philox(const orc_model* o, int m, double gamma_m, uint64_t seed, uint32_t round, int64_t doc_id_base,
+                                double* qs, double* qw, uint8_t* ent_qs, double* ent_qw);
+/* optimizeDP's view tables (PTM:2454-2488): hist[K][hist_len]; cell (t, i > 1) with n > 0 entities adds
+ * n * (1 + #{l in 1..i-1 : u_l (conc_t + l) < conc_t}), ctr (c0, 0x300+m, t, i), key (seed_lo ^ round, seed_hi);
+ * i == 1 adds n; conc_t <= 0 or NaN: one table.  active[t] = some cell i >= 1 holds an entity.  mk[t] in the
+ * kernel's order (count i on thread (i-1) % 256, block tree). */
+void orc_dp_tables_philox(const int32_t* hist, int32_t hist_len, int K, int m, const double* conc, uint64_t seed, uint32_t round,
+                          double* mk, uint8_t* active);
+/* optimizeDP's root level (PTM:2491-2517): tables[j] for items[j] in a CRP(conc[j]), ctr (c0, 0x400, j, round),
+ * key (seed_lo, seed_hi); items <= 0: 0, items == 1 or > 20000 (MAXSTIRLING) or conc <= 0: 1. */
+void orc_antoniak_draws_philox(int32_t n, const int32_t* items, const double* conc, uint64_t seed, uint32_t round, int32_t* tables);
+
 #define ORC_SWEEP_REUSE_TREES 1u  /* do not rebuild trees from the snapshot first */
 #define ORC_SWEEP_NO_APPLY    2u  /* leave n_wk/n_k untouched; deltas returned */
 #define ORC_SWEEP_FROZEN      16u /* the inferencer's mode (INF:211-212 nst=1, nut=0): stored trees, no deltas at all */
