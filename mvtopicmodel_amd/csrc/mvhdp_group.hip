@@ -231,8 +231,10 @@ static bool members_live(mvhdp_group_ctx* g)
 #define GHIP(g, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { (g)->err = std::string(#call) + ": " + hipGetErrorString(e_); return MVHDP_ERR_HIP; } } while (0)
 #define GNCCL(g, call) do { ncclResult_t r_ = (call); if (r_ != ncclSuccess) { \
     (g)->err = std::string(#call) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r_) : "RCCL error"); return MVHDP_ERR_HIP; } } while (0)
-#define GMEM(g, i, call) do { int rc_ = (call); if (rc_ != MVHDP_OK) { \
-    (g)->err = "member " + std::to_string(i) + ": " + (g)->members[i]->err; return rc_; } } while (0)
+#define GMEM(g, i, call) do { int rc_ = (call); if (rc_ != MVHDP_OK) { (g)->err = member_msg(g, i); return rc_; } } while (0)
+
+// what a failed call of member i said, as the group reports it
+static std::string member_msg(const mvhdp_group_ctx* g, size_t i) { return "member " + std::to_string(i) + ": " + g->members[i]->err; }
 
 extern "C" const char* mvhdp_group_last_error(mvhdp_group g)
 {
@@ -440,17 +442,50 @@ extern "C" int mvhdp_group_set_exchange_chunks(mvhdp_group g, int32_t chunks)
     return MVHDP_OK;
 }
 
-// ---- the exchange: buffer `which` of every member becomes the sum over ALL members of all ranks ----
-// Stream order throughout, no host wait: co-located members are added into their device's leader, the leaders all-reduce the
-// element range [e0, e1) (RCCL, in place, on the leader's stream), and ev_reduced[l] marks the range complete on leader l.
-// None of the three returns before it has issued everything it was asked to issue: a local HIP failure is remembered (first error
-// wins, g->err says what) and the calls go on -- a rank that stops half way through an exchange leaves its peers inside a collective.
+// ---- the failure protocol (one process per GPU): a rank never leaves its peers inside a collective ----
+// Whatever fails locally, every rank enters the SAME collectives (count, type, operation, order), whose number depends only on
+// replicated facts: the chunk count, the segment count taken from the flags, whether the hyper-parameters hold inactive topics, the
+// arguments of a statistic.  A rank whose own part failed (or whose host called mvhdp_group_abort) contributes zeros and a raised
+// status word -- the sweep and the recount: behind the tokensPerTopic part of the buffer; the statistics: a slot behind the message --
+// so every rank reads the failure from the summed result and all return an error from the same call.  Between a local failure and
+// the collectives after it nothing returns and no device memory is allocated.  After a failed sweep the replicas agree with each
+// other but not with the failed rank's assignments: mvhdp_group_build_counts (a recount from z, collective) makes the model
+// consistent again.  A rank that fails LATER in a step (a HIP call of its own exchange) returns its error alone, having entered every
+// collective: its host raises mvhdp_group_abort and calls the next sweep, which then fails on every rank together.  Whoever does not
+// apply the sum leaves a delta buffer that is marked dirty: the next sweep (or the recount) clears it before anything is added to it.
+// The pieces: XErr (failures are recorded, the calls go on), leaders_allreduce (every collective), sweep_members (the sweeps of a
+// step), land_exchange (an asynchronous exchange lands), GroupStat with xrank_sum_f64 / xrank_sum_i32 (the statistics).
+
+// the first failure of a sequence of calls that must all be issued (the first one wins, g->err says what)
 struct XErr {
     mvhdp_group_ctx* g;
     int rc = MVHDP_OK;
-    void hip(hipError_t e, const char* what) { if (e != hipSuccess && rc == MVHDP_OK) { rc = MVHDP_ERR_HIP; g->err = std::string(what) + ": " + hipGetErrorString(e); } }
-    void nccl(ncclResult_t r, const char* what) { if (r != ncclSuccess && rc == MVHDP_OK) { rc = MVHDP_ERR_HIP; g->err = std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "RCCL error"); } }
+    void note(int r, const std::string& what) { if (r != MVHDP_OK && rc == MVHDP_OK) { rc = r; g->err = what; } }
+    bool member(size_t i, int r) { if (r != MVHDP_OK) note(r, member_msg(g, i)); return r == MVHDP_OK; }
+    void hip(hipError_t e, const char* what) { if (e != hipSuccess) note(MVHDP_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+    void nccl(ncclResult_t r, const char* what) { if (r != ncclSuccess) note(MVHDP_ERR_HIP, std::string(what) + ": " + (g_rccl.GetErrorString ? g_rccl.GetErrorString(r) : "RCCL error")); }
 };
+
+// One in-place all-reduce of `count` elements over every leader's buffer buf_of(l), on its own stream (or streams[l]): one RCCL group
+// when this process drives several devices.  The caller decides whether the collective exists (communicators, a non-empty range).
+template <class BufOf>
+static void leaders_allreduce(mvhdp_group_ctx* g, XErr& x, size_t count, ncclDataType_t type, ncclRedOp_t op, const char* what, BufOf buf_of,
+                              const std::vector<hipStream_t>* streams = nullptr)
+{
+    const bool grouped = g->comms.size() > 1;
+    if (grouped) x.nccl(g_rccl.GroupStart(), "ncclGroupStart");
+    for (size_t l = 0; l < g->leaders.size(); l++) {
+        mvhdp_ctx* L = g->members[g->leaders[l]];
+        x.hip(hipSetDevice(L->device), "hipSetDevice");
+        void* buf = buf_of(l);
+        x.nccl(g_rccl.AllReduce(buf, buf, count, type, op, g->comms[l], streams ? (*streams)[l] : L->stream), what);
+    }
+    if (grouped) x.nccl(g_rccl.GroupEnd(), "ncclGroupEnd");
+}
+
+// ---- the exchange: buffer `which` of every member becomes the sum over ALL members of all ranks ----
+// Stream order throughout, no host wait: co-located members are added into their device's leader, the leaders all-reduce the
+// element range [e0, e1) (RCCL, in place, on the leader's stream), and ev_reduced[l] marks the range complete on leader l.
 
 static int reduce_local(mvhdp_group_ctx* g, bool counts)
 {
@@ -471,16 +506,11 @@ static int reduce_local(mvhdp_group_ctx* g, bool counts)
 static int allreduce_range(mvhdp_group_ctx* g, bool counts, int64_t e0, int64_t e1)
 {
     if (e1 <= e0 || g->comms.empty()) return MVHDP_OK;
-    Rccl* r = &g_rccl;
     XErr x{g};
-    if (g->comms.size() > 1) x.nccl(r->GroupStart(), "ncclGroupStart");
-    for (size_t l = 0; l < g->leaders.size(); l++) {
+    leaders_allreduce(g, x, (size_t)(e1 - e0), ncclInt32, ncclSum, "ncclAllReduce", [&](size_t l) {
         mvhdp_ctx* L = g->members[g->leaders[l]];
-        x.hip(hipSetDevice(L->device), "hipSetDevice");
-        int32_t* buf = (counts ? L->mm.counts : L->mm.delta) + e0;
-        x.nccl(r->AllReduce(buf, buf, (size_t)(e1 - e0), ncclInt32, ncclSum, g->comms[l], L->stream), "ncclAllReduce");
-    }
-    if (g->comms.size() > 1) x.nccl(r->GroupEnd(), "ncclGroupEnd");
+        return (counts ? L->mm.counts : L->mm.delta) + e0;
+    });
     return x.rc;
 }
 
@@ -540,11 +570,10 @@ static int pack_prepare(mvhdp_group_ctx* g)
 
 static void pack_reset(mvhdp_group_ctx* g) { g->pack_on = false; g->pack_ready = false; g->pack_hash = 0; g->sweeps_since_counts = 0; }
 
-// rows [r0, r1) of every leader's delta buffer, packed, all-reduced and unpacked again: in stream order, nothing returns early
+// rows [r0, r1) of every leader's delta buffer, packed, all-reduced and unpacked again, in stream order
 static int allreduce_rows_packed(mvhdp_group_ctx* g, int64_t r0, int64_t r1)
 {
     XErr x{g};
-    Rccl* r = &g_rccl;
     const int64_t w0 = g->woff[(size_t)r0], w1 = g->woff[(size_t)r1];
     const int K = g->members[0]->mm.K;
     const int grid = (int)std::min<int64_t>((r1 - r0 + 3) / 4, 8192);
@@ -554,15 +583,8 @@ static int allreduce_rows_packed(mvhdp_group_ctx* g, int64_t r0, int64_t r1)
         hipLaunchKernelGGL(pack_rows_kernel, dim3(std::max(grid, 1)), dim3(256), 0, L->stream, L->mm.delta, g->d_cls[l], g->d_woff[l], g->xpack[l], r0, r1, K);
         x.hip(hipGetLastError(), "pack_rows_kernel");
     }
-    if (!g->comms.empty() && w1 > w0) {
-        if (g->comms.size() > 1) x.nccl(r->GroupStart(), "ncclGroupStart");
-        for (size_t l = 0; l < g->leaders.size(); l++) {
-            mvhdp_ctx* L = g->members[g->leaders[l]];
-            x.hip(hipSetDevice(L->device), "hipSetDevice");
-            x.nccl(r->AllReduce(g->xpack[l] + w0, g->xpack[l] + w0, (size_t)(w1 - w0), ncclInt32, ncclSum, g->comms[l], L->stream), "ncclAllReduce");
-        }
-        if (g->comms.size() > 1) x.nccl(r->GroupEnd(), "ncclGroupEnd");
-    }
+    if (!g->comms.empty() && w1 > w0)
+        leaders_allreduce(g, x, (size_t)(w1 - w0), ncclInt32, ncclSum, "ncclAllReduce", [&](size_t l) { return g->xpack[l] + w0; });
     for (size_t l = 0; l < g->leaders.size(); l++) {
         mvhdp_ctx* L = g->members[g->leaders[l]];
         x.hip(hipSetDevice(L->device), "hipSetDevice");
@@ -574,8 +596,7 @@ static int allreduce_rows_packed(mvhdp_group_ctx* g, int64_t r0, int64_t r1)
 }
 
 // buildInitialTypeTopicCounts PTM:600-652 over every shard: local counts, then the sum over all members of all ranks.
-// Collective; the failure protocol of group_step below: a rank whose recount failed contributes zeros and a 1 in the status word behind
-// the tokensPerTopic part, every rank enters the same all-reduce and all return an error from this call.
+// Collective; a rank whose recount failed contributes zeros and a 1 in the status word behind the tokensPerTopic part.
 extern "C" int mvhdp_group_build_counts(mvhdp_group g)
 {
     CHECK_G(g);
@@ -586,29 +607,26 @@ extern "C" int mvhdp_group_build_counts(mvhdp_group g)
     }
     const int n = (int)g->members.size();
     const int64_t len = counts_len_of(g->members[0]);
-    int local_err = MVHDP_OK;
-    auto note = [&](int rc, const std::string& what) { if (rc != MVHDP_OK && local_err == MVHDP_OK) { local_err = rc; g->err = what; } };
-    XErr x{g};
+    XErr local{g}, x{g};                                  // this rank's status word; the HIP calls of the exchange
     pack_reset(g);                                        // (new counts: the rows' classes are decided again)
     for (int i = 0; i < n; i++) {
         mvhdp_ctx* h = g->members[i];
-        const int rc = mvhdp_build_counts(h);
-        if (rc != MVHDP_OK) note(rc, "member " + std::to_string(i) + ": " + h->err);
+        local.member(i, mvhdp_build_counts(h));
         // a stale delta buffer (a failed exchange left the peers' sums in it) must not survive the recount
         if (!h->delta_clean) { x.hip(hipSetDevice(h->device), "hipSetDevice"); x.hip(hipMemsetAsync(h->mm.delta, 0, (size_t)(len + MVHDP_TAIL_WORDS) * sizeof(int32_t), h->stream), "hipMemsetAsync"); h->delta_clean = true; h->delta_pending = false; }
     }
-    if (local_err != MVHDP_OK)
+    if (local.rc != MVHDP_OK)
         for (int i = 0; i < n; i++) { mvhdp_ctx* h = g->members[i]; x.hip(hipSetDevice(h->device), "hipSetDevice"); x.hip(hipMemsetAsync(h->mm.counts, 0, (size_t)len * sizeof(int32_t), h->stream), "hipMemsetAsync"); }
     for (int i = 0; i < n; i++) { x.hip(hipSetDevice(g->members[i]->device), "hipSetDevice"); x.hip(hipEventRecord(g->ev_swept[i], g->members[i]->stream), "hipEventRecord"); }
-    note(reduce_local(g, true), g->err);
-    note(x.rc, g->err);
+    local.note(reduce_local(g, true), g->err);
+    local.note(x.rc, g->err);
     for (size_t l = 0; l < g->leaders.size(); l++) {
         mvhdp_ctx* L = g->members[g->leaders[l]];
         x.hip(hipSetDevice(L->device), "hipSetDevice");
-        hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, L->stream, L->mm.counts + len, local_err != MVHDP_OK ? 1 : 0);
+        hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, L->stream, L->mm.counts + len, local.rc != MVHDP_OK ? 1 : 0);
     }
-    note(allreduce_range(g, true, 0, len + 1), g->err);
-    note(fan_out_range(g, true, 0, len + 1), g->err);
+    local.note(allreduce_range(g, true, 0, len + 1), g->err);
+    local.note(fan_out_range(g, true, 0, len + 1), g->err);
     int32_t failed_ranks = 0;
     mvhdp_ctx* L0 = g->members[g->leaders[0]];
     x.hip(hipSetDevice(L0->device), "hipSetDevice");
@@ -617,51 +635,42 @@ extern "C" int mvhdp_group_build_counts(mvhdp_group g)
         x.hip(hipSetDevice(g->members[i]->device), "hipSetDevice");
         x.hip(hipStreamSynchronize(g->members[i]->stream), "hipStreamSynchronize");
     }
-    note(x.rc, g->err);
-    if (local_err == MVHDP_OK && failed_ranks == 0)
-        for (int i = 0; i < n; i++) { const int rc = mvhdp_counts_written(g->members[i]); if (rc != MVHDP_OK) note(rc, "member " + std::to_string(i) + ": " + g->members[i]->err); }
+    local.note(x.rc, g->err);
+    if (local.rc == MVHDP_OK && failed_ranks == 0)
+        for (int i = 0; i < n; i++) local.member(i, mvhdp_counts_written(g->members[i]));
     else
         for (int i = 0; i < n; i++) { g->members[i]->counts_stale = true; g->members[i]->have_trees = false; }
-    if (local_err != MVHDP_OK) return local_err;
+    if (local.rc != MVHDP_OK) return local.rc;
     if (failed_ranks != 0)
         GFAIL(g, MVHDP_ERR_STATE, "the recount failed on " + std::to_string(failed_ranks) + " other rank(s) of the group (or the collective broke): the counts are not valid");
     return MVHDP_OK;
 }
 
+// The members' sweeps of one step, NO_APPLY: every member's sweep goes on its device before any is waited for (none once one has
+// failed, or when the host raised mvhdp_group_abort), and every sweep that was begun is finished, whatever happened.
+static void sweep_members(mvhdp_group_ctx* g, XErr& local, uint32_t sweep_idx, uint64_t seed, uint32_t flags, std::vector<mvhdp_sweep_stats>& st)
+{
+    const int n = (int)g->members.size();
+    std::vector<PendingSweep> ps((size_t)n);
+    if (g->abort_raised) { local.note(MVHDP_ERR_STATE, "the host raised mvhdp_group_abort on this rank"); g->abort_raised = false; }
+    for (int i = 0; i < n && local.rc == MVHDP_OK; i++) {
+        mvhdp_ctx* h = g->members[i];
+        // the trees a pipelined apply left behind are those of the counts this sweep starts from (a live sweep rebuilds per segment itself)
+        const uint32_t reuse = (h->have_trees && !(flags & MVHDP_SWEEP_LIVE)) ? MVHDP_SWEEP_REUSE_TREES : 0u;
+        local.member(i, mvhdp_sweep_begin(h, sweep_idx, seed, flags | MVHDP_SWEEP_NO_APPLY | reuse, nullptr, nullptr, ps[i]));
+    }
+    for (int i = 0; i < n; i++)
+        if (ps[i].open) local.member(i, mvhdp_sweep_finish(g->members[i], ps[i], &st[i]));
+}
+
 // One exchange-terminated step: every member sweeps (all of its entities, or one segment of them) with NO_APPLY, the deltas are
 // summed over the group and applied by every replica.  st: per-member statistics of this step.
-//
-// Failure protocol (one process per GPU: a rank must never leave the others inside a collective).  Whatever happens locally, every
-// rank enters the SAME collectives -- their number depends only on replicated facts: the chunk count, the segment count taken from the
-// flags, whether the hyper-parameters hold inactive topics -- and none of the calls in between returns early (XErr).  A rank whose sweep
-// or local sum failed (or whose host called mvhdp_group_abort) contributes zero deltas and a 1 in the status word behind the
-// tokensPerTopic part, which is summed with that part: every rank reads the sum at the end of the step and all return an error together.
-// After such an error the replicas agree with each other but not with the failed rank's assignments: mvhdp_group_build_counts (a recount
-// from z, collective) makes the model consistent again.  A rank that fails LATER in the step (a HIP call of its own exchange) returns
-// its error alone, having entered every collective: its host raises mvhdp_group_abort and calls the next sweep, which then fails on
-// every rank together.  Whoever does not apply the sum leaves a delta buffer that is marked dirty: the next sweep (or the recount)
-// clears it before anything is added to it again.
 static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uint32_t flags, std::vector<mvhdp_sweep_stats>& st)
 {
     const int n = (int)g->members.size();
-    const bool live = (flags & MVHDP_SWEEP_LIVE) != 0;
-    std::vector<PendingSweep> ps((size_t)n);
-    int local_err = MVHDP_OK;
-    auto note = [&](int rc, const std::string& what) { if (rc != MVHDP_OK && local_err == MVHDP_OK) { local_err = rc; g->err = what; } };
-    if (g->abort_raised) { note(MVHDP_ERR_STATE, "the host raised mvhdp_group_abort on this rank"); g->abort_raised = false; }
-    // 1. every member's sweep goes on its device before any is waited for; every sweep that was begun is finished, whatever happened
-    for (int i = 0; i < n && local_err == MVHDP_OK; i++) {
-        mvhdp_ctx* h = g->members[i];
-        // the trees a pipelined apply left behind are those of the counts this sweep starts from (a live sweep rebuilds per segment itself)
-        const uint32_t reuse = (h->have_trees && !live) ? MVHDP_SWEEP_REUSE_TREES : 0u;
-        const int rc = mvhdp_sweep_begin(h, sweep_idx, seed, flags | MVHDP_SWEEP_NO_APPLY | reuse, nullptr, nullptr, ps[i]);
-        if (rc != MVHDP_OK) note(rc, "member " + std::to_string(i) + ": " + h->err);
-    }
-    for (int i = 0; i < n; i++) {
-        if (!ps[i].open) continue;
-        const int rc = mvhdp_sweep_finish(g->members[i], ps[i], &st[i]);
-        if (rc != MVHDP_OK) note(rc, "member " + std::to_string(i) + ": " + g->members[i]->err);
-    }
+    XErr local{g};                                        // this rank's status word
+    // 1. every member's sweep
+    sweep_members(g, local, sweep_idx, seed, flags, st);
     XErr x{g};
     const MvModel& mm = g->members[0]->mm;
     const int64_t rows = mm.rowbase[mm.M], K = mm.K, nk_off = rows * K, len = counts_len_of(g->members[0]);
@@ -674,7 +683,7 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
             h->delta_pending = false; h->counts_stale = true; h->have_trees = false; h->rows_applied = -1;
         }
     };
-    if (local_err != MVHDP_OK) drop_local();
+    if (local.rc != MVHDP_OK) drop_local();
     for (int i = 0; i < n; i++) {
         mvhdp_ctx* h = g->members[i];
         x.hip(hipSetDevice(h->device), "hipSetDevice");
@@ -687,10 +696,10 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
     x.hip(hipSetDevice(L0->device), "hipSetDevice");
     x.hip(hipEventRecord(g->ev_x0, L0->stream), "hipEventRecord");
     {
-        const bool was_ok = local_err == MVHDP_OK;
-        note(reduce_local(g, false), g->err);
-        note(x.rc, g->err);
-        if (was_ok && local_err != MVHDP_OK) {
+        const bool was_ok = local.rc == MVHDP_OK;
+        local.note(reduce_local(g, false), g->err);
+        local.note(x.rc, g->err);
+        if (was_ok && local.rc != MVHDP_OK) {
             // the local sum itself failed: what the leaders hold is not this process's share -- zeros and a raised status word instead
             for (int i = 0; i < n; i++) { hipSetDevice(g->members[i]->device); hipStreamSynchronize(g->members[i]->stream); }
             drop_local();
@@ -699,28 +708,28 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
     // the words behind the tokensPerTopic part, summed with it: [0] ranks whose sweep failed; [1], [2] this process's proposal for the
     // packed exchange and its square (0: none yet) -- every rank proposes the same layout iff n * sum(h^2) == (sum h)^2 with sum h > 0,
     // a test every rank makes on the same two sums, so all switch to the packed exchange behind the same sweep
-    const int32_t prop = (!g->pack_on && g->pack_ready && local_err == MVHDP_OK) ? g->pack_hash : 0;
+    const int32_t prop = (!g->pack_on && g->pack_ready && local.rc == MVHDP_OK) ? g->pack_hash : 0;
     for (size_t l = 0; l < g->leaders.size(); l++) {
         mvhdp_ctx* L = g->members[g->leaders[l]];
         x.hip(hipSetDevice(L->device), "hipSetDevice");
-        hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, L->stream, L->mm.delta + len, local_err != MVHDP_OK ? 1 : 0);
+        hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, L->stream, L->mm.delta + len, local.rc != MVHDP_OK ? 1 : 0);
         hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, L->stream, L->mm.delta + len + 1, prop);
         hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, L->stream, L->mm.delta + len + 2, prop * prop);
     }
     g->last_exchange_bytes += (len + 3 - nk_off) * (long long)sizeof(int32_t);
     int xrc = allreduce_range(g, false, nk_off, len + 3);
     { const int rc = fan_out_range(g, false, nk_off, len + 3); if (xrc == MVHDP_OK) xrc = rc; }
-    bool applying = local_err == MVHDP_OK && xrc == MVHDP_OK;
-    if (applying) for (int i = 0; i < n && applying; i++) { const int rc = mvhdp_apply_delta_begin(g->members[i]); if (rc) { note(rc, "member " + std::to_string(i) + ": " + g->members[i]->err); applying = false; } }
+    bool applying = local.rc == MVHDP_OK && xrc == MVHDP_OK;
+    for (int i = 0; i < n && applying; i++) applying = local.member(i, mvhdp_apply_delta_begin(g->members[i]));
     const int nch = (int)std::max<int64_t>(1, std::min<int64_t>(g->chunks, rows));
     for (int c = 0; c < nch; c++) {
         const int64_t r0 = rows * c / nch, r1 = rows * (c + 1) / nch;
         if (r1 <= r0) continue;
         if (g->pack_on) { const int rc = allreduce_rows_packed(g, r0, r1); if (xrc == MVHDP_OK) xrc = rc; }
-        else { const int rc = allreduce_range(g, false, r0 * K, r1 * K); if (xrc == MVHDP_OK) xrc = rc; g->last_exchange_bytes += (r1 - r0) * K * (long long)sizeof(int32_t); }     // (issued whatever happened before)
+        else { const int rc = allreduce_range(g, false, r0 * K, r1 * K); if (xrc == MVHDP_OK) xrc = rc; g->last_exchange_bytes += (r1 - r0) * K * (long long)sizeof(int32_t); }
         { const int rc = fan_out_range(g, false, r0 * K, r1 * K); if (xrc == MVHDP_OK) xrc = rc; }
         if (applying && xrc == MVHDP_OK)
-            for (int i = 0; i < n && applying; i++) { const int rc = mvhdp_apply_delta_rows(g->members[i], r0, r1); if (rc) { note(rc, "member " + std::to_string(i) + ": " + g->members[i]->err); applying = false; } }
+            for (int i = 0; i < n && applying; i++) applying = local.member(i, mvhdp_apply_delta_rows(g->members[i], r0, r1));
     }
     // 3. UPD:263-270 across shards: the first activating delta in (entity, view, position) order wins on every replica alike
     long long key = LLONG_MAX;
@@ -738,20 +747,12 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
             for (int i = 0; i < n; i++) {
                 if (g->leader_of[i] != li) continue;
                 x.hip(hipStreamWaitEvent(L->stream, g->ev_swept[i], 0), "hipStreamWaitEvent");
-                x.hip(launch_min_births(g->d_btab[l], local_err == MVHDP_OK ? g->members[i]->d_birth_table : nullptr, Kb, first, L->stream), "min_births_kernel");
+                x.hip(launch_min_births(g->d_btab[l], local.rc == MVHDP_OK ? g->members[i]->d_birth_table : nullptr, Kb, first, L->stream), "min_births_kernel");
                 first = false;
             }
         }
-        if (!g->comms.empty() && g->nranks > 1) {                          // (entered whatever the local status: a failed rank's table is all NONE)
-            Rccl* r = &g_rccl;
-            if (g->comms.size() > 1) x.nccl(r->GroupStart(), "ncclGroupStart");
-            for (size_t l = 0; l < g->leaders.size(); l++) {
-                mvhdp_ctx* L = g->members[g->leaders[l]];
-                x.hip(hipSetDevice(L->device), "hipSetDevice");
-                x.nccl(r->AllReduce(g->d_btab[l], g->d_btab[l], (size_t)Kb, ncclInt64, ncclMin, g->comms[l], L->stream), "birth table all-reduce");
-            }
-            if (g->comms.size() > 1) x.nccl(r->GroupEnd(), "ncclGroupEnd");
-        }
+        if (!g->comms.empty() && g->nranks > 1)                            // (a failed rank's table is all NONE)
+            leaders_allreduce(g, x, (size_t)Kb, ncclInt64, ncclMin, "birth table all-reduce", [&](size_t l) { return g->d_btab[l]; });
         g->last_exchange_bytes += (long long)Kb * (long long)sizeof(long long);
         // every leader holds the reduced table; every replica activates from the same host copy of leader 0's
         btab.assign((size_t)Kb, LLONG_MAX);
@@ -759,34 +760,27 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
         x.hip(hipMemcpyAsync(btab.data(), g->d_btab[0], (size_t)Kb * sizeof(long long), hipMemcpyDeviceToHost, L0->stream), "hipMemcpyAsync");
         x.hip(hipStreamSynchronize(L0->stream), "hipStreamSynchronize");
     } else if (has_inactive) {
-        if (local_err == MVHDP_OK) for (int i = 0; i < n; i++) key = std::min<long long>(key, (long long)st[i].activation_key);
+        if (local.rc == MVHDP_OK) for (int i = 0; i < n; i++) key = std::min<long long>(key, (long long)st[i].activation_key);
         if (!g->comms.empty() && g->nranks > 1) {
-            Rccl* r = &g_rccl;
             for (size_t l = 0; l < g->leaders.size(); l++) {
                 mvhdp_ctx* L = g->members[g->leaders[l]];
                 x.hip(hipSetDevice(L->device), "hipSetDevice");
                 x.hip(hipMemcpyAsync(g->d_key[l], &key, sizeof key, hipMemcpyHostToDevice, L->stream), "hipMemcpyAsync");
             }
-            if (g->comms.size() > 1) x.nccl(r->GroupStart(), "ncclGroupStart");
-            for (size_t l = 0; l < g->leaders.size(); l++) {
-                mvhdp_ctx* L = g->members[g->leaders[l]];
-                x.hip(hipSetDevice(L->device), "hipSetDevice");
-                x.nccl(r->AllReduce(g->d_key[l], g->d_key[l], 1, ncclInt64, ncclMin, g->comms[l], L->stream), "activation key all-reduce");
-            }
-            if (g->comms.size() > 1) x.nccl(r->GroupEnd(), "ncclGroupEnd");
+            leaders_allreduce(g, x, 1, ncclInt64, ncclMin, "activation key all-reduce", [&](size_t l) { return g->d_key[l]; });
             x.hip(hipSetDevice(L0->device), "hipSetDevice");
             x.hip(hipMemcpyAsync(&key, g->d_key[0], sizeof key, hipMemcpyDeviceToHost, L0->stream), "hipMemcpyAsync");
             x.hip(hipStreamSynchronize(L0->stream), "hipStreamSynchronize");
         }
     }
-    if (xrc != MVHDP_OK && local_err == MVHDP_OK) local_err = xrc;         // (g->err was set where the collective failed)
+    local.note(xrc, g->err);                                                // (g->err was set where the collective failed)
     // the status word of the whole group, read behind everything this step put on the first device's stream
     int32_t tail[3] = {0, 0, 0};
     x.hip(hipSetDevice(L0->device), "hipSetDevice");
     x.hip(hipEventRecord(g->ev_x1, L0->stream), "hipEventRecord");
     x.hip(hipMemcpyAsync(tail, L0->mm.delta + len, sizeof tail, hipMemcpyDeviceToHost, L0->stream), "hipMemcpyAsync");
     x.hip(hipStreamSynchronize(L0->stream), "hipStreamSynchronize");
-    note(x.rc, g->err);
+    local.note(x.rc, g->err);
     const int32_t failed_ranks = tail[0];
     // (the test of the proposals: made from the reduced words alone, so every rank decides alike; a failed sweep decides nothing)
     if (!g->pack_on && failed_ranks == 0 && tail[1] > 0 && (long long)g->nranks * tail[2] == (long long)tail[1] * tail[1]) g->pack_on = true;
@@ -800,7 +794,7 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
         if (applying) {
             int rc2 = mvhdp_apply_delta_end(h, shard_births ? -1 : topic, shard_births ? -1 : view);
             if (rc2 == MVHDP_OK && shard_births) rc2 = mvhdp_activate_births_ex(h, btab.data(), nullptr, nullptr);
-            if (rc2 != MVHDP_OK) note(rc2, "member " + std::to_string(i) + ": " + h->err);
+            local.member(i, rc2);
         } else {
             hipSetDevice(h->device); hipStreamSynchronize(h->stream);
             if (h->rows_applied >= 0) { h->rows_applied = -1; h->have_trees = false; }     // a bracket this step opened and could not close
@@ -814,7 +808,7 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
     float ms = 0;
     hipSetDevice(L0->device);
     if (hipEventElapsedTime(&ms, g->ev_x0, g->ev_x1) == hipSuccess) g->last_exchange_ms += ms;
-    if (local_err != MVHDP_OK) return local_err;
+    if (local.rc != MVHDP_OK) return local.rc;
     if (failed_ranks != 0) {
         // the other replicas applied the same (partial) sum and agree with each other; the model as a whole needs the recount
         for (int i = 0; i < n; i++) g->members[i]->counts_stale = true;
@@ -858,8 +852,7 @@ static int async_buffers(mvhdp_group_ctx* g)
 }
 
 // what is in flight lands: every member adds the other shards' share of the exchanged deltas; *failed: ranks whose sweep had failed.
-// Issues everything it has to issue whatever fails on the way (a step of the asynchronous exchange calls it in front of its own
-// collective, which the peers are about to enter).
+// Issues everything whatever fails on the way: a step of the asynchronous exchange calls it in front of its own collective.
 static int async_land(mvhdp_group_ctx* g, int32_t* failed)
 {
     *failed = 0;
@@ -884,18 +877,25 @@ static int async_land(mvhdp_group_ctx* g, int32_t* failed)
     return x.rc;
 }
 
+// What is in flight lands, for mvhdp_group_drain and the statistics.  A failure of this rank alone goes to *local; a sweep that had
+// failed on some rank (read from the exchanged status word) fails the call on every rank alike.  Either way the counts are stale.
+static int land_exchange(mvhdp_group_ctx* g, int* local)
+{
+    int32_t failed = 0;
+    const int rc = async_land(g, &failed);
+    if (rc == MVHDP_OK && failed == 0) return MVHDP_OK;
+    for (mvhdp_ctx* h : g->members) h->counts_stale = true;
+    if (rc != MVHDP_OK) { *local = rc; return MVHDP_OK; }
+    GFAIL(g, MVHDP_ERR_STATE, "a sweep whose deltas were still on the wire had failed on " + std::to_string(failed) + " rank(s): call mvhdp_group_build_counts on every rank");
+}
+
 extern "C" int mvhdp_group_drain(mvhdp_group g)
 {
     CHECK_G(g);
     DeviceGuard dg;
-    int32_t failed = 0;
-    int rc = async_land(g, &failed);
-    if (rc) { for (mvhdp_ctx* h : g->members) h->counts_stale = true; return rc; }
-    if (failed != 0) {
-        for (mvhdp_ctx* h : g->members) h->counts_stale = true;
-        GFAIL(g, MVHDP_ERR_STATE, "a sweep whose deltas were still on the wire had failed on " + std::to_string(failed) + " rank(s): call mvhdp_group_build_counts on every rank");
-    }
-    return MVHDP_OK;
+    int local = MVHDP_OK;
+    const int rc = land_exchange(g, &local);
+    return local != MVHDP_OK ? local : rc;
 }
 
 static int group_step_async(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uint32_t flags, std::vector<mvhdp_sweep_stats>& st)
@@ -908,34 +908,22 @@ static int group_step_async(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t see
     int rc = async_buffers(g); if (rc) return rc;
     const int64_t len = counts_len_of(g->members[0]);
     const size_t bytes = (size_t)len * sizeof(int32_t);
-    std::vector<PendingSweep> ps((size_t)n);
-    int local_err = MVHDP_OK;
-    auto note = [&](int r, const std::string& what) { if (r != MVHDP_OK && local_err == MVHDP_OK) { local_err = r; g->err = what; } };
-    if (g->abort_raised) { note(MVHDP_ERR_STATE, "the host raised mvhdp_group_abort on this rank"); g->abort_raised = false; }
+    XErr local{g};                                         // this rank's status word
     // 1. this sweep, live on every member's own replica (which lacks the other shards' previous sweep: still on the wire)
-    for (int i = 0; i < n && local_err == MVHDP_OK; i++) {
-        const int r = mvhdp_sweep_begin(g->members[i], sweep_idx, seed, (flags & ~MVHDP_SWEEP_ASYNC_EXCHANGE) | MVHDP_SWEEP_NO_APPLY, nullptr, nullptr, ps[i]);
-        if (r != MVHDP_OK) note(r, "member " + std::to_string(i) + ": " + g->members[i]->err);
-    }
-    for (int i = 0; i < n; i++) {
-        if (!ps[i].open) continue;
-        const int r = mvhdp_sweep_finish(g->members[i], ps[i], &st[i]);
-        if (r != MVHDP_OK) note(r, "member " + std::to_string(i) + ": " + g->members[i]->err);
-    }
-    // From here to the all-reduce below nothing returns: the peers enter that collective whatever happens on this rank (XErr).
+    sweep_members(g, local, sweep_idx, seed, flags & ~MVHDP_SWEEP_ASYNC_EXCHANGE, st);
     XErr x{g};
     // 2. the previous sweep's exchange has had this sweep's time: it lands now (counts were restored to the sweep-start snapshot by
     //    the NO_APPLY form: first this sweep's own deltas go back in, then the other shards' share of the previous one)
     for (int i = 0; i < n; i++) {
         mvhdp_ctx* h = g->members[i];
         x.hip(hipSetDevice(h->device), "hipSetDevice");
-        if (local_err != MVHDP_OK) { x.hip(hipMemsetAsync(h->mm.delta, 0, bytes, h->stream), "hipMemsetAsync"); h->counts_stale = true; }
+        if (local.rc != MVHDP_OK) { x.hip(hipMemsetAsync(h->mm.delta, 0, bytes, h->stream), "hipMemsetAsync"); h->counts_stale = true; }
         else x.hip(launch_add_into(h->mm.counts, h->mm.delta, len, h->stream), "add_into_kernel");
     }
     int32_t failed = 0;
-    note(async_land(g, &failed), g->err);
-    note(x.rc, g->err);
-    if (local_err != MVHDP_OK)                             // (a failure found after the deltas went back in: this rank still ships zeros and a raised word)
+    local.note(async_land(g, &failed), g->err);
+    local.note(x.rc, g->err);
+    if (local.rc != MVHDP_OK)                              // (a failure found after the deltas went back in: this rank still ships zeros and a raised word)
         for (int i = 0; i < n; i++) { mvhdp_ctx* h = g->members[i]; hipSetDevice(h->device); hipMemsetAsync(h->mm.delta, 0, bytes, h->stream); h->counts_stale = true; }
     // 3. this sweep's deltas go on the wire (a copy: the delta buffer is the next sweep's), the collective on its own stream
     for (int i = 0; i < n; i++) {
@@ -944,7 +932,7 @@ static int group_step_async(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t see
         x.hip(hipMemcpyAsync(g->xbuf[i], h->mm.delta, bytes, hipMemcpyDeviceToDevice, h->stream), "hipMemcpyAsync");
         x.hip(hipMemcpyAsync(g->sbuf[i], h->mm.delta, bytes, hipMemcpyDeviceToDevice, h->stream), "hipMemcpyAsync");
         x.hip(hipMemsetAsync(h->mm.delta, 0, bytes, h->stream), "hipMemsetAsync");
-        hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, h->stream, g->xbuf[i] + len, (g->leader_of[i] == i && local_err != MVHDP_OK) ? 1 : 0);
+        hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, h->stream, g->xbuf[i] + len, (g->leader_of[i] == i && local.rc != MVHDP_OK) ? 1 : 0);
         x.hip(hipEventRecord(g->ev_swept[i], h->stream), "hipEventRecord");
         h->delta_pending = false; h->delta_clean = true; h->have_trees = false;
     }
@@ -958,17 +946,8 @@ static int group_step_async(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t see
             if (i != li) x.hip(launch_add_into(g->xbuf[li], g->xbuf[i], len, g->comm[l]), "add_into_kernel");
         }
     }
-    if (!g->comms.empty()) {
-        Rccl* r = &g_rccl;
-        if (g->comms.size() > 1) x.nccl(r->GroupStart(), "ncclGroupStart");
-        for (size_t l = 0; l < g->leaders.size(); l++) {
-            mvhdp_ctx* L = g->members[g->leaders[l]];
-            x.hip(hipSetDevice(L->device), "hipSetDevice");
-            int32_t* buf = g->xbuf[g->leaders[l]];
-            x.nccl(r->AllReduce(buf, buf, (size_t)(len + 1), ncclInt32, ncclSum, g->comms[l], g->comm[l]), "ncclAllReduce");
-        }
-        if (g->comms.size() > 1) x.nccl(r->GroupEnd(), "ncclGroupEnd");
-    }
+    if (!g->comms.empty())
+        leaders_allreduce(g, x, (size_t)(len + 1), ncclInt32, ncclSum, "ncclAllReduce", [&](size_t l) { return g->xbuf[g->leaders[l]]; }, &g->comm);
     for (size_t l = 0; l < g->leaders.size(); l++) {
         const int li = g->leaders[l];
         x.hip(hipSetDevice(g->members[li]->device), "hipSetDevice");
@@ -977,9 +956,9 @@ static int group_step_async(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t see
         x.hip(hipEventRecord(g->ev_xfer[l], g->comm[l]), "hipEventRecord");
     }
     g->async_pending = true;
-    note(x.rc, g->err);
+    local.note(x.rc, g->err);
     for (int i = 0; i < n; i++) { st[i].activation_key = LLONG_MAX; st[i].activated_topic = -1; st[i].activated_modality = -1; st[i].activations = 0; }
-    if (local_err != MVHDP_OK) { for (mvhdp_ctx* h : g->members) h->counts_stale = true; return local_err; }
+    if (local.rc != MVHDP_OK) { for (mvhdp_ctx* h : g->members) h->counts_stale = true; return local.rc; }
     if (failed != 0) {
         for (mvhdp_ctx* h : g->members) h->counts_stale = true;
         GFAIL(g, MVHDP_ERR_STATE, "the previous sweep failed on " + std::to_string(failed) + " other rank(s) of the group: call mvhdp_group_build_counts on every rank");
@@ -1066,16 +1045,15 @@ extern "C" int mvhdp_group_sweep(mvhdp_group g, uint32_t sweep_idx, uint64_t see
 // ---------------------------------------------------------------------------------------------------------------
 namespace {
 
-// The cross-rank pieces of the statistics (one process per GPU).  Same rule as the sweep: a rank whose own part failed still enters
-// the collective -- with zeros and a raised status slot -- so that every rank learns of it from the result and all return an error from
-// the same call; nothing is allocated on the way (the scratch buffer exists since mvhdp_group_create_rank) and no HIP failure returns
-// before the all-reduce has been issued.  local_status: MVHDP_OK or this rank's error; *failed_ranks: ranks that raised their slot.
+// The cross-rank pieces of the statistics (one process per GPU; a no-op in one process).  local_status: MVHDP_OK or this rank's
+// error, which sends zeros and a raised status slot; *failed_ranks: ranks that raised their slot.  Nothing is allocated on the device
+// on the way: the scratch buffer exists since mvhdp_group_create_rank.
 
-// all[r*n + i] = rank r's vals[i]; single process: all = vals
-int xrank_gather_f64(mvhdp_group_ctx* g, const double* vals, int n, int local_status, std::vector<double>& all, int* failed_ranks)
+// vals[i] <- 0.0 + rank 0's vals[i] + rank 1's + ... in rank order; written only when every rank succeeded
+int xrank_sum_f64(mvhdp_group_ctx* g, double* vals, int n, int local_status, int* failed_ranks)
 {
     *failed_ranks = 0;
-    if (!g->multi_process || g->nranks <= 1) { all.assign(vals, vals + n); return MVHDP_OK; }
+    if (!g->multi_process || g->nranks <= 1) return MVHDP_OK;      // (vals as they are: 0.0 + -0.0 would be +0.0)
     mvhdp_ctx* L = g->members[g->leaders[0]];
     const size_t per = (size_t)n + 1, total = (size_t)g->nranks * per;
     if (total * sizeof(double) > XSCRATCH_BYTES || !g->d_scratch) GFAIL(g, MVHDP_ERR_INVALID_ARG, "xrank_gather_f64: message larger than the scratch buffer");   // (replicated sizes: every rank refuses alike)
@@ -1086,15 +1064,13 @@ int xrank_gather_f64(mvhdp_group_ctx* g, const double* vals, int n, int local_st
     double* d = (double*)g->d_scratch;
     x.hip(hipSetDevice(L->device), "hipSetDevice");
     x.hip(hipMemcpyAsync(d, host.data(), total * sizeof(double), hipMemcpyHostToDevice, L->stream), "hipMemcpyAsync");
-    x.nccl(g_rccl.AllReduce(d, d, total, ncclDouble, ncclSum, g->comms[0], L->stream), "ncclAllReduce");
+    leaders_allreduce(g, x, total, ncclDouble, ncclSum, "ncclAllReduce", [&](size_t) { return d; });    // (exact: one non-zero term per element)
     x.hip(hipMemcpyAsync(host.data(), d, total * sizeof(double), hipMemcpyDeviceToHost, L->stream), "hipMemcpyAsync");
     x.hip(hipStreamSynchronize(L->stream), "hipStreamSynchronize");
     if (x.rc != MVHDP_OK) return x.rc;
-    all.resize((size_t)g->nranks * n);
-    for (int r = 0; r < g->nranks; r++) {
-        std::copy(host.begin() + (size_t)r * per, host.begin() + (size_t)r * per + n, all.begin() + (size_t)r * n);
-        if (host[(size_t)r * per + n] != 0.0) (*failed_ranks)++;
-    }
+    for (int r = 0; r < g->nranks; r++) if (host[(size_t)r * per + n] != 0.0) (*failed_ranks)++;
+    if (local_status != MVHDP_OK || *failed_ranks != 0) return MVHDP_OK;
+    for (int i = 0; i < n; i++) { double a = 0; for (int r = 0; r < g->nranks; r++) a += host[(size_t)r * per + i]; vals[i] = a; }
     return MVHDP_OK;
 }
 
@@ -1117,7 +1093,7 @@ int xrank_sum_i32(mvhdp_group_ctx* g, int32_t* vals, size_t n, int local_status,
         piece[k] = local_status == MVHDP_OK ? 0 : 1;
         const size_t cnt = k + (last ? 1 : 0);
         x.hip(hipMemcpyAsync(d, piece.data(), cnt * sizeof(int32_t), hipMemcpyHostToDevice, L->stream), "hipMemcpyAsync");
-        x.nccl(g_rccl.AllReduce(d, d, cnt, ncclInt32, ncclSum, g->comms[0], L->stream), "ncclAllReduce");
+        leaders_allreduce(g, x, cnt, ncclInt32, ncclSum, "ncclAllReduce", [&](size_t) { return d; });
         x.hip(hipMemcpyAsync(piece.data(), d, cnt * sizeof(int32_t), hipMemcpyDeviceToHost, L->stream), "hipMemcpyAsync");
         x.hip(hipStreamSynchronize(L->stream), "hipStreamSynchronize");
         if (x.rc == MVHDP_OK) { std::copy(piece.begin(), piece.begin() + k, vals + off); if (last) *failed_ranks = piece[k]; }
@@ -1126,23 +1102,27 @@ int xrank_sum_i32(mvhdp_group_ctx* g, int32_t* vals, size_t n, int local_status,
     return x.rc;
 }
 
-// A statistic of a group whose asynchronous exchange is still in flight lands it first.  Returns non-zero only for what EVERY rank sees
-// alike (a peer's failed sweep, read from the exchanged status word); a failure of this rank alone goes to *local_status, and the
-// caller still enters its collectives.
-int land_before_statistics(mvhdp_group_ctx* g, int* local_status)
-{
-    if (!g->async_pending) return MVHDP_OK;
-    int32_t failed = 0;
-    const int rc = async_land(g, &failed);
-    if (rc != MVHDP_OK) { if (*local_status == MVHDP_OK) *local_status = rc; for (mvhdp_ctx* h : g->members) h->counts_stale = true; if (!g->multi_process) return rc; return MVHDP_OK; }
-    if (failed != 0) {
-        for (mvhdp_ctx* h : g->members) h->counts_stale = true;
-        GFAIL(g, MVHDP_ERR_STATE, "a sweep whose deltas were still on the wire had failed on " + std::to_string(failed) + " rank(s): call mvhdp_group_build_counts on every rank");
+// The frame of one group statistic: land() first, member() for every member's call, finish() behind the collectives (xrank_sum_*).
+// The first failure ends the member loop; in one process the collectives are no-ops and finish() returns it at once.
+struct GroupStat {
+    mvhdp_group_ctx* g;
+    int lst = MVHDP_OK;                       // this rank's own first failure
+    std::string keep;                         // its message (a failing collective may write g->err after it)
+    bool ok() const { return lst == MVHDP_OK; }
+    bool multi() const { return g->multi_process && g->nranks > 1; }
+    // a pending asynchronous exchange lands; non-zero: what the call returns at once (a peer's failed sweep: on every rank alike)
+    int land() { const int rc = land_exchange(g, &lst); if (lst != MVHDP_OK) { keep = g->err; if (!g->multi_process) return lst; } return rc; }
+    bool member(size_t i, int rc) { if (rc != MVHDP_OK && lst == MVHDP_OK) { lst = rc; g->err = keep = member_msg(g, i); } return rc == MVHDP_OK; }
+    // behind the collectives: this rank's own error, then a collective's, then a peer's
+    int finish(int rc1 = MVHDP_OK, int rc2 = MVHDP_OK, int failed1 = 0, int failed2 = 0)
+    {
+        if (lst != MVHDP_OK) { g->err = keep; return lst; }
+        if (rc1 != MVHDP_OK) return rc1;
+        if (rc2 != MVHDP_OK) return rc2;
+        if (failed1 || failed2) GFAIL(g, MVHDP_ERR_STATE, "the statistic failed on " + std::to_string(std::max(failed1, failed2)) + " other rank(s) of the group");
+        return MVHDP_OK;
     }
-    return MVHDP_OK;
-}
-
-#define XFAILED(g, failed) GFAIL(g, MVHDP_ERR_STATE, "the statistic failed on " + std::to_string(failed) + " other rank(s) of the group")
+};
 
 }  // namespace
 
@@ -1162,32 +1142,19 @@ extern "C" int mvhdp_group_log_likelihood(mvhdp_group g, double* out)
     CHECK_G(g);
     if (!out) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_log_likelihood: null");
     DeviceGuard dg;
-    int lst = MVHDP_OK;
-    { const int rcd = land_before_statistics(g, &lst); if (rcd) return rcd; }
-    const bool multi = g->multi_process && g->nranks > 1;
+    GroupStat st{g};
+    if (const int rc = st.land()) return rc;
     const int M = g->members[0]->mm.M;
     for (int m = 0; m < M; m++) {
         double ll = 0;
         int64_t cnt = 0;
-        for (int i : g->by_entity) {
-            if (lst != MVHDP_OK) break;
-            const int rc = mvhdp_ll_doc_accumulate(g->members[i], m, &ll, &cnt);
-            if (rc != MVHDP_OK) { lst = rc; g->err = "member " + std::to_string(i) + ": " + g->members[i]->err; if (!multi) return rc; }
-        }
-        if (multi) {
-            const double mine[2] = {ll, (double)cnt};
-            std::vector<double> all;
-            int failed = 0;
-            const std::string keep = g->err;
-            const int rc = xrank_gather_f64(g, mine, 2, lst, all, &failed);
-            if (lst != MVHDP_OK) { g->err = keep; return lst; }
-            if (rc) return rc;
-            if (failed) XFAILED(g, failed);
-            ll = 0; double c = 0;
-            for (int r = 0; r < g->nranks; r++) { ll += all[(size_t)2 * r]; c += all[(size_t)2 * r + 1]; }
-            cnt = (int64_t)c;
-        }
-        GMEM(g, 0, mvhdp_ll_model_finish(g->members[0], m, ll, cnt, &out[m]));
+        for (int i : g->by_entity)
+            if (!st.ok() || !st.member(i, mvhdp_ll_doc_accumulate(g->members[i], m, &ll, &cnt))) break;
+        double sum[2] = {ll, (double)cnt};                                 // (a token count is exact in a double)
+        int failed = 0;
+        const int rc = xrank_sum_f64(g, sum, 2, st.lst, &failed);
+        if (const int r = st.finish(rc, MVHDP_OK, failed)) return r;
+        GMEM(g, 0, mvhdp_ll_model_finish(g->members[0], m, sum[0], (int64_t)sum[1], &out[m]));
     }
     return MVHDP_OK;
 }
@@ -1197,30 +1164,22 @@ extern "C" int mvhdp_group_doc_topic_hist(mvhdp_group g, int32_t m, int32_t* his
 {
     CHECK_G(g);
     DeviceGuard dg;
-    int lst = MVHDP_OK;
-    { const int rcd = land_before_statistics(g, &lst); if (rcd) return rcd; }
-    const bool multi = g->multi_process && g->nranks > 1;
+    GroupStat st{g};
+    if (const int rc = st.land()) return rc;
     const int K = g->members[0]->mm.K;
     const size_t nh = hist ? (size_t)K * (size_t)std::max(hist_len, 0) : 0, nl = doc_len_counts ? (size_t)std::max(len_len, 0) : 0;
     std::vector<int32_t> th(nh), tl(nl);
     if (hist) std::fill(hist, hist + nh, 0);
     if (doc_len_counts) std::fill(doc_len_counts, doc_len_counts + nl, 0);
-    std::string keep;
-    for (size_t i = 0; i < g->members.size() && lst == MVHDP_OK; i++) {
-        const int rc = mvhdp_get_doc_topic_hist(g->members[i], m, hist ? th.data() : nullptr, hist_len, doc_len_counts ? tl.data() : nullptr, len_len);
-        if (rc != MVHDP_OK) { lst = rc; g->err = keep = "member " + std::to_string(i) + ": " + g->members[i]->err; if (!multi) return rc; break; }
+    for (size_t i = 0; i < g->members.size() && st.ok(); i++) {
+        if (!st.member(i, mvhdp_get_doc_topic_hist(g->members[i], m, hist ? th.data() : nullptr, hist_len, doc_len_counts ? tl.data() : nullptr, len_len))) break;
         for (size_t q = 0; q < nh; q++) hist[q] += th[q];
         for (size_t q = 0; q < nl; q++) doc_len_counts[q] += tl[q];
     }
-    // (both collectives are entered whatever the first one said: their number depends on the arguments alone, which every rank passes alike)
     int f1 = 0, f2 = 0;
-    const int rc1 = hist ? xrank_sum_i32(g, hist, nh, lst, &f1) : MVHDP_OK;
-    const int rc2 = doc_len_counts ? xrank_sum_i32(g, doc_len_counts, nl, lst, &f2) : MVHDP_OK;
-    if (lst != MVHDP_OK) { if (!keep.empty()) g->err = keep; return lst; }
-    if (rc1) return rc1;
-    if (rc2) return rc2;
-    if (f1 || f2) XFAILED(g, std::max(f1, f2));
-    return MVHDP_OK;
+    const int rc1 = hist ? xrank_sum_i32(g, hist, nh, st.lst, &f1) : MVHDP_OK;
+    const int rc2 = doc_len_counts ? xrank_sum_i32(g, doc_len_counts, nl, st.lst, &f2) : MVHDP_OK;
+    return st.finish(rc1, rc2, f1, f2);
 }
 
 // countHistogram of optimizeBeta PTM:2295-2309: a statistic of the replicated n_wk -- any member's
@@ -1229,9 +1188,9 @@ extern "C" int mvhdp_group_count_histogram(mvhdp_group g, int32_t m, int32_t* hi
     CHECK_G(g);
     DeviceGuard dg;
     // (no collective of its own; a drain is the landing of something every rank has already issued)
-    int lst = MVHDP_OK;
-    { const int rcd = land_before_statistics(g, &lst); if (rcd) return rcd; }
-    if (lst != MVHDP_OK) return lst;
+    GroupStat st{g};
+    if (const int rc = st.land()) return rc;
+    if (!st.ok()) return st.lst;
     GMEM(g, 0, mvhdp_get_count_histogram(g->members[0], m, hist, len));
     return MVHDP_OK;
 }
@@ -1242,27 +1201,15 @@ extern "C" int mvhdp_group_view_overlap_sums(mvhdp_group g, double* sums)
     CHECK_G(g);
     if (!sums) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_view_overlap_sums: null");
     DeviceGuard dg;
-    int lst = MVHDP_OK;
-    { const int rcd = land_before_statistics(g, &lst); if (rcd) return rcd; }
-    const bool multi = g->multi_process && g->nranks > 1;
+    GroupStat st{g};
+    if (const int rc = st.land()) return rc;
     const int M = g->members[0]->mm.M;
     for (int i = 0; i < M * M; i++) sums[i] = 0.0;
-    std::string keep;
-    for (int i : g->by_entity) {
-        if (lst != MVHDP_OK) break;
-        const int rc = mvhdp_view_overlap_accumulate(g->members[i], sums);
-        if (rc != MVHDP_OK) { lst = rc; g->err = keep = "member " + std::to_string(i) + ": " + g->members[i]->err; if (!multi) return rc; }
-    }
-    if (multi) {
-        std::vector<double> all;
-        int failed = 0;
-        const int rc = xrank_gather_f64(g, sums, M * M, lst, all, &failed);
-        if (lst != MVHDP_OK) { if (!keep.empty()) g->err = keep; return lst; }
-        if (rc) return rc;
-        if (failed) XFAILED(g, failed);
-        for (int i = 0; i < M * M; i++) { double a = 0; for (int r = 0; r < g->nranks; r++) a += all[(size_t)r * M * M + i]; sums[i] = a; }
-    }
-    return MVHDP_OK;
+    for (int i : g->by_entity)
+        if (!st.ok() || !st.member(i, mvhdp_view_overlap_accumulate(g->members[i], sums))) break;
+    int failed = 0;
+    const int rc = xrank_sum_f64(g, sums, M * M, st.lst, &failed);
+    return st.finish(rc, MVHDP_OK, failed);
 }
 
 // optimizeGamma's document level PTM:2415-2433 (mvhdp_gamma_doc_statistics): every entity draws from its own stream (global entity
@@ -1272,30 +1219,18 @@ extern "C" int mvhdp_group_gamma_doc_statistics(mvhdp_group g, int32_t m, double
     CHECK_G(g);
     if (!qs || !qw) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_gamma_doc_statistics: null");
     DeviceGuard dg;
-    int lst = MVHDP_OK;
-    { const int rcd = land_before_statistics(g, &lst); if (rcd) return rcd; }
-    const bool multi = g->multi_process && g->nranks > 1;
-    double a = 0, b = 0;
-    std::string keep;
+    GroupStat st{g};
+    if (const int rc = st.land()) return rc;
+    double sum[2] = {0, 0};
     for (int i : g->by_entity) {
-        if (lst != MVHDP_OK) break;
         double x = 0, y = 0;
-        const int rc = mvhdp_gamma_doc_statistics(g->members[i], m, gamma_m, seed, round, &x, &y);
-        if (rc != MVHDP_OK) { lst = rc; g->err = keep = "member " + std::to_string(i) + ": " + g->members[i]->err; if (!multi) return rc; break; }
-        a += x; b += y;
+        if (!st.ok() || !st.member(i, mvhdp_gamma_doc_statistics(g->members[i], m, gamma_m, seed, round, &x, &y))) break;
+        sum[0] += x; sum[1] += y;
     }
-    if (multi) {
-        const double mine[2] = {a, b};
-        std::vector<double> all;
-        int failed = 0;
-        const int rc = xrank_gather_f64(g, mine, 2, lst, all, &failed);
-        if (lst != MVHDP_OK) { if (!keep.empty()) g->err = keep; return lst; }
-        if (rc) return rc;
-        if (failed) XFAILED(g, failed);
-        a = 0; b = 0;
-        for (int r = 0; r < g->nranks; r++) { a += all[(size_t)2 * r]; b += all[(size_t)2 * r + 1]; }
-    }
-    *qs = a; *qw = b;
+    int failed = 0;
+    const int rc = xrank_sum_f64(g, sum, 2, st.lst, &failed);
+    if (const int r = st.finish(rc, MVHDP_OK, failed)) return r;
+    *qs = sum[0]; *qw = sum[1];
     return MVHDP_OK;
 }
 
@@ -1308,25 +1243,19 @@ extern "C" int mvhdp_group_diagnostics(mvhdp_group g, const mvhdp_diag_args* arg
     CHECK_G(g);
     DeviceGuard dg;
     mvhdp_ctx* h0 = g->members[0];
-    { const int rc = mvhdp_diag_check_args(h0, args, out); if (rc) { g->err = "member 0: " + h0->err; return rc; } }
-    int lst = MVHDP_OK;
-    { const int rcd = land_before_statistics(g, &lst); if (rcd) return rcd; }
-    const bool multi = g->multi_process && g->nranks > 1;
+    { const int rc = mvhdp_diag_check_args(h0, args, out); if (rc) { g->err = member_msg(g, 0); return rc; } }
+    GroupStat st{g};
+    if (const int rc = st.land()) return rc;
     const int K = h0->mm.K, N = args->num_top_words;
-    std::string keep;
     DiagModel dm;
     DiagAcc acc;
     acc.reset(K, N);
-    if (lst == MVHDP_OK) {
-        const int rc = mvhdp_diag_model(h0, N, dm);
-        if (rc != MVHDP_OK) { lst = rc; g->err = keep = "member 0: " + h0->err; if (!multi) return rc; }
-    }
+    if (st.ok()) st.member(0, mvhdp_diag_model(h0, N, dm));
     for (int i : g->by_entity) {
-        if (lst != MVHDP_OK) break;
+        if (!st.ok()) break;
         DiagAcc mine;
         mine.reset(K, N);
-        const int rc = mvhdp_diag_docs(g->members[i], dm, mine);
-        if (rc != MVHDP_OK) { lst = rc; g->err = keep = "member " + std::to_string(i) + ": " + g->members[i]->err; if (!multi) return rc; break; }
+        if (!st.member(i, mvhdp_diag_docs(g->members[i], dm, mine))) break;
         for (size_t q = 0; q < acc.codoc.size(); q++) acc.codoc[q] += mine.codoc[q];
         for (int k = 0; k < K; k++) {
             acc.rank1_docs[k] += mine.rank1_docs[k]; acc.nonzero_docs[k] += mine.nonzero_docs[k];
@@ -1335,7 +1264,9 @@ extern "C" int mvhdp_group_diagnostics(mvhdp_group g, const mvhdp_diag_args* arg
         for (size_t q = 0; q < acc.at_proportions.size(); q++) acc.at_proportions[q] += mine.at_proportions[q];
         acc.num_tokens += mine.num_tokens;
     }
-    if (multi) {
+    if (!st.multi()) {
+        if (const int rc = st.finish()) return rc;
+    } else {
         // one int32 vector [codoc | rank-1 | non-zero | proportions], one f64 vector [c log c | numTokens]
         std::vector<int32_t> iv;
         iv.reserve(acc.codoc.size() + (size_t)K * (2 + MVHDP_DIAG_PROPORTIONS));
@@ -1346,23 +1277,16 @@ extern "C" int mvhdp_group_diagnostics(mvhdp_group g, const mvhdp_diag_args* arg
         std::vector<double> fv(acc.sum_count_log_count);
         fv.push_back((double)acc.num_tokens);
         int f1 = 0, f2 = 0;
-        std::vector<double> all;
-        const int rc1 = xrank_sum_i32(g, iv.data(), iv.size(), lst, &f1);
-        const int rc2 = xrank_gather_f64(g, fv.data(), (int)fv.size(), lst, all, &f2);
-        if (lst != MVHDP_OK) { if (!keep.empty()) g->err = keep; return lst; }
-        if (rc1) return rc1;
-        if (rc2) return rc2;
-        if (f1 || f2) XFAILED(g, std::max(f1, f2));
+        const int rc1 = xrank_sum_i32(g, iv.data(), iv.size(), st.lst, &f1);
+        const int rc2 = xrank_sum_f64(g, fv.data(), (int)fv.size(), st.lst, &f2);
+        if (const int rc = st.finish(rc1, rc2, f1, f2)) return rc;
         size_t o = 0;
         std::copy(iv.begin() + o, iv.begin() + o + acc.codoc.size(), acc.codoc.begin()); o += acc.codoc.size();
         std::copy(iv.begin() + o, iv.begin() + o + K, acc.rank1_docs.begin()); o += K;
         std::copy(iv.begin() + o, iv.begin() + o + K, acc.nonzero_docs.begin()); o += K;
         std::copy(iv.begin() + o, iv.begin() + o + acc.at_proportions.size(), acc.at_proportions.begin());
-        const size_t nf = fv.size();
-        double tok = 0;
-        for (int k = 0; k < K; k++) { double a = 0; for (int r = 0; r < g->nranks; r++) a += all[(size_t)r * nf + k]; acc.sum_count_log_count[k] = a; }
-        for (int r = 0; r < g->nranks; r++) tok += all[(size_t)r * nf + K];
-        acc.num_tokens = (int64_t)tok;
+        std::copy(fv.begin(), fv.begin() + K, acc.sum_count_log_count.begin());
+        acc.num_tokens = (int64_t)fv[K];
     }
     GMEM(g, 0, mvhdp_diag_finish(h0, dm, acc, args, out));
     return MVHDP_OK;

@@ -144,6 +144,18 @@ def main():
         sweep(2)
         sweep(3)
         snap("end")
+    elif scenario == "fail_statistic":
+        bad = rank == nranks - 1
+        maxlen = int(max(np.diff(c.doc_off[m]).max() for m in range(c.M))) + 1
+        calls = {"gamma": lambda: g.gamma_doc_statistics(0, -1.0 if bad else 1.0, 5, 0),       # the f64 collective
+                 "hist": lambda: g.get_doc_topic_hist(c.M if bad else 0, maxlen, maxlen)}       # the two int32 collectives
+        for name, call in calls.items():
+            try:
+                call()
+                log[name] = {"ok": True}
+            except MvhdpError as e:
+                log[name] = {"ok": False, "code": e.code, "msg": str(e)}
+        out["ll"] = g.model_log_likelihood()                      # every rank is in step again
     elif scenario == "die":
         sweep(0)
         if rank == nranks - 1:

@@ -6,8 +6,8 @@ like the real one -- selected through MVHDP_RCCL_LIB.  Test infrastructure only:
 Every rank is a fresh child process (tests/rank_worker.py); this process holds the references: the oracle (deferred sweeps: bit for
 bit), the same shards as members of a one-process group (the segmented sweep across shards: bit for bit), a single handle (the
 statistics either side of the sweep), and the invariants of live sweeps (the counts are the counts of the assignments, on every rank).
-Failures: a rank whose sweep is refused, a rank whose host raises mvhdp_group_abort, a rank that dies -- the peers must return an error
-from the same call, never hang (every run has a timeout)."""
+Failures: a rank whose sweep is refused, a rank whose host raises mvhdp_group_abort, a rank whose statistic is refused, a rank that
+dies -- the peers must return an error from the same call, never hang (every run has a timeout)."""
 import json
 import os
 import subprocess
@@ -216,6 +216,29 @@ def test_a_failing_rank_fails_the_sweep_on_every_rank_and_a_recount_recovers(tmp
         nwk, nk = o.get_counts(m)
         for r, a in enumerate(arrs):
             assert np.array_equal(a[f"end_nwk{m}"], nwk) and np.array_equal(a[f"end_nk{m}"], nk), f"rank {r}: counts of view {m} after the recovery"
+
+
+@pytest.mark.parametrize("nranks", [2, 4])
+def test_a_statistic_refused_on_one_rank_fails_on_every_rank_and_the_next_one_succeeds(tmp_path, fake_rccl, nranks):
+    """The last rank passes a bad argument (a local MVHDP_ERR_INVALID_ARG of its member, no device fault) to gamma_doc_statistics (the
+    f64 collective) and to get_doc_topic_hist (the two int32 collectives).  It still enters every collective: it returns its member's
+    error, every peer MVHDP_ERR_STATE from the same call, none hangs, and the log-likelihood after it is the single handle's."""
+    procs, outs, logs, arrs = run_ranks(tmp_path, fake_rccl, nranks, "fail_statistic")
+    assert_all_ok(procs, outs, logs)
+    bad = nranks - 1
+    for r, lg in enumerate(logs):
+        for name, what in (("gamma", "gamma_doc_statistics: bad argument"), ("hist", "get_doc_topic_hist: bad argument")):
+            e = lg[name]
+            if r == bad:
+                assert not e["ok"] and e["code"] == -1 and f"member 0: {what}" in e["msg"], f"rank {r}: {name} {e}"
+            else:
+                assert not e["ok"] and e["code"] == -2 and "the statistic failed on 1 other rank(s)" in e["msg"], f"rank {r}: {name} {e}"
+    c, z = W.corpus()
+    s = make_native(c, W.hyper("fail_statistic"), z)
+    ll = s.model_log_likelihood()
+    s.close()
+    for r, a in enumerate(arrs):
+        assert np.allclose(a["ll"], ll, rtol=1e-12, atol=0), f"rank {r}: LL {a['ll']} against {ll}"
 
 
 def test_a_rank_that_dies_gives_its_peers_an_error_not_a_hang(tmp_path, fake_rccl):
