@@ -336,6 +336,65 @@ int mvhdp_discr_weights(mvhdp_handle h, double* per_view /*[M]*/, int32_t m, dou
  * MVHDP_ERR_STATE, outputs untouched. */
 int mvhdp_diagnostics(mvhdp_handle h, const mvhdp_diag_args* args, mvhdp_diag_out* out);
 
+/* ---- word and topic embeddings: trainTypeVectors (PTM:517-524, 1186-1206, 1495-1498) and SciTopicFlow.runWordEmbeddings (FLOW:115-136).
+ * TWE = MVTopicModel/TopicWordEmbeddings.java, TWER = MVTopicModel/TopicWordEmbeddingRunnable.java.  WordEmbeddings is TWE with no
+ * topics and no context columns: the same trainer with with_topics = 0 (a WordEmbeddings host makes a K = 1, M = 1 handle over its
+ * text).  Rows: the V_0 word rows, then (with topics) the K topic rows; weights and negative weights [R][C] in fp64 on the device.
+ * Skip-gram with negative sampling over view 0 plus the terms that tie each token to its topic (TWER:261-291); tokens and z are read
+ * straight from the handle.  Every draw comes from Philox4x32-10.  A group of document shards has no form of
+ * this: a member trains on its own entities only.  The softmax table p_emb(w|t) stays on the device for the useVectorsLambda mix of
+ * the sweep, which is not done yet: useVectorsLambda stays 0. ---- */
+typedef struct {
+    int32_t num_columns;                 /* C, 1..256 (PTM:523 vectorSize; FLOW:74 uses 200) */
+    int32_t num_context_columns;         /* Cc, 0 <= Cc < C: columns [0, Cc) "context", [Cc, C) "content" (50); ignored without topics (TWE:136) */
+    int32_t with_topics;                 /* 1: TopicWordEmbeddings (R = V_0 + K), 0: WordEmbeddings (R = V_0) */
+    int32_t window;                      /* windowSize >= 1 (5) */
+    int32_t num_samples;                 /* negatives per call, 0..32 (5) */
+    int32_t min_doc_length;              /* entities keeping fewer tokens are skipped, >= 1 (10) */
+    int64_t sampling_table_size;         /* 1..2^31-1 (10^8) */
+    double  sampling_factor;             /* countWords(data, f) (1e-4) */
+    double  min_exp, max_exp;            /* sigmoid bounds (-6, 6) */
+    int32_t sigmoid_cache_size;          /* 1..4096 (1000) */
+    int32_t reserved;                    /* 0 */
+} mvhdp_emb_config;
+typedef struct {                         /* one mvhdp_emb_train, summed over its epochs */
+    int64_t words_so_far;                /* view-0 tokens visited (TWER:243) */
+    int64_t words_sampled;               /* tokens kept by the subsampling (TWER:251) */
+    int64_t words_considered;            /* kept tokens of the entities not skipped (TWER:263) */
+    int64_t docs_skipped;                /* entities keeping fewer than min_doc_length tokens (TWER:257) */
+    int64_t calls;                       /* gradientLearn calls (numUpdates TWER:146) */
+    int64_t negatives_skipped;           /* negative draws equal to the input row (TWER:119) */
+    double  residual;                    /* sum of the residuals (TWER:114,142); getMeanError = residual / calls */
+    double  last_epoch_residual;         /* the same over the last epoch */
+    int64_t last_epoch_calls;
+    double  kernel_ms;
+} mvhdp_emb_stats;
+#define MVHDP_EMB_SERIAL 0x1u            /* one wave, entities in id order: deterministic, the restatement's order.  Default: Hogwild */
+/* new TopicWordEmbeddings(alphabet[0], C, Cc, window, K, ..) TWE:126-163 / new WordEmbeddings WE:119-145: weights = (u - 0.5) / C
+ * (or the caller's [R][C]) and negative weights 0; the sigmoid cache TWE:157-162 with cache[size] left 0.0.  Replaces any earlier state. */
+int mvhdp_emb_init(mvhdp_handle h, const mvhdp_emb_config* cfg, const double* weights /*[R][C] or NULL*/, uint64_t seed);
+/* countWords(data, f) TWE:341-401 over the handle's view-0 tokens: wordCounts and totalWords cumulative over calls (kept quirk),
+ * retention[w] = min((sqrt(s) + 1) / s, 1) with s = count / (f total), the sampling table equal index for index to the reference's. */
+int mvhdp_emb_count_words(mvhdp_handle h);
+/* train(data, threads, num_samples, epochs) TWE:423-483 with TWER:82-293: `epochs` passes over the entities in id order.  Learning rate
+ * of entity d in epoch e: max(0.025e-4, 0.025 (1 - (e N_0 + doc_off[d]) / (epochs totalWords))).  seed and round select the streams.
+ * MVHDP_ERR_INVALID_ARG, vectors untouched, for a view-0 token outside [0, V_0) or, with topics, a z outside [0, K). */
+int mvhdp_emb_train(mvhdp_handle h, int32_t epochs, uint64_t seed, uint32_t round, uint32_t flags, mvhdp_emb_stats* stats /* or NULL */);
+/* getWordVectors / getTopicVectors TWE:726-745 (the rows from V_0 on are the topics), writeContext, checkpoints.  Either may be NULL. */
+int mvhdp_emb_get_vectors(mvhdp_handle h, double* weights /*[R][C]*/, double* negative_weights /*[R][C]*/);
+int mvhdp_emb_set_vectors(mvhdp_handle h, const double* weights /*[R][C]*/, const double* negative_weights /*[R][C]*/);
+/* probes of countWords: cumulative counts [V_0], retention [V_0], totalWords; table entries [first, first + n) */
+int mvhdp_emb_word_stats(mvhdp_handle h, int64_t* counts /* or NULL */, double* retention /* or NULL */, int64_t* total_words /* or NULL */);
+int mvhdp_emb_sampling_table(mvhdp_handle h, int64_t first, int64_t n, int32_t* types /*[n]*/);
+/* CalcSoftmaxTopicWordProbabilities PTM:337-367 (with topics): dot over all C columns of word row w and topic row t, exp(dot - max_w dot)
+ * kept on the device as [V_0][K]; sum_exp[t] accumulates over calls as PTM:360 does (reset_sums = 1: from 0).  Copies may be NULL. */
+int mvhdp_emb_softmax(mvhdp_handle h, int32_t reset_sums, double* exp_dot /*[K][V_0]*/, double* sum_exp /*[K]*/);
+/* findClosest(v) TWE:485-540: the n (1..64) word rows and topic rows of highest cosine against query [C] in IDSorter order (cosine
+ * descending, ties by descending id); slots beyond V_0 / K hold -1 / NaN.  topics / topic_sims may be NULL (no topics: untouched). */
+int mvhdp_emb_nearest(mvhdp_handle h, const double* query /*[C]*/, int32_t n, int32_t* words, double* word_sims, int32_t* topics, double* topic_sims);
+/* frees the embedding state (mvhdp_destroy and the exit handler do too) */
+int mvhdp_emb_release(mvhdp_handle h);
+
 /* ---- the hot path ---- */
 /* One Gibbs sweep over every entity: replaces "submit updaters + submit
  * workers + barrier.await()" PTM:1213-1239, i.e. WRK:186-233 x nst threads and

@@ -17,6 +17,8 @@ ABI_SYMBOLS = [
     "mvhdp_get_count_histogram", "mvhdp_view_overlap_sums", "mvhdp_model_log_likelihood", "mvhdp_doc_topic_proportions",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
+    "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
+    "mvhdp_emb_word_stats", "mvhdp_emb_sampling_table", "mvhdp_emb_softmax", "mvhdp_emb_nearest", "mvhdp_emb_release",
     "mvhdp_sweep", "mvhdp_sweep_many", "mvhdp_get_tuning", "mvhdp_set_tuning", "mvhdp_plan_probe", "mvhdp_tuner_probe",
     "mvhdp_apply_delta", "mvhdp_apply_delta_begin", "mvhdp_apply_delta_rows", "mvhdp_apply_delta_end",
     "mvhdp_get_birth_keys", "mvhdp_activate_births",
@@ -113,6 +115,20 @@ class DiagOutC(C.Structure):
                 ("top_counts", C.c_void_p), ("nonzero", C.c_void_p), ("num_rank1_docs", C.c_void_p), ("num_nonzero_docs", C.c_void_p),
                 ("num_docs_at_proportions", C.c_void_p), ("sum_count_log_count", C.c_void_p), ("word_type_counts", C.c_void_p),
                 ("num_tokens", C.c_void_p), ("discr_weight_per_view", C.c_void_p)]
+
+
+class EmbConfigC(C.Structure):
+    _fields_ = [("num_columns", C.c_int32), ("num_context_columns", C.c_int32), ("with_topics", C.c_int32), ("window", C.c_int32),
+                ("num_samples", C.c_int32), ("min_doc_length", C.c_int32), ("sampling_table_size", C.c_int64),
+                ("sampling_factor", C.c_double), ("min_exp", C.c_double), ("max_exp", C.c_double),
+                ("sigmoid_cache_size", C.c_int32), ("reserved", C.c_int32)]
+
+
+class EmbStatsC(C.Structure):
+    _fields_ = [("words_so_far", C.c_int64), ("words_sampled", C.c_int64), ("words_considered", C.c_int64),
+                ("docs_skipped", C.c_int64), ("calls", C.c_int64), ("negatives_skipped", C.c_int64),
+                ("residual", C.c_double), ("last_epoch_residual", C.c_double), ("last_epoch_calls", C.c_int64),
+                ("kernel_ms", C.c_double)]
 
 
 _lib = None
@@ -229,6 +245,16 @@ def load_library():
     L.mvhdp_top_words.argtypes = [vp, i32, i32, vp, vp, vp]
     L.mvhdp_discr_weights.argtypes = [vp, vp, i32, vp]
     L.mvhdp_diagnostics.argtypes = [vp, C.POINTER(DiagArgsC), C.POINTER(DiagOutC)]
+    L.mvhdp_emb_init.argtypes = [vp, C.POINTER(EmbConfigC), vp, u64]
+    L.mvhdp_emb_count_words.argtypes = [vp]
+    L.mvhdp_emb_train.argtypes = [vp, i32, u64, u32, u32, C.POINTER(EmbStatsC)]
+    L.mvhdp_emb_get_vectors.argtypes = [vp, vp, vp]
+    L.mvhdp_emb_set_vectors.argtypes = [vp, vp, vp]
+    L.mvhdp_emb_word_stats.argtypes = [vp, vp, vp, vp]
+    L.mvhdp_emb_sampling_table.argtypes = [vp, i64, i64, vp]
+    L.mvhdp_emb_softmax.argtypes = [vp, i32, vp, vp]
+    L.mvhdp_emb_nearest.argtypes = [vp, vp, i32, vp, vp, vp, vp]
+    L.mvhdp_emb_release.argtypes = [vp]
     L.mvhdp_sweep.argtypes = [vp, u32, u64, u32, vp, C.POINTER(DebugC), C.POINTER(SweepStatsC)]
     L.mvhdp_sweep_many.argtypes = [vp, u32, i32, u64, u32, vp]
     L.mvhdp_get_tuning.argtypes = [vp, C.POINTER(TuningC)]

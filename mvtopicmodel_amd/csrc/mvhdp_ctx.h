@@ -19,6 +19,8 @@
 #include <vector>
 
 
+struct EmbState;                             // mvhdp_emb.hip: the word and topic embeddings of a handle
+
 struct mvhdp_ctx {
     mvhdp_config cfg{};
     MvModel mm{};
@@ -109,6 +111,7 @@ struct mvhdp_ctx {
     WalkTuner wt;                            // the walk-threshold search
     bool dbg_env = false;                    // MVHDP_DEBUG was set at create
     size_t lds_attr_set = 0;
+    EmbState* emb = nullptr;                 // mvhdp_emb_init .. mvhdp_emb_release
 };
 
 
@@ -192,3 +195,6 @@ int mvhdp_diag_check_args(mvhdp_ctx* h, const mvhdp_diag_args* args, const mvhdp
 int mvhdp_diag_model(mvhdp_ctx* h, int N, DiagModel& dm);
 int mvhdp_diag_docs(mvhdp_ctx* h, const DiagModel& dm, DiagAcc& acc);
 int mvhdp_diag_finish(mvhdp_ctx* h, const DiagModel& dm, const DiagAcc& acc, const mvhdp_diag_args* args, const mvhdp_diag_out* out);
+
+// frees h->emb and its device buffers (mvhdp_emb.hip; release_device_resources calls it)
+void mvhdp_emb_free(mvhdp_ctx* h);

@@ -29,6 +29,8 @@ struct Shard {                       // what the jlong handle points to: the lib
     int V[MVHDP_MAX_MODALITIES] = {};
     jlong D = -1;
     jlong N[MVHDP_MAX_MODALITIES] = {};
+    jlong embR = 0;                  // rows of the embedding matrix (V_0, + K with topics); 0: none (nEmbInit .. nEmbRelease)
+    int embC = 0, embK = 0;          //   its columns, its topic rows
     int pins = 0;                    // JNI calls currently inside the library on this handle (guarded by g_reg_mutex)
 };
 
@@ -731,5 +733,152 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupDiagnost
     int rc = mvhdp_group_diagnostics(gr->g, &a, &o);
     if (rc) throw_group(env, gr->g, rc, "mvhdp_group_diagnostics");
 }
+
+// ---- word and topic embeddings (TopicWordEmbeddings TWE / TopicWordEmbeddingRunnable TWER; include/mvhdp.h mvhdp_emb_*) ----
+// Every array is flat and checked against the embedding shape the handle was given by nEmbInit: [R*C] vectors (R = V_0, + K with
+// topics), [V_0] word statistics, [K*V_0] softmax, [n] nearest.  null where the header allows it.
+static bool emb_missing(JNIEnv* env, const Shard* s)
+{
+    if (s->embR > 0) return false;
+    throw_msg(env, "java/lang/IllegalStateException", "embeddings: embInit has not been called");
+    return true;
+}
+
+// new TopicWordEmbeddings(alphabet[0], C, Cc, window, K, ..) TWE:126-163: ints {numColumns, numContextColumns, withTopics, window,
+// numSamples, minDocLength, sigmoidCacheSize}, doubles {samplingFactor, minExp, maxExp}; weights [R*C] or null (drawn on the device)
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbInit(JNIEnv* env, jclass, jlong p, jintArray ints, jlong tableSize, jdoubleArray doubles, jdoubleArray weights, jlong seed)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (bad_len(env, ints, 7, "embInit ints") || bad_len(env, doubles, 3, "embInit doubles")) return;
+    jint iv[7]; jdouble dv[3];
+    env->GetIntArrayRegion(ints, 0, 7, iv);
+    env->GetDoubleArrayRegion(doubles, 0, 3, dv);
+    mvhdp_emb_config c;
+    std::memset(&c, 0, sizeof c);
+    c.num_columns = iv[0]; c.num_context_columns = iv[1]; c.with_topics = iv[2] ? 1 : 0; c.window = iv[3]; c.num_samples = iv[4];
+    c.min_doc_length = iv[5]; c.sigmoid_cache_size = iv[6]; c.sampling_table_size = tableSize;
+    c.sampling_factor = dv[0]; c.min_exp = dv[1]; c.max_exp = dv[2];
+    const jlong R = (jlong)s->V[0] + (c.with_topics ? s->K : 0);
+    if (weights && (c.num_columns < 1 || bad_len(env, weights, R * c.num_columns, "embInit weights [R*C]"))) return;
+    Doubles w(env, weights, JNI_ABORT);
+    if (w.failed()) return;
+    int rc = mvhdp_emb_init(s->h, &c, w.p, static_cast<uint64_t>(seed));
+    if (rc) { s->embR = 0; throw_rt(env, s->h, rc, "mvhdp_emb_init"); return; }
+    s->embR = R; s->embC = c.num_columns; s->embK = c.with_topics ? s->K : 0;
+}
+
+// countWords(data, f) TWE:341-401 (cumulative, as the reference's)
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbCountWords(JNIEnv* env, jclass, jlong p)
+{ ShardPin pin_(p); Shard* s = pin_.s; if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+  int rc = mvhdp_emb_count_words(s->h); if (rc) throw_rt(env, s->h, rc, "mvhdp_emb_count_words"); }
+
+// train(data, threads, numSamples, epochs) TWE:423-483: longs [7] {wordsSoFar, wordsSampled, wordsConsidered, docsSkipped, calls,
+// negativesSkipped, lastEpochCalls}, doubles [3] {residual, lastEpochResidual, kernelMs}
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbTrain(JNIEnv* env, jclass, jlong p, jint epochs, jlong seed, jint round, jint flags, jlongArray longs, jdoubleArray doubles)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (bad_len(env, longs, 7, "embTrain longs") || bad_len(env, doubles, 3, "embTrain doubles")) return;
+    mvhdp_emb_stats st;
+    std::memset(&st, 0, sizeof st);
+    int rc = mvhdp_emb_train(s->h, epochs, static_cast<uint64_t>(seed), static_cast<uint32_t>(round), static_cast<uint32_t>(flags), &st);
+    if (rc) { throw_rt(env, s->h, rc, "mvhdp_emb_train"); return; }
+    const jlong l[7] = {st.words_so_far, st.words_sampled, st.words_considered, st.docs_skipped, st.calls, st.negatives_skipped, st.last_epoch_calls};
+    const jdouble d[3] = {st.residual, st.last_epoch_residual, st.kernel_ms};
+    env->SetLongArrayRegion(longs, 0, 7, l);
+    env->SetDoubleArrayRegion(doubles, 0, 3, d);
+}
+
+// getWordVectors / getTopicVectors TWE:726-745 (rows V_0.. are the topics): [R*C] each, or null
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbGetVectors(JNIEnv* env, jclass, jlong p, jdoubleArray weights, jdoubleArray negativeWeights)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (emb_missing(env, s)) return;
+    const jlong n = s->embR * s->embC;
+    if ((weights && bad_len(env, weights, n, "embGetVectors weights")) || (negativeWeights && bad_len(env, negativeWeights, n, "embGetVectors negativeWeights"))) return;
+    Doubles w(env, weights, 0), g(env, negativeWeights, 0);
+    if (w.failed() || g.failed()) return;
+    int rc = mvhdp_emb_get_vectors(s->h, w.p, g.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_emb_get_vectors");
+}
+
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSetVectors(JNIEnv* env, jclass, jlong p, jdoubleArray weights, jdoubleArray negativeWeights)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (emb_missing(env, s)) return;
+    const jlong n = s->embR * s->embC;
+    if ((weights && bad_len(env, weights, n, "embSetVectors weights")) || (negativeWeights && bad_len(env, negativeWeights, n, "embSetVectors negativeWeights"))) return;
+    Doubles w(env, weights, JNI_ABORT), g(env, negativeWeights, JNI_ABORT);
+    if (w.failed() || g.failed()) return;
+    int rc = mvhdp_emb_set_vectors(s->h, w.p, g.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_emb_set_vectors");
+}
+
+// wordCounts [V_0], retentionProbability [V_0] (either may be null), totalWords [1]
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbWordStats(JNIEnv* env, jclass, jlong p, jlongArray counts, jdoubleArray retention, jlongArray totalWords)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (emb_missing(env, s)) return;
+    if ((counts && bad_len(env, counts, s->V[0], "embWordStats counts")) || (retention && bad_len(env, retention, s->V[0], "embWordStats retention")) ||
+        bad_len(env, totalWords, 1, "embWordStats totalWords")) return;
+    Longs c(env, counts, 0);
+    Doubles r(env, retention, 0);
+    if (c.failed() || r.failed()) return;
+    int64_t total = 0;
+    int rc = mvhdp_emb_word_stats(s->h, reinterpret_cast<int64_t*>(c.p), r.p, &total);
+    if (rc) { throw_rt(env, s->h, rc, "mvhdp_emb_word_stats"); return; }
+    const jlong t = total;
+    env->SetLongArrayRegion(totalWords, 0, 1, &t);
+}
+
+// samplingTable[first .. first + types.length)
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSamplingTable(JNIEnv* env, jclass, jlong p, jlong first, jintArray types)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (emb_missing(env, s)) return;
+    if (!types) { throw_msg(env, "java/lang/IllegalArgumentException", "embSamplingTable: types is null"); return; }
+    Ints t(env, types, 0);
+    if (t.failed()) return;
+    int rc = mvhdp_emb_sampling_table(s->h, first, env->GetArrayLength(types), t.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_emb_sampling_table");
+}
+
+// CalcSoftmaxTopicWordProbabilities PTM:337-367: expDotProductValues [K*V_0] or null, sumExpValues [K] (accumulated, PTM:360) or null
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSoftmax(JNIEnv* env, jclass, jlong p, jboolean resetSums, jdoubleArray expDot, jdoubleArray sumExp)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (emb_missing(env, s)) return;
+    if ((expDot && bad_len(env, expDot, (jlong)s->embK * s->V[0], "embSoftmax expDot [K*V_0]")) || (sumExp && bad_len(env, sumExp, s->embK, "embSoftmax sumExp"))) return;
+    Doubles e(env, expDot, 0), m(env, sumExp, 0);
+    if (e.failed() || m.failed()) return;
+    int rc = mvhdp_emb_softmax(s->h, resetSums ? 1 : 0, e.p, m.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_emb_softmax");
+}
+
+// findClosest TWE:485-540: query [C]; words / wordSims [n]; topics / topicSims [n] or null
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbNearest(JNIEnv* env, jclass, jlong p, jdoubleArray query, jint n, jintArray words, jdoubleArray wordSims, jintArray topics, jdoubleArray topicSims)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if (emb_missing(env, s)) return;
+    if (n < 1 || n > 64) { throw_msg(env, "java/lang/IllegalArgumentException", "embNearest: n must be 1..64"); return; }
+    if (bad_len(env, query, s->embC, "embNearest query") || bad_len(env, words, n, "embNearest words") || bad_len(env, wordSims, n, "embNearest wordSims") ||
+        (topics && bad_len(env, topics, n, "embNearest topics")) || (topicSims && bad_len(env, topicSims, n, "embNearest topicSims"))) return;
+    Doubles q(env, query, JNI_ABORT), ws(env, wordSims, 0), ts(env, topicSims, 0);
+    Ints w(env, words, 0), t(env, topics, 0);
+    if (q.failed() || ws.failed() || ts.failed() || w.failed() || t.failed()) return;
+    int rc = mvhdp_emb_nearest(s->h, q.p, n, w.p, ws.p, t.p, ts.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_emb_nearest");
+}
+
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbRelease(JNIEnv* env, jclass, jlong p)
+{ ShardPin pin_(p); Shard* s = pin_.s; if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+  int rc = mvhdp_emb_release(s->h); if (rc) { throw_rt(env, s->h, rc, "mvhdp_emb_release"); return; } s->embR = 0; s->embC = 0; s->embK = 0; }
 
 }  // extern "C"

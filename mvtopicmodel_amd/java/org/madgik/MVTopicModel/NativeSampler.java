@@ -99,6 +99,49 @@ public final class NativeSampler implements AutoCloseable {
         return st;
     }
 
+    /** mvhdp_emb_config: the shape of TopicWordEmbeddings(alphabet[0], numColumns, numContextColumns, window, numTopics, ..) (TWE:126-163)
+     *  and what countWords / train take; the defaults are the reference's (PTM:523, FLOW:74, train(data, threads, 5, 2)). */
+    public static final class EmbConfig {
+        public int numColumns = 200, numContextColumns = 50, window = 5, numSamples = 5, minDocLength = 10, sigmoidCacheSize = 1000;
+        public boolean withTopics = true;                     // false: WordEmbeddings (FLOW:115-136; no topic rows, no context columns)
+        public long samplingTableSize = 100000000L;
+        public double samplingFactor = 1e-4, minExp = -6.0, maxExp = 6.0;
+    }
+    /** What one embTrain reports (mvhdp_emb_stats), summed over its epochs. */
+    public static final class EmbStats {
+        public long wordsSoFar, wordsSampled, wordsConsidered, docsSkipped, calls, negativesSkipped, lastEpochCalls;
+        public double residual, lastEpochResidual, kernelMs;
+        public double meanError() { return lastEpochCalls == 0 ? 0.0 : lastEpochResidual / lastEpochCalls; }   // getMeanError TWER:70-79
+    }
+    public static final int EMB_SERIAL = 0x1;             // one wave, entities in id order (deterministic); default: Hogwild
+    /** new TopicWordEmbeddings TWE:126-163 on the device; weightsFlat [R*C] (R = V_0, + K with topics) or null: drawn on the device. */
+    public void embInit(EmbConfig c, double[] weightsFlat, long seed) {
+        int[] ints = {c.numColumns, c.numContextColumns, c.withTopics ? 1 : 0, c.window, c.numSamples, c.minDocLength, c.sigmoidCacheSize};
+        nEmbInit(handle, ints, c.samplingTableSize, new double[] {c.samplingFactor, c.minExp, c.maxExp}, weightsFlat, seed);
+    }
+    /** matrix.countWords(data, samplingFactor) TWE:341-401 over the view-0 tokens set with setCorpus (cumulative, as the reference's). */
+    public void embCountWords() { nEmbCountWords(handle); }
+    /** matrix.train(data, numThreads, numSamples, epochs) TWE:423-483 over view 0 and its current assignments. */
+    public EmbStats embTrain(int epochs, long seed, int round, int flags) {
+        long[] l = new long[7]; double[] d = new double[3];
+        nEmbTrain(handle, epochs, seed, round, flags, l, d);
+        EmbStats st = new EmbStats();
+        st.wordsSoFar = l[0]; st.wordsSampled = l[1]; st.wordsConsidered = l[2]; st.docsSkipped = l[3]; st.calls = l[4];
+        st.negativesSkipped = l[5]; st.lastEpochCalls = l[6]; st.residual = d[0]; st.lastEpochResidual = d[1]; st.kernelMs = d[2];
+        return st;
+    }
+    /** weights / negativeWeights [R*C] row-major, or null: getWordVectors (rows 0..V_0) / getTopicVectors (rows V_0..) TWE:726-745. */
+    public void embGetVectors(double[] weightsFlat, double[] negativeWeightsFlat) { nEmbGetVectors(handle, weightsFlat, negativeWeightsFlat); }
+    public void embSetVectors(double[] weightsFlat, double[] negativeWeightsFlat) { nEmbSetVectors(handle, weightsFlat, negativeWeightsFlat); }
+    /** wordCounts [V_0] and retentionProbability [V_0] (or null); returns totalWords. */
+    public long embWordStats(long[] counts, double[] retention) { long[] t = new long[1]; nEmbWordStats(handle, counts, retention, t); return t[0]; }
+    public void embSamplingTable(long first, int[] types) { nEmbSamplingTable(handle, first, types); }
+    /** CalcSoftmaxTopicWordProbabilities PTM:337-367: expDotProductValues [K*V_0] (or null), sumExpValues [K] accumulated over calls. */
+    public void embSoftmax(boolean resetSums, double[] expDotFlat, double[] sumExp) { nEmbSoftmax(handle, resetSums, expDotFlat, sumExp); }
+    /** findClosest TWE:485-540: the n (1..64) closest words and topics by cosine, IDSorter order. */
+    public void embNearest(double[] query, int n, int[] words, double[] wordSims, int[] topics, double[] topicSims) { nEmbNearest(handle, query, n, words, wordSims, topics, topicSims); }
+    public void embRelease() { nEmbRelease(handle); }
+
     /**
      * The sweep's own choices (mvhdp_tuning): none of them changes a result.  learntWalkStep / treeBranchShare are what the
      * library's walk-threshold search has found -- read them from one sampler and hand them to another (a document shard, a
@@ -287,4 +330,14 @@ public final class NativeSampler implements AutoCloseable {
     private static native void nGroupDiagnostics(long g, int n, int[] wordLength, double[] scores, double[] wordScores, int[] codoc, int[] topTypes,
                                                  int[] topCounts, int[] nonzero, int[] rank1Docs, int[] nonzeroDocs, int[] atProportions,
                                                  double[] sumCountLogCount, int[] wordTypeCounts, long[] numTokens, double[] perView);
+    private static native void nEmbInit(long h, int[] ints, long tableSize, double[] doubles, double[] weights, long seed);
+    private static native void nEmbCountWords(long h);
+    private static native void nEmbTrain(long h, int epochs, long seed, int round, int flags, long[] longs, double[] doubles);
+    private static native void nEmbGetVectors(long h, double[] weights, double[] negativeWeights);
+    private static native void nEmbSetVectors(long h, double[] weights, double[] negativeWeights);
+    private static native void nEmbWordStats(long h, long[] counts, double[] retention, long[] totalWords);
+    private static native void nEmbSamplingTable(long h, long first, int[] types);
+    private static native void nEmbSoftmax(long h, boolean resetSums, double[] expDot, double[] sumExp);
+    private static native void nEmbNearest(long h, double[] query, int n, int[] words, double[] wordSims, int[] topics, double[] topicSims);
+    private static native void nEmbRelease(long h);
 }

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   GroupInfoC, HyperC, MvhdpError, SweepStatsC, TuningC, load_library)
+                   EmbConfigC, EmbStatsC, GroupInfoC, HyperC, MvhdpError, SweepStatsC, TuningC, load_library)
 
 SWEEP_REUSE_TREES = 0x1
 SWEEP_NO_APPLY = 0x2
@@ -32,6 +32,8 @@ def SWEEP_LIVE_SEGMENTS(n):
 def SWEEP_ONLY_SEGMENT(s):
     return ((int(s) + 1) & 0xFF) << 24
 
+
+EMB_SERIAL = 0x1
 
 BUF_COUNTS = 0
 BUF_DELTA = 1
@@ -101,6 +103,47 @@ class SweepStats:
     reserved: int = 0
     dbg: list = field(default=None, repr=False)
     trace: np.ndarray = field(default=None, repr=False)
+
+
+@dataclass
+class EmbConfig:
+    """mvhdp_emb_config: the shape of TopicWordEmbeddings(alphabet[0], C, Cc, window, K, ..) (TWE:126-163) and what countWords /
+    train take.  defaults() are the reference's values: C = vectorSize 200 (FLOW:74), Cc = 50 (PTM:523), train(data, threads, 5, 2)."""
+    num_columns: int = 200
+    num_context_columns: int = 50
+    with_topics: bool = True
+    window: int = 5
+    num_samples: int = 5
+    min_doc_length: int = 10
+    sampling_table_size: int = 100_000_000
+    sampling_factor: float = 1e-4
+    min_exp: float = -6.0
+    max_exp: float = 6.0
+    sigmoid_cache_size: int = 1000
+
+    @staticmethod
+    def defaults(with_topics=True, **kw):
+        kw.setdefault("num_context_columns", 50 if with_topics else 0)
+        return EmbConfig(with_topics=bool(with_topics), **kw)
+
+    def to_c(self):
+        return EmbConfigC(int(self.num_columns), int(self.num_context_columns), int(bool(self.with_topics)), int(self.window),
+                          int(self.num_samples), int(self.min_doc_length), int(self.sampling_table_size), float(self.sampling_factor),
+                          float(self.min_exp), float(self.max_exp), int(self.sigmoid_cache_size), 0)
+
+
+@dataclass
+class EmbStats:
+    words_so_far: int = 0
+    words_sampled: int = 0
+    words_considered: int = 0
+    docs_skipped: int = 0
+    calls: int = 0
+    negatives_skipped: int = 0
+    residual: float = 0.0
+    last_epoch_residual: float = 0.0
+    last_epoch_calls: int = 0
+    kernel_ms: float = 0.0
 
 
 def java_string_lengths(vocabulary):
@@ -352,6 +395,84 @@ class NativeSampler:
         rc, d = _run_diagnostics(self.L, self.L.mvhdp_diagnostics, self.h, self.K, self.V[0], self.M, num_top_words, vocabulary, word_length)
         self._ck(rc)
         return d
+
+    # -- word and topic embeddings (TopicWordEmbeddings; include/mvhdp.h mvhdp_emb_*) ---------------------------------
+    def emb_init(self, cfg: EmbConfig, weights=None, seed=0):
+        """new TopicWordEmbeddings (TWE:126-163): rows V_0 words (+ K topics with cfg.with_topics), C columns."""
+        c = cfg.to_c()
+        rows = self.V[0] + (self.K if cfg.with_topics else 0)
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float64)
+        if w is not None and w.shape != (rows, cfg.num_columns):
+            raise ValueError(f"weights must be [{rows}][{cfg.num_columns}]")
+        self._emb_shape = None
+        self._ck(self.L.mvhdp_emb_init(self.h, C.byref(c), _ptr(w), int(seed)))
+        self._emb_shape = (rows, int(cfg.num_columns), int(self.K if cfg.with_topics else 0))
+
+    def _emb_dims(self):
+        """(rows, columns, topic rows) of the embeddings; MvhdpError(STATE) as the library gives it before emb_init."""
+        if getattr(self, "_emb_shape", None) is None:
+            raise MvhdpError(-2, "embeddings: mvhdp_emb_init has not been called")
+        return self._emb_shape
+
+    def emb_count_words(self):
+        """countWords(data, f) TWE:341-401 over view 0 (cumulative)."""
+        self._ck(self.L.mvhdp_emb_count_words(self.h))
+
+    def emb_train(self, epochs, seed, round_idx=0, serial=False) -> EmbStats:
+        """train(data, threads, num_samples, epochs) TWE:423-483; serial: one wave in entity order (deterministic)."""
+        st = EmbStatsC()
+        self._ck(self.L.mvhdp_emb_train(self.h, int(epochs), int(seed), int(round_idx), EMB_SERIAL if serial else 0, C.byref(st)))
+        return EmbStats(**{f: getattr(st, f) for f, _ in EmbStatsC._fields_})
+
+    def emb_get_vectors(self):
+        """(weights, negative_weights), each [R][C]: word rows, then topic rows (getWordVectors / getTopicVectors)."""
+        R, ncol, _ = self._emb_dims()
+        w = np.empty((R, ncol), dtype=np.float64)
+        n = np.empty((R, ncol), dtype=np.float64)
+        self._ck(self.L.mvhdp_emb_get_vectors(self.h, _ptr(w), _ptr(n)))
+        return w, n
+
+    def emb_set_vectors(self, weights=None, negative_weights=None):
+        R, ncol, _ = self._emb_dims()
+        a = [None if x is None else np.ascontiguousarray(x, dtype=np.float64) for x in (weights, negative_weights)]
+        for x in a:
+            if x is not None and x.shape != (R, ncol):
+                raise ValueError(f"vectors must be [{R}][{ncol}]")
+        self._ck(self.L.mvhdp_emb_set_vectors(self.h, _ptr(a[0]), _ptr(a[1])))
+
+    def emb_word_stats(self):
+        """(cumulative wordCounts [V_0] int64, retentionProbability [V_0], totalWords)."""
+        self._emb_dims()
+        c = np.empty(self.V[0], dtype=np.int64)
+        r = np.empty(self.V[0], dtype=np.float64)
+        t = C.c_int64()
+        self._ck(self.L.mvhdp_emb_word_stats(self.h, _ptr(c), _ptr(r), C.byref(t)))
+        return c, r, t.value
+
+    def emb_sampling_table(self, first, n):
+        out = np.empty(int(n), dtype=np.int32)
+        self._ck(self.L.mvhdp_emb_sampling_table(self.h, int(first), int(n), _ptr(out)))
+        return out
+
+    def emb_softmax(self, reset_sums=False, want_exp=True):
+        """CalcSoftmaxTopicWordProbabilities PTM:337-367: (expDotProductValues [K][V_0] or None, sumExpValues [K], accumulated)."""
+        _, _, K = self._emb_dims()
+        e = np.empty((K, self.V[0]), dtype=np.float64) if want_exp else None
+        s = np.empty(K, dtype=np.float64)
+        self._ck(self.L.mvhdp_emb_softmax(self.h, 1 if reset_sums else 0, _ptr(e), _ptr(s)))
+        return e, s
+
+    def emb_nearest(self, query, n=10):
+        """findClosest TWE:485-540: (words [n], word cosines [n], topics [n], topic cosines [n]) in IDSorter order."""
+        q = np.ascontiguousarray(query, dtype=np.float64)
+        w, ws = np.empty(int(n), np.int32), np.empty(int(n), np.float64)
+        t, ts = np.full(int(n), -1, np.int32), np.full(int(n), np.nan)
+        self._ck(self.L.mvhdp_emb_nearest(self.h, _ptr(q), int(n), _ptr(w), _ptr(ws), _ptr(t), _ptr(ts)))
+        return w, ws, t, ts
+
+    def emb_release(self):
+        self._ck(self.L.mvhdp_emb_release(self.h))
+        self._emb_shape = None
 
     # -- the hot path ---------------------------------------------------------
     def sweep(self, sweep_idx, seed, flags=0, p=None, want_dbg=False, trace=None) -> SweepStats:
