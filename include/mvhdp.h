@@ -343,7 +343,7 @@ int mvhdp_diagnostics(mvhdp_handle h, const mvhdp_diag_args* args, mvhdp_diag_ou
  * Skip-gram with negative sampling over view 0 plus the terms that tie each token to its topic (TWER:261-291); tokens and z are read
  * straight from the handle.  Every draw comes from Philox4x32-10.  A group of document shards has no form of
  * this: a member trains on its own entities only.  The softmax table p_emb(w|t) stays on the device for the useVectorsLambda mix of
- * the sweep, which is not done yet: useVectorsLambda stays 0. ---- */
+ * the sweep: mvhdp_set_vectors_mix(h, lambda, NULL, NULL) below hands it to the samplers. ---- */
 typedef struct {
     int32_t num_columns;                 /* C, 1..256 (PTM:523 vectorSize; FLOW:74 uses 200) */
     int32_t num_context_columns;         /* Cc, 0 <= Cc < C: columns [0, Cc) "context", [Cc, C) "content" (50); ignored without topics (TWE:136) */
@@ -392,8 +392,35 @@ int mvhdp_emb_softmax(mvhdp_handle h, int32_t reset_sums, double* exp_dot /*[K][
 /* findClosest(v) TWE:485-540: the n (1..64) word rows and topic rows of highest cosine against query [C] in IDSorter order (cosine
  * descending, ties by descending id); slots beyond V_0 / K hold -1 / NaN.  topics / topic_sims may be NULL (no topics: untouched). */
 int mvhdp_emb_nearest(mvhdp_handle h, const double* query /*[C]*/, int32_t n, int32_t* words, double* word_sims, int32_t* topics, double* topic_sims);
-/* frees the embedding state (mvhdp_destroy and the exit handler do too) */
+/* frees the embedding state (mvhdp_destroy and the exit handler do too); a mix that was set stands (it owns its table) */
 int mvhdp_emb_release(mvhdp_handle h);
+
+/* ---- useVectorsLambda: the sweep with the embeddings' p(w|t) mixed in, view 0 only (WRK:504-507, PTM:2673-2678, UPD:244-260):
+ *     p_wt = lambda * (expDotProductValues[k][w] / sumExpValues[k]) + (1 - lambda) * ((n_wk + beta_0) / (n_k + betaSum_0))
+ * in the document term of every view-0 token and in every leaf of a view-0 word tree (0 for an inactive topic, as ever).  Views m > 0,
+ * modelLogLikelihood, the diagnostics, mvhdp_build_inference_trees, mvhdp_init_assignments_from_trees and MVHDP_SWEEP_FROZEN do not use it
+ * (the inferencer's worker has lambda = 0, INF:251-252).
+ * lambda == 0: mix off (the state after mvhdp_create: the kernels launched are those of a handle that never set one).  0 < lambda <= 1: on.
+ * Anything else, NaN included: MVHDP_ERR_INVALID_ARG.  lambda is confined to [0, 1] because the samplers' certified prefix scan and their
+ * fp32 screening rest on every term of the document sum being non-negative.
+ * exp_dot [K][V_0] / sum_exp [K]: host arrays in the reference's layout, every entry finite, exp_dot >= 0, sum_exp > 0, every
+ * lambda * (exp_dot / sum_exp) finite and within fp32's range (else MVHDP_ERR_INVALID_ARG, the mix in force untouched); or both NULL: the handle's own softmax table and accumulated sums as the last
+ * mvhdp_emb_softmax left them (MVHDP_ERR_STATE when there is none).  The handle keeps lambda * (e / S) as a table of its own, [V_0][K] fp64,
+ * and its fp32 rounding for the samplers' fp32 screening (12 V_0 K bytes: 240 MB at V_0 = 50 000, K = 400; mvhdp_destroy and
+ * lambda = 0 free them): a later mvhdp_emb_softmax does NOT change what the samplers read until the next
+ * mvhdp_set_vectors_mix (the reference switches at one point too, PTM:1199-1207).  Invalidates the F+trees (mvhdp_trees_current -> 0).
+ * With a mix on:  deferred sweeps in every form (segments, ONLY_SEGMENT, NO_APPLY + mvhdp_apply_delta*, SEGMENT_APPLY, SEGMENT_OVERLAP,
+ * mvhdp_sweep_many, inactive topics) sample with it, bit for bit what the sequential restatement tests/native/mix_ref.c gives;
+ * MVHDP_SWEEP_LIVE runs in its stored-tree form only (mvhdp_tuning.live_rows is ignored: trees rebuilt with the mix at every segment border,
+ * four segments by default; the 16-bit mirror form, live16, works as without a mix); a group's members each carry their own copy
+ * (mvhdp_group_sweep: MVHDP_ERR_STATE when its local members disagree on lambda; across processes equality is the host's duty like the
+ * flags'; MVHDP_SWEEP_ASYNC_EXCHANGE and MVHDP_SWEEP_SHARD_BIRTHS with a mix: MVHDP_ERR_UNSUPPORTED).
+ * The walk-threshold search keeps a state of its own for sweeps with a mix; it is NOT persisted: mvhdp_get_tuning / mvhdp_set_tuning
+ * report and restore the search of the sweeps without a mix only (learnt_walk_step[3] stays reserved), so a resumed chain with a mix
+ * searches again. */
+int mvhdp_set_vectors_mix(mvhdp_handle h, double lambda, const double* exp_dot /*[K][V_0] or NULL*/, const double* sum_exp /*[K] or NULL*/);
+/* lambda (0: off) and, unless NULL, the table lambda * (e / S) as the device holds it, [V_0][K] (MVHDP_ERR_STATE when the mix is off).  Either may be NULL. */
+int mvhdp_get_vectors_mix(mvhdp_handle h, double* lambda, double* mix /*[V_0][K] or NULL*/);
 
 /* ---- the hot path ---- */
 /* One Gibbs sweep over every entity: replaces "submit updaters + submit
@@ -485,6 +512,9 @@ typedef struct {
     int32_t num_cus;                             /* 0 = 256 */
     int32_t kernel_registers[6][3];              /* VGPRs of each kernel class: plain, walk flavour, debug build */
     int32_t inactive_topics;                     /* 1: inActiveTopicIndex is not empty (a live sweep then takes more segments: a topic is born per border) */
+    int32_t vectors_mix;                         /* 1: a useVectorsLambda mix is set (mvhdp_set_vectors_mix): the mix flavours of the kernels run -- always the walk
+                                                    flavour --, a live sweep takes its stored-tree form.  0: today's plans, bit for bit */
+    int32_t kernel_registers_mix[6][3];          /* VGPRs of the mix flavours, as kernel_registers ([.][0] unused); a 0 takes the plain flavour's count */
 } mvhdp_plan_input;
 typedef struct {
     int32_t status;                              /* what mvhdp_sweep would return for these flags (MVHDP_OK or an error) */

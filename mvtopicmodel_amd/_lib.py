@@ -19,6 +19,7 @@ ABI_SYMBOLS = [
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
     "mvhdp_emb_word_stats", "mvhdp_emb_sampling_table", "mvhdp_emb_softmax", "mvhdp_emb_nearest", "mvhdp_emb_release",
+    "mvhdp_set_vectors_mix", "mvhdp_get_vectors_mix",
     "mvhdp_sweep", "mvhdp_sweep_many", "mvhdp_get_tuning", "mvhdp_set_tuning", "mvhdp_plan_probe", "mvhdp_tuner_probe",
     "mvhdp_apply_delta", "mvhdp_apply_delta_begin", "mvhdp_apply_delta_rows", "mvhdp_apply_delta_end",
     "mvhdp_get_birth_keys", "mvhdp_activate_births",
@@ -87,7 +88,8 @@ class PlanInputC(C.Structure):
                 ("max_entity_tokens", C.c_int64), ("entities_longer_than", C.c_int64 * 5),
                 ("tokens_by_list_rounds", C.c_uint64 * 17), ("entities_by_class", C.c_uint64 * 8),
                 ("flags", C.c_uint32), ("debug", C.c_int32), ("batch", C.c_int32), ("trees_current", C.c_int32),
-                ("num_cus", C.c_int32), ("kernel_registers", (C.c_int32 * 3) * 6), ("inactive_topics", C.c_int32)]
+                ("num_cus", C.c_int32), ("kernel_registers", (C.c_int32 * 3) * 6), ("inactive_topics", C.c_int32),
+                ("vectors_mix", C.c_int32), ("kernel_registers_mix", (C.c_int32 * 3) * 6)]
 
 
 class PlanOutputC(C.Structure):
@@ -255,6 +257,8 @@ def load_library():
     L.mvhdp_emb_softmax.argtypes = [vp, i32, vp, vp]
     L.mvhdp_emb_nearest.argtypes = [vp, vp, i32, vp, vp, vp, vp]
     L.mvhdp_emb_release.argtypes = [vp]
+    L.mvhdp_set_vectors_mix.argtypes = [vp, C.c_double, vp, vp]
+    L.mvhdp_get_vectors_mix.argtypes = [vp, C.POINTER(C.c_double), vp]
     L.mvhdp_sweep.argtypes = [vp, u32, u64, u32, vp, C.POINTER(DebugC), C.POINTER(SweepStatsC)]
     L.mvhdp_sweep_many.argtypes = [vp, u32, i32, u64, u32, vp]
     L.mvhdp_get_tuning.argtypes = [vp, C.POINTER(TuningC)]

@@ -174,13 +174,14 @@ extern "C" int mvhdp_create(const mvhdp_config* cfg, mvhdp_handle* out)
     h->d_doc_counter = h->d_ctl + ST_COUNT + 1 + META_WORDS64;                       // one work-queue head per kernel class
     CREATE_HIP(hipHostMalloc((void**)&h->h_ctl, CTL_WORDS * sizeof(unsigned long long), hipHostMallocDefault));   // pinned: the read-back never blocks the host
     for (int c = 0; c < MVHDP_N_CLASSES; c++)
-        for (int f = 0; f < 3; f++) h->regs.regs[c][f] = mvhdp_sweep_kernel_regs(c, f);
+        for (int f = 0; f < 3; f++) { h->regs.regs[c][f] = mvhdp_sweep_kernel_regs(c, f); h->regs.regs_mix[c][f] = mvhdp_sweep_kernel_regs(c, f ? f : 1, true); }
     read_environment(h);
     mm.alpha = h->d_alpha;
     mm.inactive = h->d_inactive;
     h->h_alpha.assign((size_t)M * (K + 1), 0.0);
     h->h_inactive.assign((size_t)K, 0);
     h->wt.init_defaults(K);
+    h->wt_mix.init_defaults(K);
     *out = h;
     return MVHDP_OK;
 }
@@ -196,6 +197,7 @@ static void release_device_resources(mvhdp_ctx* h)
     for (int m = 0; m < MVHDP_MAXM; m++) { fr(h->d_doc_off[m]); fr(h->d_tok[m]); fr(h->d_z[m]); fr(h->d_carry[m]); fr(h->d_present[m]); }
     fr(h->mm.counts); fr(h->mm.delta16); fr(h->mm.counts16); fr(h->mm.heavy); fr(h->mm.delta); fr(h->mm.trees); fr(h->mm.root); fr(h->mm.coef); fr(h->mm.mass0); fr(h->d_births); fr(h->d_birth_keys); fr(h->d_birth_table); fr(h->mm.dtab); fr(h->mm.p);
     fr(h->d_alpha); fr(h->d_inactive); fr(h->d_ctl);
+    fr(h->d_mix); fr(h->d_mix32); h->mm.mix = nullptr; h->mm.mix32 = nullptr; h->mix_lambda = 0.0;
     mvhdp_emb_free(h);
     if (h->h_ctl) { hipHostFree(h->h_ctl); h->h_ctl = nullptr; }
     h->d_stats = nullptr; h->d_act_key = nullptr; h->d_doc_counter = nullptr; h->d_ovf_meta = nullptr;
@@ -830,6 +832,7 @@ static void fill_plan_in(mvhdp_ctx* h, uint32_t flags, bool debug, bool batch, P
     in.unassigned = false;
     for (int m = 0; m < mm.M; m++) in.unassigned = in.unassigned || h->unassigned[m];
     in.first_inactive = mm.first_inactive;
+    in.vectors_mix = mm.mix != nullptr && !(flags & MVHDP_SWEEP_FROZEN);      // (the inferencer's worker has lambda = 0: INF:251-252)
     in.num_cus = h->num_cus; in.max_lds = h->max_lds;
     in.regs = h->regs;
 }
@@ -877,10 +880,12 @@ struct SegCtl {
 
 // Route pass + every class kernel of segment `seg` on stream s (the wider classes on the side streams behind a fork event, joined
 // back into s): positions seg, seg + nseg, ... of the longest-first order.  mk = the model these kernels read and update.
-static hipError_t launch_segment_kernels(mvhdp_ctx* h, const SweepPlan& p, const MvModel& mk, const SweepLaunch& sl, int seg, hipStream_t s,
+static hipError_t launch_segment_kernels(mvhdp_ctx* h, const SweepPlan& p, const MvModel& mk_in, const SweepLaunch& sl, int seg, hipStream_t s,
                                          const SegCtl& ctl, unsigned long long* d_stats)
 {
     const MvModel& mm = h->mm;
+    MvModel mk = mk_in;
+    if (p.frozen) { mk.mix = nullptr; mk.mix32 = nullptr; }                       // a FROZEN sweep samples without the mix (INF:251-252): the plain kernels
     const int nseg = p.nseg;
     hipError_t e = hipSuccess;
     auto step = [&](hipError_t r) { if (e == hipSuccess) e = r; };
@@ -1375,7 +1380,8 @@ static void learn_from_sweep(mvhdp_ctx* h, const SweepPlan& p, const unsigned lo
     const MvModel& mm = h->mm;
     bool any_walk = false;
     for (int c = 0; c < MVHDP_N_CLASSES; c++) any_walk = any_walk || (p.cls[c].used && p.cls[c].walk);
-    if (any_walk) h->wt.measured(mm.M, p.nseg, hs + ST_VIEW_BASE);
+    WalkTuner& wt = walk_tuner_of(h, p.flags);
+    if (any_walk) wt.measured(mm.M, p.nseg, hs + ST_VIEW_BASE);
     if (mm.D > 0 && p.only_seg >= 0) {
         // a single segment was swept: its histograms describe a part of the entities only -- the earlier ones stay (every plan of
         // a single-segment sweep launches whatever is reachable), only an abandoned entity asks for a recount
@@ -1387,7 +1393,7 @@ static void learn_from_sweep(mvhdp_ctx* h, const SweepPlan& p, const unsigned lo
     }
     if (h->dbg_env) {
         fprintf(stderr, "[mvhdp] walk threshold %.2f (base %.2f, phase %d, dir %+d, group %d); tree branch %.4f of tokens, walked on demand %.4f; per view tree share:",
-                (double)h->wt.walk_probe_i / MVHDP_WALK_BINS, (double)h->wt.walk_i / MVHDP_WALK_BINS, h->wt.walk_phase, h->wt.walk_dir, h->wt.walk_cls,
+                (double)wt.walk_probe_i / MVHDP_WALK_BINS, (double)wt.walk_i / MVHDP_WALK_BINS, wt.walk_phase, wt.walk_dir, wt.walk_cls,
                 (double)hs[ST_TREE] / std::max<double>(1.0, (double)hs[ST_TOKENS]), (double)hs[ST_ONDEMAND] / std::max<double>(1.0, (double)hs[ST_TOKENS]));
         for (int m = 0; m < mm.M; m++) {
             const double n = std::max<double>(1.0, (double)hs[ST_VIEW_BASE + m * MVHDP_VIEW_STATS]);
@@ -1410,7 +1416,7 @@ static void learn_from_sweep(mvhdp_ctx* h, const SweepPlan& p, const unsigned lo
                     (double)hs[ST_T_INIT] / hs[ST_N_WAVES], (double)hs[ST_T_FLUSH] / hs[ST_N_WAVES], (double)hs[ST_T_TOTAL] / hs[ST_N_WAVES]);
     }
     const double tokens = (double)hs[ST_TOKENS];
-    h->wt.observe(comparable && tokens > 0, p.walk_cfg, mm.M, tokens > 0 ? kernel_ms * 1e6 / tokens : 0.0);
+    wt.observe(comparable && tokens > 0, p.walk_cfg, mm.M, tokens > 0 ? kernel_ms * 1e6 / tokens : 0.0);
 }
 
 static void debug_print_plan(const mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_idx)
@@ -1459,7 +1465,7 @@ int mvhdp_sweep_begin(mvhdp_ctx* h, uint32_t sweep_idx, uint64_t seed, uint32_t 
     rc = ensure_slot_counts(h); if (rc) return rc;
     ps.flags = flags; ps.dbg = dbg; ps.debug = dbg != nullptr; ps.oc = SweepOutcome();
     PlanIn in; fill_plan_in(h, flags, ps.debug, false, in);
-    plan_sweep(in, h->tu, h->wt, ps.p);
+    plan_sweep(in, h->tu, walk_tuner_of(h, flags), ps.p);
     if (ps.p.err) FAIL(h, ps.p.err, ps.p.msg);
     rc = set_generic_lds(h, ps.p); if (rc) return rc;
     if (h->dbg_env) debug_print_plan(h, ps.p, sweep_idx);
@@ -1596,7 +1602,7 @@ extern "C" int mvhdp_sweep_many(mvhdp_handle h, uint32_t first_idx, int32_t n, u
     rc = ensure_slot_counts(h); if (rc) return rc;
     PlanIn in; fill_plan_in(h, flags, false, true, in);
     SweepPlan p;
-    plan_sweep(in, h->tu, h->wt, p);
+    plan_sweep(in, h->tu, walk_tuner_of(h, flags), p);
     if (p.err) FAIL(h, p.err, p.msg);
     rc = set_generic_lds(h, p); if (rc) return rc;
     if (h->dbg_env) debug_print_plan(h, p, first_idx);
@@ -1706,6 +1712,9 @@ extern "C" int mvhdp_plan_probe(const mvhdp_plan_input* pi, const mvhdp_tuning* 
     in.first_inactive = pi->inactive_topics ? 0 : -1;
     in.num_cus = pi->num_cus > 0 ? pi->num_cus : 256;
     for (int c = 0; c < MVHDP_N_CLASSES; c++) for (int f = 0; f < 3; f++) in.regs.regs[c][f] = pi->kernel_registers[c][f];
+    // (a probe that names no register counts for the mix flavours sizes them as the plain ones)
+    for (int c = 0; c < MVHDP_N_CLASSES; c++) for (int f = 0; f < 3; f++) in.regs.regs_mix[c][f] = pi->kernel_registers_mix[c][f] > 0 ? pi->kernel_registers_mix[c][f] : pi->kernel_registers[c][f];
+    in.vectors_mix = pi->vectors_mix != 0 && !(pi->flags & MVHDP_SWEEP_FROZEN);
     PlanTuning tu;
     WalkTuner wt;
     wt.init_defaults(in.K);

@@ -112,6 +112,12 @@ struct mvhdp_ctx {
     bool dbg_env = false;                    // MVHDP_DEBUG was set at create
     size_t lds_attr_set = 0;
     EmbState* emb = nullptr;                 // mvhdp_emb_init .. mvhdp_emb_release
+    // the useVectorsLambda mix (mvhdp_set_vectors_mix, mvhdp_emb.hip): the handle's own table lambda * (e / S), [V_0][K]; mm.mix points at it
+    // while 0 < lambda <= 1.  Its walk-threshold search is kept apart from the plain flavours' (a view-0 gather three times as wide -- a 2-byte mirror cell plus a 4-byte mix cell -- moves the optimum).
+    double* d_mix = nullptr;
+    float* d_mix32 = nullptr;                // its fp32 rounding (MvModel::mix32)
+    double mix_lambda = 0.0;
+    WalkTuner wt_mix;
 };
 
 
@@ -198,3 +204,5 @@ int mvhdp_diag_finish(mvhdp_ctx* h, const DiagModel& dm, const DiagAcc& acc, con
 
 // frees h->emb and its device buffers (mvhdp_emb.hip; release_device_resources calls it)
 void mvhdp_emb_free(mvhdp_ctx* h);
+// the walk-threshold search the coming sweep belongs to: the mix flavours keep their own
+static inline WalkTuner& walk_tuner_of(mvhdp_ctx* h, uint32_t flags) { return (h->mm.mix && !(flags & MVHDP_SWEEP_FROZEN)) ? h->wt_mix : h->wt; }

@@ -65,6 +65,14 @@ struct MvModel {
     double p_a[MVHDP_MAXM][MVHDP_MAXM], p_b[MVHDP_MAXM][MVHDP_MAXM];
     double* p;                         // [D][M][M] view weights (nullptr when M==1)
     int32_t first_inactive;            // inActiveTopicIndex.first() or -1
+    // The useVectorsLambda mix of view 0 (mvhdp_set_vectors_mix; WRK:504-507, PTM:2673-2678): p_wt = mix[w][k] + oml * ((n_wk + beta) / (n_k + betaSum))
+    // with mix[w][k] = lambda * (expDot[k][w] / sumExp[k]) formed once, rows parallel to the view-0 rows of n_wk (a slot's byte offset into its
+    // count row, doubled, is its offset into the mix row), and oml = 1 - lambda.  nullptr: the mix is off, and every launcher takes the
+    // instantiation without it -- the kernels of a handle that never set a mix are the ones they were.  (Last in the block: nothing moves.)
+    const double* mix;                 // [V_0][K] or nullptr
+    const float* mix32;                // [V_0][K] the same values rounded to fp32: what the fp32 screening of the register kernels gathers (a cell at
+                                       //   the byte offset of its count cell, half the lines of a mix row); the fp64 table serves the rare token that goes to fp64
+    double oml;
 };
 
 // SweepLaunch::flags, internal: a live sweep waits for its chunk-end atomics and invalidates the CU's L1 before it goes on (with one
@@ -207,8 +215,9 @@ hipError_t mvhdp_launch_sweep_fast(const MvModel& mm, const SweepLaunch& sl, int
 int mvhdp_sweep_fast_occupancy(int rmax, bool debug, bool walk, int block_threads, size_t lds_bytes);
 int mvhdp_sweep_generic_occupancy(bool debug, int block_threads, size_t lds_bytes);
 // VGPRs of the compiled sweep kernel of class c (0..4 register-resident, 5 generic); flavour 0: plain, 1: walk, 2: debug
-int mvhdp_sweep_kernel_regs(int cls, int flavour);
-int mvhdp_sweep_generic_regs(bool debug);
+// mix: the flavours compiled with the useVectorsLambda mix (MvModel::mix), which a sweep launches when a mix is set
+int mvhdp_sweep_kernel_regs(int cls, int flavour, bool mix = false);
+int mvhdp_sweep_generic_regs(bool debug, bool mix = false);
 
 #define MVHDP_DOC_BATCH 2
 #define MVHDP_HIST_BINS 17

@@ -777,3 +777,107 @@ extern "C" int mvhdp_emb_release(mvhdp_handle h)
     mvhdp_emb_free(h);
     return MVHDP_OK;
 }
+
+// ---------------------------------------------------------------------------------------------------------------
+// The useVectorsLambda mix of the sweep (PTM:1199-1207 hands the tables to the workers; WRK:504-507, PTM:2673-2678, UPD:244-260 use them):
+// the handle's own table mix[w][k] = lambda * (e[k][w] / S[k]) -- the first product of the reference's expression, its two operations in
+// the reference's order, each correctly rounded -- in the layout of the view-0 rows of n_wk.  The samplers and the tree kernel add
+// (1 - lambda) * the count ratio (MvModel::mix, MvModel::oml).
+// ---------------------------------------------------------------------------------------------------------------
+// e in the reference's layout [K][V0] (a host's tables)
+__global__ __launch_bounds__(256) void mix_from_kv_kernel(const double* __restrict__ e, const double* __restrict__ S, double lambda, int V0, int K, double* __restrict__ mix, float* __restrict__ mix32, unsigned int* __restrict__ bad)
+{
+    const int64_t n = (int64_t)V0 * K;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t w = i / K;
+        const int k = (int)(i - w * K);
+        const double v = lambda * (e[(int64_t)k * V0 + w] / S[k]);
+        mix[i] = v; mix32[i] = (float)v;
+        if (!(v >= 0.0 && v <= 1.7e308 && (double)(float)v <= 3.4e38)) atomicOr(bad, 1u);   // (a finite e over a tiny S: the quotient is checked, not only its parts)
+    }
+}
+// e as mvhdp_emb_softmax keeps it, [V0][K]
+__global__ __launch_bounds__(256) void mix_from_vk_kernel(const double* __restrict__ e, const double* __restrict__ S, double lambda, int V0, int K, double* __restrict__ mix, float* __restrict__ mix32, unsigned int* __restrict__ bad)
+{
+    const int64_t n = (int64_t)V0 * K;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const double v = lambda * (e[i] / S[i % K]);
+        mix[i] = v; mix32[i] = (float)v;
+        if (!(v >= 0.0 && v <= 1.7e308 && (double)(float)v <= 3.4e38)) atomicOr(bad, 1u);
+    }
+}
+
+extern "C" int mvhdp_set_vectors_mix(mvhdp_handle h, double lambda, const double* exp_dot, const double* sum_exp)
+{
+    CHECK_H(h);
+    if (!(lambda >= 0.0 && lambda <= 1.0)) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: lambda outside [0, 1]");
+    if ((exp_dot == nullptr) != (sum_exp == nullptr)) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: exp_dot and sum_exp go together (both, or both NULL)");
+    if (h->rows_applied >= 0) FAIL(h, MVHDP_ERR_STATE, "set_vectors_mix: an mvhdp_apply_delta_begin bracket is open");
+    const int V0 = h->mm.V[0], K = h->mm.K;
+    const size_t n = (size_t)V0 * K;
+    HIPC(h, hipSetDevice(h->device));
+    if (lambda == 0.0) {                                        // off: the state after mvhdp_create
+        HIPC(h, hipStreamSynchronize(h->stream));
+        if (h->d_mix) { hipFree(h->d_mix); h->d_mix = nullptr; }
+        if (h->d_mix32) { hipFree(h->d_mix32); h->d_mix32 = nullptr; }
+        h->mm.mix = nullptr; h->mm.mix32 = nullptr; h->mm.oml = 1.0; h->mix_lambda = 0.0;
+        h->have_trees = false;
+        return MVHDP_OK;
+    }
+    const double* S_host = sum_exp;
+    if (!exp_dot) {
+        EmbState* e = h->emb;
+        if (!e || !e->expdot || e->sum_exp.size() != (size_t)K || e->V0 != V0)
+            FAIL(h, MVHDP_ERR_STATE, "set_vectors_mix: no softmax table on the handle (mvhdp_emb_softmax has not been called)");
+        S_host = e->sum_exp.data();
+    } else {
+        for (size_t i = 0; i < n; i++) if (!(exp_dot[i] >= 0.0) || !std::isfinite(exp_dot[i])) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: an exp_dot entry is negative or not finite");
+    }
+    for (int k = 0; k < K; k++) if (!(S_host[k] > 0.0) || !std::isfinite(S_host[k])) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: a sum_exp entry is not a positive finite number");
+    // everything checked: from here on the new table replaces the old one
+    EmbBuf b;
+    double *d_S = nullptr, *d_e = nullptr, *d_new = nullptr;
+    HIPC(h, b.get(&d_S, (size_t)K));
+    if (exp_dot) HIPC(h, b.get(&d_e, n));
+    HIPC(h, hipMalloc(&d_new, n * sizeof(double)));
+    float* d_new32 = nullptr;
+    { hipError_t e32 = hipMalloc(&d_new32, n * sizeof(float) + 16); if (e32 != hipSuccess) { hipFree(d_new); HIPC(h, e32); } }
+    const hipStream_t st = h->stream;
+    unsigned int* d_bad = nullptr;
+    unsigned int h_bad = 0;
+    { hipError_t eb = b.get(&d_bad, (size_t)1); if (eb != hipSuccess) { hipFree(d_new); hipFree(d_new32); HIPC(h, eb); } }
+    hipError_t er = hipMemsetAsync(d_bad, 0, sizeof(unsigned int), st);
+    if (er == hipSuccess) er = hipMemcpyAsync(d_S, S_host, (size_t)K * 8, hipMemcpyHostToDevice, st);
+    if (er == hipSuccess && exp_dot) er = hipMemcpyAsync(d_e, exp_dot, n * 8, hipMemcpyHostToDevice, st);
+    if (er == hipSuccess) {
+        if (exp_dot) hipLaunchKernelGGL(mix_from_kv_kernel, dim3(grid_for((int64_t)n)), dim3(256), 0, st, d_e, d_S, lambda, V0, K, d_new, d_new32, d_bad);
+        else         hipLaunchKernelGGL(mix_from_vk_kernel, dim3(grid_for((int64_t)n)), dim3(256), 0, st, h->emb->expdot, d_S, lambda, V0, K, d_new, d_new32, d_bad);
+        er = hipGetLastError();
+    }
+    if (er == hipSuccess) er = hipMemcpyAsync(&h_bad, d_bad, sizeof(unsigned int), hipMemcpyDeviceToHost, st);
+    if (er == hipSuccess) er = hipStreamSynchronize(st);
+    if (er != hipSuccess) { hipFree(d_new); hipFree(d_new32); HIPC(h, er); }
+    if (h_bad) {                                               // the mix in force stays as it is
+        hipFree(d_new); hipFree(d_new32);
+        FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: lambda * (exp_dot / sum_exp) is not finite (or beyond fp32's range) for some cell");
+    }
+    if (h->d_mix) hipFree(h->d_mix);
+    if (h->d_mix32) hipFree(h->d_mix32);
+    h->d_mix = d_new; h->d_mix32 = d_new32;
+    h->mm.mix = d_new; h->mm.mix32 = d_new32; h->mm.oml = 1.0 - lambda; h->mix_lambda = lambda;
+    h->have_trees = false;
+    return MVHDP_OK;
+}
+
+extern "C" int mvhdp_get_vectors_mix(mvhdp_handle h, double* lambda, double* mix)
+{
+    CHECK_H(h);
+    if (lambda) *lambda = h->mix_lambda;
+    if (mix) {
+        if (!h->d_mix) FAIL(h, MVHDP_ERR_STATE, "get_vectors_mix: no mix is set");
+        HIPC(h, hipSetDevice(h->device));
+        HIPC(h, hipStreamSynchronize(h->stream));
+        HIPC(h, hipMemcpy(mix, h->d_mix, (size_t)h->mm.V[0] * h->mm.K * sizeof(double), hipMemcpyDeviceToHost));
+    }
+    return MVHDP_OK;
+}

@@ -992,6 +992,11 @@ extern "C" int mvhdp_group_sweep(mvhdp_group g, uint32_t sweep_idx, uint64_t see
     if ((flags & MVHDP_SWEEP_SEGMENT_APPLY) && (flags & MVHDP_SWEEP_LIVE)) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_sweep: SEGMENT_APPLY excludes LIVE");
     if ((flags & MVHDP_SWEEP_SHARD_BIRTHS) && !(flags & MVHDP_SWEEP_LIVE)) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_sweep: SHARD_BIRTHS goes with LIVE");
     if ((flags & MVHDP_SWEEP_ASYNC_EXCHANGE) && !(flags & MVHDP_SWEEP_LIVE)) GFAIL(g, MVHDP_ERR_INVALID_ARG, "group_sweep: ASYNC_EXCHANGE goes with LIVE (a deferred sweep is the parity contract: every replica must hold the global counts)");
+    // the useVectorsLambda mix: every member carries its own copy (mvhdp_set_vectors_mix per member); the local members must agree
+    for (size_t i = 1; i < g->members.size(); i++)
+        if (g->members[i]->mix_lambda != g->members[0]->mix_lambda) GFAIL(g, MVHDP_ERR_STATE, "group_sweep: the members disagree on the vectors mix (mvhdp_set_vectors_mix on every member, same lambda)");
+    if (!g->members.empty() && g->members[0]->mm.mix && (flags & (MVHDP_SWEEP_ASYNC_EXCHANGE | MVHDP_SWEEP_SHARD_BIRTHS)))
+        GFAIL(g, MVHDP_ERR_UNSUPPORTED, "group_sweep: ASYNC_EXCHANGE / SHARD_BIRTHS with a vectors mix");
     DeviceGuard dg;
     const int n = (int)g->members.size();
     std::vector<mvhdp_sweep_stats> total((size_t)n), st((size_t)n);

@@ -133,7 +133,9 @@ __device__ __forceinline__ void tree_from_leaves(const MvModel& mm, int64_t row,
 // K = 1000: 1.00 -> 0.73 ms) and 4 below (C4 0.196 -> 0.175 ms, C3 0.102 -> 0.097); 1 -- a quarter of the registers -- for a rebuild beside
 // a resident sweep kernel (overlapped live segments): what counts there is how many of its waves fit into the registers the samplers
 // leave, not how long one of them takes (TB = 8 there: C3 live 5.2 -> 5.8 ms).  gpurun_out/r5l, r5m.
-template <int TB>
+// MIX: the flavour that knows the useVectorsLambda mix of view 0 (MvModel::mix; PTM:2673-2678): launched instead of the plain one by every
+// launcher below while a mix is set, so that the plain kernels stay what they were.  inference_leaves ignores the mix (INF:576).
+template <int TB, bool MIX = false>
 __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool inference_leaves, bool write_full, int64_t row_begin, int64_t row_end,
                                                          bool apply_first, unsigned long long* negatives, bool from_mirror, bool only_heavy = false)
 {
@@ -154,6 +156,8 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
         const double beta = mm.beta[m], beta_sum = mm.beta_sum[m], gamma = mm.gamma[m];
         uint16_t* c16 = mm.counts16 + row * K;
         const bool light_src = from_mirror && mm.heavy[row] != MVHDP_ROW_HEAVY;
+        const bool mixed = MIX && m == 0 && !inference_leaves;
+        const double* mixrow = mixed ? mm.mix + row * K : nullptr;        // (view 0 starts at row 0: its row index is the type)
         bool hv = false;
         // Both passes over the row read in batches of TB cells a lane, every load of a batch issued before the first is used: one wave
         // works on one row, so a loop that loads, divides and stores cell by cell pays a cache round trip per iteration -- 20 us a row
@@ -190,12 +194,13 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
         }
         for (int k0 = 0; k0 < K; k0 += WAVE * TB) {
             int cv[TB], nkv[TB];
-            double alv[TB];
+            double alv[TB], mxv[TB];
             bool inact[TB];
 #pragma unroll
             for (int u = 0; u < TB; u++) {
                 const int k = k0 + u * WAVE + lane;
                 const bool in = k < K;
+                mxv[u] = (MIX && mixed && in) ? mixrow[k] : 0.0;
                 cv[u] = in ? (light_src ? (int)c16[k] : cnt[k]) : 0;
                 nkv[u] = in ? nk[k] : 0;
                 alv[u] = (in && !inference_leaves) ? al[k] : 0.0;
@@ -215,6 +220,7 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
                         leaf = 0.0;
                     } else {
                         double p_wt = ((double)c + beta) / ((double)nkv[u] + beta_sum);   // PTM:2676
+                        if (MIX && mixed) p_wt = mxv[u] + mm.oml * p_wt;   // PTM:2673-2674: lambda * (e / S) + (1 - lambda) * the count ratio, unfused
                         leaf = gamma * alv[u] * p_wt;                      // PTM:2678
                     }
                     t[K + k] = leaf;
@@ -230,13 +236,16 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
     }
 }
 
+#define LAUNCH_TREES(TB, ...) do { if (mm.mix) hipLaunchKernelGGL((build_trees_kernel<TB, true>), __VA_ARGS__); \
+                                   else hipLaunchKernelGGL((build_trees_kernel<TB, false>), __VA_ARGS__); } while (0)
+
 hipError_t mvhdp_launch_build_trees(const MvModel& mm, bool inference_leaves, bool write_full, hipStream_t s, bool beside_samplers)
 {
     if (!beside_samplers) return mvhdp_launch_build_trees_rows(mm, inference_leaves, write_full, 0, mm.rowbase[mm.M], false, nullptr, s);
     const int64_t nrows = mm.rowbase[mm.M];
     if (nrows <= 0) return hipSuccess;
     int grid = (int)(nrows < 65536 ? nrows : 65536);
-    hipLaunchKernelGGL(build_trees_kernel<1>, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
+    LAUNCH_TREES(1, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
                        (int64_t)0, nrows, false, (unsigned long long*)nullptr, false);
     return hipGetLastError();
 }
@@ -248,10 +257,10 @@ hipError_t mvhdp_launch_build_trees_rows(const MvModel& mm, bool inference_leave
     if (nrows <= 0) return hipSuccess;
     int grid = (int)(nrows < 65536 ? nrows : 65536);          // (a block per row: a tenth of that many blocks looping over rows is 6 % slower, gpurun_out/r5c)
     if (mm.K > 512)
-        hipLaunchKernelGGL(build_trees_kernel<8>, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
+        LAUNCH_TREES(8, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
                            row_begin, row_end, apply_first, negatives, false);
     else
-        hipLaunchKernelGGL(build_trees_kernel<4>, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
+        LAUNCH_TREES(4, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
                            row_begin, row_end, apply_first, negatives, false);
     return hipGetLastError();
 }
@@ -262,13 +271,13 @@ hipError_t mvhdp_launch_build_trees_from_mirror(const MvModel& mm, bool write_fu
     if (nrows <= 0) return hipSuccess;
     int grid = (int)(nrows < 65536 ? nrows : 65536);
     if (beside_samplers)
-        hipLaunchKernelGGL(build_trees_kernel<1>, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
+        LAUNCH_TREES(1, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
                            (int64_t)0, nrows, false, (unsigned long long*)nullptr, true);
     else if (mm.K > 512)
-        hipLaunchKernelGGL(build_trees_kernel<8>, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
+        LAUNCH_TREES(8, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
                            (int64_t)0, nrows, false, (unsigned long long*)nullptr, true);
     else
-        hipLaunchKernelGGL(build_trees_kernel<4>, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
+        LAUNCH_TREES(4, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
                            (int64_t)0, nrows, false, (unsigned long long*)nullptr, true);
     return hipGetLastError();
 }
@@ -559,7 +568,7 @@ hipError_t mvhdp_launch_live_rows_prepare(const MvModel& mm, bool from_mirror, b
     // the HEAVY words (more than 65534 tokens: a few hundred rows at most) keep a stored tree, built from the 32-bit table where their
     // counts live; the flags are those the pass above has just written (or kept)
     if (with_heavy_trees)
-        hipLaunchKernelGGL(build_trees_kernel<4>, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, false, (int64_t)0, nrows, false,
+        LAUNCH_TREES(4, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, false, (int64_t)0, nrows, false,
                            (unsigned long long*)nullptr, true, true);
     return hipGetLastError();
 }
@@ -696,7 +705,9 @@ size_t mvhdp_sweep_wave_bytes(int M, int S_cap)
     return (b + 15) & ~(size_t)15;
 }
 
-template <bool DEBUG>
+// MIX: the flavour with the useVectorsLambda mix of view 0 (MvModel::mix; WRK:504-507) -- a sweep launches it instead of the plain one
+// while a mix is set (and the sweep is not FROZEN), so that the plain kernel stays what it was.
+template <bool DEBUG, bool MIX = false>
 __global__ __launch_bounds__(256) void sweep_kernel(MvModel mm, SweepLaunch sl)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -875,6 +886,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(MvModel mm, SweepLaunch sl)
                     const double root = bcast_d(root_l, t);
                     const int64_t row = row0 + w;
                     const int32_t* __restrict__ cnt = nwk + row * K;
+                    const double* __restrict__ mixrow = (MIX && m == 0) ? mm.mix + (int64_t)w * K : nullptr;
 
                     // WRK:434-468 decrement the local count; drop the topic from the list when it is gone from all views
                     if (so >= 0) {
@@ -904,6 +916,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(MvModel mm, SweepLaunch sl)
                                     int k = sk[i];
                                     if (k >= 0) {
                                         double p_wt = div_inrange((double)cnt[k] + beta_m, sden[i]);          // WRK:507
+                                        if (MIX && m == 0) p_wt = mixrow[k] + mm.oml * p_wt;                    // WRK:504-505
                                         term = (p_mm * (double)sn[m * S + i] + soth[i]) * p_wt;            // WRK:509
                                     }
                                 }
@@ -918,6 +931,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(MvModel mm, SweepLaunch sl)
                                 double term = 0.0;
                                 if (k >= 0) {
                                     double p_wt = div_inrange((double)cnt[k] + beta_m, sden[i]);
+                                    if (MIX && m == 0) p_wt = mixrow[k] + mm.oml * p_wt;                        // WRK:504-505
                                     term = (p_mm * (double)sn[m * S + i] + soth[i]) * p_wt;
                                 }
                                 scum[i] = term;
@@ -1080,9 +1094,11 @@ __global__ __launch_bounds__(256) void sweep_kernel(MvModel mm, SweepLaunch sl)
 
 hipError_t mvhdp_sweep_set_max_lds(size_t bytes)
 {
-    hipError_t e = hipFuncSetAttribute((const void*)sweep_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-    if (e != hipSuccess) return e;
-    return hipFuncSetAttribute((const void*)sweep_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    for (const void* f : {(const void*)sweep_kernel<false>, (const void*)sweep_kernel<true>, (const void*)sweep_kernel<false, true>, (const void*)sweep_kernel<true, true>}) {
+        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 int mvhdp_sweep_generic_occupancy(bool debug, int block_threads, size_t lds_bytes)
@@ -1102,10 +1118,11 @@ int mvhdp_sweep_generic_occupancy(bool debug, int block_threads, size_t lds_byte
     return b < 1 ? 1 : b;
 }
 
-int mvhdp_sweep_generic_regs(bool debug)
+int mvhdp_sweep_generic_regs(bool debug, bool mix)
 {
     hipFuncAttributes a;
-    const void* f = debug ? (const void*)sweep_kernel<true> : (const void*)sweep_kernel<false>;
+    const void* f = mix ? (debug ? (const void*)sweep_kernel<true, true> : (const void*)sweep_kernel<false, true>)
+                        : (debug ? (const void*)sweep_kernel<true> : (const void*)sweep_kernel<false>);
     if (hipFuncGetAttributes(&a, f) != hipSuccess) return 128;
     return a.numRegs;
 }
@@ -1114,8 +1131,12 @@ hipError_t mvhdp_launch_sweep(const MvModel& mm, const SweepLaunch& sl, int grid
 {
     size_t lds = sl.block_shared_bytes + (size_t)sl.waves_per_block * sl.wave_bytes;
     dim3 block(64 * sl.waves_per_block);
-    if (debug) hipLaunchKernelGGL(sweep_kernel<true>, dim3(grid_blocks), block, lds, s, mm, sl);
-    else       hipLaunchKernelGGL(sweep_kernel<false>, dim3(grid_blocks), block, lds, s, mm, sl);
+    if (mm.mix) {
+        if (debug) hipLaunchKernelGGL((sweep_kernel<true, true>), dim3(grid_blocks), block, lds, s, mm, sl);
+        else       hipLaunchKernelGGL((sweep_kernel<false, true>), dim3(grid_blocks), block, lds, s, mm, sl);
+    }
+    else if (debug) hipLaunchKernelGGL(sweep_kernel<true>, dim3(grid_blocks), block, lds, s, mm, sl);
+    else            hipLaunchKernelGGL(sweep_kernel<false>, dim3(grid_blocks), block, lds, s, mm, sl);
     return hipGetLastError();
 }
 

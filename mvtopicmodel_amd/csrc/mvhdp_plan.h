@@ -34,7 +34,8 @@ enum { PLAN_STREAM_MAIN = 0, PLAN_STREAM_A = 1, PLAN_STREAM_B = 2, PLAN_STREAM_C
 
 // Register counts of the compiled kernels (hipFuncGetAttributes at mvhdp_create; typical values in the CPU tests):
 // [class 0..4][0: plain, 1: walk flavour, 2: debug], [5][0/2]: the generic kernel
-struct PlanRegs { int regs[MVHDP_N_CLASSES][3]; };
+// regs_mix: the same for the flavours compiled with the useVectorsLambda mix ([.][0] unused: a sweep with a mix always takes the walk flavour)
+struct PlanRegs { int regs[MVHDP_N_CLASSES][3]; int regs_mix[MVHDP_N_CLASSES][3]; };
 
 struct PlanIn {
     int K = 0, M = 0;
@@ -50,6 +51,7 @@ struct PlanIn {
     bool trees_current = false;                 // the F+trees (and the 16-bit mirror) match the counts before this call
     bool unassigned = false;                    // some token may still be unassigned (z = -1): row totals can grow during the sweep
     int first_inactive = -1;
+    bool vectors_mix = false;                   // a useVectorsLambda mix is set and this sweep samples with it (not FROZEN): the MIX kernel flavours run
     int num_cus = 256;
     size_t max_lds = 160 * 1024;
     PlanRegs regs{};
@@ -334,7 +336,8 @@ static inline void plan_sweep(const PlanIn& in, const PlanTuning& tu, WalkTuner&
     // (a deferred sweep accepts a segment count too: same integers as one segment, the trees being those of the snapshot)
     // (the live-rows form of a live sweep: decided here, before the segment count and the grids, from what cannot change below -- no
     // entity can reach the generic LDS kernel, whose tree branch reads FTree.tree)
-    bool want_rows = p.live && !p.frozen && !in.debug && tu.live_rows != 0 && !(flags & (MVHDP_SWEEP_REUSE_TREES | MVHDP_SWEEP_GENERIC_KERNEL)) &&
+    // (with a mix: the stored-tree form whatever the tuning says -- the live rows' fp32 tree branch has no mix term)
+    bool want_rows = p.live && !in.vectors_mix && !p.frozen && !in.debug && tu.live_rows != 0 && !(flags & (MVHDP_SWEEP_REUSE_TREES | MVHDP_SWEEP_GENERIC_KERNEL)) &&
                      tu.force_primary != 32 && std::min<int64_t>(in.K, std::max<int64_t>(in.mdt, 1)) <= 1024 && in.mdt <= 65535;
     int nseg = (int)((flags >> 16) & 0xffu);
     // (a truncated HDP needs no more: in the live-rows form topics are born chunk by chunk, SweepLaunch::births -- the stored-tree form and a
@@ -413,7 +416,9 @@ static inline void plan_sweep(const PlanIn& in, const PlanTuning& tu, WalkTuner&
         while (g.wpb > 1 && p.block_shared_bytes + (size_t)g.wpb * g.wave_bytes > in.max_lds) g.wpb >>= 1;
         g.lds = p.block_shared_bytes + (size_t)g.wpb * g.wave_bytes;
         if (g.lds > in.max_lds) return false;
-        const int regs = is_fast ? in.regs.regs[c][in.debug ? 2 : (walk ? 1 : 0)] : in.regs.regs[5][in.debug ? 2 : 0];
+        // (the grids of the mix flavours from THEIR register counts)
+        const int (*rg)[3] = in.vectors_mix ? in.regs.regs_mix : in.regs.regs;
+        const int regs = is_fast ? rg[c][in.debug ? 2 : (walk ? 1 : 0)] : rg[5][in.debug ? 2 : 0];
         const int bpc = plan_blocks_per_cu(regs, 64 * g.wpb, g.lds);
         const int64_t need = (in.D + (int64_t)g.wpb * MVHDP_DOC_BATCH - 1) / ((int64_t)g.wpb * MVHDP_DOC_BATCH);
         // (two segments in flight: one block per CU stays free for the updater's kernels and the next segment's first blocks)
@@ -440,7 +445,8 @@ static inline void plan_sweep(const PlanIn& in, const PlanTuning& tu, WalkTuner&
     // lines to matter (K >= 256: at least 1 KiB a row) the walk flavour runs even when every threshold is 0 -- C5 (K = 1000, tree-branch
     // share 0.44: no view is steered) sweeps in 51.9 ms on the mirror against 64.4 ms on the 32-bit rows.
     const bool mirror_pays = mirror_ok && !p.live && K >= 256;
-    auto walk_of = [&](int c) { const int g = group_of(c); bool w = measure || in.debug || mirror_pays; for (int m = 0; m < M; m++) w = w || theta[g][m] > 0.0; return w ? 1 : 0; };
+    // (a sweep with a mix: always the walk flavour -- the mix is compiled for it only; a threshold of 0 walks every token)
+    auto walk_of = [&](int c) { const int g = group_of(c); bool w = measure || in.debug || mirror_pays || in.vectors_mix; for (int m = 0; m < M; m++) w = w || theta[g][m] > 0.0; return w ? 1 : 0; };
 
     ClassLaunch gen;
     if (!geometry(false, 5, 0, gen)) return fail(MVHDP_ERR_UNSUPPORTED, "per-entity LDS state exceeds 160 KiB (K * modalities too large)");
@@ -537,5 +543,5 @@ static inline void plan_sweep(const PlanIn& in, const PlanTuning& tu, WalkTuner&
                 }
         } else p.coef_lds = false;
     } else p.coef_lds = false;
-    p.walk_cfg = (p.live_rows ? 1 << 20 : 0) + (p.fast ? (1 << p.dominant) : 32) * 2 + (p.route ? 1 : 0) + 64 * nseg + (p.live ? 1 << 16 : 0) + (p.seg_apply ? 1 << 17 : 0) + (p.live16 ? 1 << 18 : 0) + (p.overlap ? 1 << 19 : 0);
+    p.walk_cfg = (in.vectors_mix ? 1 << 21 : 0) + (p.live_rows ? 1 << 20 : 0) + (p.fast ? (1 << p.dominant) : 32) * 2 + (p.route ? 1 : 0) + 64 * nseg + (p.live ? 1 << 16 : 0) + (p.seg_apply ? 1 << 17 : 0) + (p.live16 ? 1 << 18 : 0) + (p.overlap ? 1 << 19 : 0);
 }

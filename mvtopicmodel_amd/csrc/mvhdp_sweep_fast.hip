@@ -64,6 +64,9 @@ size_t mvhdp_sweep_fast_wave_bytes(int M, int S_cap, int rmax)
 #ifndef MVHDP_LB_ROWS
 #define MVHDP_LB_ROWS 7      // the live-rows flavours of the 1- and 2-round variants (four more registers: the token's row)
 #endif
+#ifndef MVHDP_LB_MIX
+#define MVHDP_LB_MIX 6       // the 1- and 2-round MIX flavours (the slots' mix cells: 80 registers instead of 72); 7: C3 5.68 -> 5.84 ms
+#endif
 #ifndef MVHDP_LB8
 #define MVHDP_LB8 1          // 3 waves/SIMD (168 VGPRs) spills 100 B/lane and is 13 % slower on C5 than 2 waves at 199
 #endif
@@ -97,6 +100,8 @@ __device__ __forceinline__ int gather_cell(gptr_t p)
     return (int)*q;
 #endif
 }
+template <typename T>
+__device__ __forceinline__ T gather_mix(gptr_t p) { return *(const __attribute__((address_space(1))) T*)p; }
 #define W_HEAVY 0x40000000                      // bit 30 of a lane's type id: the row is heavy (type ids stay below 2^29: mvhdp_create checks)
 #define W_BIG   0x20000000                      // bit 29: the row's deltas do not fit 16 bits for sure (MVHDP_ROW_BIG or heavy): they go to the 32-bit delta table
 #define W_ROW(w) ((w) & 0x1fffffff)
@@ -286,9 +291,16 @@ __device__ __forceinline__ int row_sample_live(rowq_t q0, bool have_q0, bool in_
 // every other mode stay what they were, register for register.
 // LIVEROWS = 2: the same with the two-batch shortcut of row_sample_live compiled in (rows of the mirror longer than one register batch,
 // K in 513 .. 1024: C5) -- a flavour of its own because its few extra scalars cost the K <= 512 kernels 5 % through their spills (C4: 24.1 -> 25.4 ms)
-template <int RMAX, bool DEBUG, bool WALK, bool NARROW, bool ROOMY = false, int LIVEROWS = 0>
-__global__ __launch_bounds__(256, (RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB4 : (RMAX == 2 ? (ROOMY ? MVHDP_LB2_ROOMY : (LIVEROWS ? MVHDP_LB_ROWS : MVHDP_LB2)) : (RMAX == 1 ? (LIVEROWS ? MVHDP_LB_ROWS : WALK ? MVHDP_LB1W : MVHDP_LB1) : MVHDP_LB16))))) void sweep_fast_kernel(MvModel mm, SweepLaunch sl)
+// MIX (walk flavour only, never with LIVEROWS): the useVectorsLambda mix of view 0 (MvModel::mix; WRK:504-507): in view 0 every slot's
+// mix[w][k] is gathered beside its count cell -- same place in the token loop, same number of tokens ahead, into register buffers of its own
+// -- and p_wt = mix + (1 - lambda) * (n_wk + beta) / (n_k + betaSum); the other views run what they run without it (the view is wave-uniform:
+// a scalar branch).  A flavour of its own so that the kernels of a handle without a mix stay what they were, register for register.  The 1- and
+// 2-round variants are compiled for 6 waves per SIMD (80 registers) instead of 7: each slot brings two registers for its mix value and two for
+// the one in flight (MVHDP_LB_MIX; 7 waves with the spills that takes: the same at C4, 3 % slower at C3, profiles/vectors_mix.md).
+template <int RMAX, bool DEBUG, bool WALK, bool NARROW, bool ROOMY = false, int LIVEROWS = 0, bool MIX = false>
+__global__ __launch_bounds__(256, ((MIX && RMAX <= 2) ? MVHDP_LB_MIX : RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB4 : (RMAX == 2 ? (ROOMY ? MVHDP_LB2_ROOMY : (LIVEROWS ? MVHDP_LB_ROWS : MVHDP_LB2)) : (RMAX == 1 ? (LIVEROWS ? MVHDP_LB_ROWS : WALK ? MVHDP_LB1W : MVHDP_LB1) : MVHDP_LB16))))) void sweep_fast_kernel(MvModel mm, SweepLaunch sl)
 {
+    static_assert(!MIX || (WALK && LIVEROWS == 0 && !ROOMY), "the mix flavours: walk flavour, stored trees");
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef MVHDP_TIMING
     const unsigned long long t_begin0 = __builtin_amdgcn_s_memtime();
@@ -337,6 +349,8 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB
     // fp32 screening of the token loop's decisions (mvhdp_sweep_fast_token.inc): two more registers per slot, so not for the
     // 8- and 16-round variants, which sit at their register limit; the debug flavour reports fp64 masses and decides in fp64
     constexpr bool SCREEN = !DEBUG;
+    typedef typename std::conditional<SCREEN, float, double>::type mixg_t;      // (MIX: the type of the mix cells gathered ahead, see mix_v)
+    constexpr int MIXSH = SCREEN ? 0 : 1;                                       //   ... and the shift that turns a count cell's byte offset into theirs
     int* sn = sk + S;
 #define sn_get(idx) (PACK ? (int)((const unsigned short*)sn)[(idx)] : sn[(idx)])
 #define sn_set(idx, v) do { if (PACK) ((unsigned short*)sn)[(idx)] = (unsigned short)(v); else sn[(idx)] = (v); } while (0)
@@ -518,6 +532,16 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB
             };
             float rden32[RMAX], brden32[RMAX], oth32[RMAX];      // the fp32 forms the screening works with: 1/den, beta/den, oth
             const float beta32 = (float)beta_m, scale32 = (float)scale_m;
+            // the mix: view 0 only (WRK:504 `m == 0`); 1 - lambda as the handle formed it, once; its fp32 rounding is folded into the
+            // screening's two per-slot constants, so that the screening pays one addition per slot for the mix and nothing else
+            const bool mixv = MIX && m == 0;
+            const double oml = MIX ? mm.oml : 1.0;
+            const float oml32 = (float)oml;
+            // what the token loop gathers ahead: with the screening the fp32 copy of the table (a cell at the byte offset of its count cell: half
+            // the lines of a mix row, and half the registers -- a C4 sweep 61.5 -> 45.6 ms, profiles/vectors_mix.md); the debug flavour, which decides
+            // in fp64 alone, the fp64 table itself
+            const char* const mix_v = MIX ? (SCREEN ? (const char*)mm.mix32 : (const char*)mm.mix) : nullptr;
+            const char* const mix64_v = MIX ? (const char*)mm.mix : nullptr;
             const float* const smp_m = mm.coef + (int64_t)M * Kp + (int64_t)m * K;                   // running sums of the smoothing parts coef_k * beta of the view's leaves
             const float smS = LIVEROWS ? uniform_f(smp_m[K - 1]) : 0.0f;                             // S_m: their total
 #pragma unroll
@@ -544,6 +568,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB
                     oth[r] = 0.0; den[r] = 1.0;
                     rden32[r] = __builtin_amdgcn_rcpf((float)dn);
                     brden32[r] = beta32 * rden32[r];
+                    if (MIX && mixv) { rden32[r] *= oml32; brden32[r] *= oml32; }
                     oth32[r] = acc * scale32;
                 } else {
                     if (used) {
@@ -691,6 +716,7 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB
                 // own latency is what counts; one where six waves hide it and registers are what counts.
                 constexpr int NB = (RMAX >= MVHDP_NB2_FROM) ? 2 : 1;
                 int gn[RMAX], gn2[RMAX];
+                mixg_t gm[RMAX], gm2[RMAX];                                  // (MIX, view 0: the slots' mix values, gathered with the counts)
                 // The loop visits the chunk's tokens of known types only, in position order, off a scalar mask: a token of a type
                 // outside the vocabulary (WRK:427-428 skips it) is counted here and never enters the loop -- no path through the loop body
                 // leaves the slot registers untouched, which is what lets the compiler update them in place.
@@ -713,6 +739,11 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB
 #pragma unroll
                         for (int r = 0; r < RMAX; r++) { const int v = gather_cell<int32_t>(c0p + (unsigned int)koff[r]); if (a == 0) gn[r] = v; else gn2[r] = v; }
                     }
+                    if (MIX && mixv) {                                       // (a mix row is K doubles: twice the byte offset of the slot's count cell)
+                        const gptr_t m0p = scalar_row(mix_v, r0, (unsigned int)K * (unsigned int)sizeof(mixg_t));
+#pragma unroll
+                        for (int r = 0; r < RMAX; r++) { const mixg_t v = gather_mix<mixg_t>(m0p + ((unsigned int)koff[r] << MIXSH)); if (a == 0) gm[r] = v; else gm2[r] = v; }
+                    }
                 }
 
                 while (rem) {                                               // WRK:425
@@ -720,17 +751,21 @@ __global__ __launch_bounds__(256, (RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB
                     rem &= ~(1ull << t);
 #define TOK_T t
 #define TOK_G gn
+#define TOK_MG gm
 #include "mvhdp_sweep_fast_token.inc"
 #undef TOK_T
 #undef TOK_G
+#undef TOK_MG
                     if (NB == 2 && rem) {
                         const int t1 = (int)__builtin_ctzll(rem);
                         rem &= ~(1ull << t1);
 #define TOK_T t1
 #define TOK_G gn2
+#define TOK_MG gm2
 #include "mvhdp_sweep_fast_token.inc"
 #undef TOK_T
 #undef TOK_G
+#undef TOK_MG
                     }
                 }
 
@@ -877,6 +912,14 @@ static bool roomy_build(int rmax, int K) { return rmax == 2 && K >= 512; }
 // build, which exists for K >= 512 only, is always that flavour: the shortcut checks the batch count at run time as well)
 static bool two_batch_rows(int K) { return K > 512 && K <= 1024; }
 
+// the mix flavours (MvModel::mix set): always the walk flavour (a threshold of 0 walks every token), no ROOMY build of their own
+template <int RMAX>
+static const void* fast_kernel_ptr_mix(bool debug, bool narrow)
+{
+    if (debug) return (const void*)sweep_fast_kernel<RMAX, true, true, false, false, 0, true>;
+    return narrow ? (const void*)sweep_fast_kernel<RMAX, false, true, true, false, 0, true> : (const void*)sweep_fast_kernel<RMAX, false, true, false, false, 0, true>;
+}
+
 template <int RMAX>
 static const void* fast_kernel_ptr(bool debug, bool walk, bool narrow, int K = 0, bool live_rows = false)
 {
@@ -900,6 +943,17 @@ static hipError_t launch_fast(const MvModel& mm, const SweepLaunch& sl, int grid
     dim3 block(64 * sl.waves_per_block);
     const bool narrow = sl.narrow && sl.walk && !debug;
     const bool rows = sl.live_rows && sl.walk && !debug;
+    if (mm.mix) {
+        if (rows || !sl.walk) return hipErrorInvalidValue;                 // (the plan gives a sweep with a mix stored trees and the walk flavour)
+        if (lds > 65536) {
+            hipError_t e = hipFuncSetAttribute(fast_kernel_ptr_mix<RMAX>(debug, narrow), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess) return e;
+        }
+        if (debug)       hipLaunchKernelGGL((sweep_fast_kernel<RMAX, true, true, false, false, 0, true>), dim3(grid_blocks), block, lds, s, mm, sl);
+        else if (narrow) hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, true, false, 0, true>), dim3(grid_blocks), block, lds, s, mm, sl);
+        else             hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, false, false, 0, true>), dim3(grid_blocks), block, lds, s, mm, sl);
+        return hipGetLastError();
+    }
     if (lds > 65536) {
         hipError_t e = hipFuncSetAttribute(fast_kernel_ptr<RMAX>(debug, sl.walk != 0, narrow, mm.K, rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
@@ -974,21 +1028,22 @@ int mvhdp_sweep_fast_occupancy(int rmax, bool debug, bool walk, int block_thread
 }
 
 template <int RMAX>
-static int regs_fast(int flavour)
+static int regs_fast(int flavour, bool mix)
 {
     hipFuncAttributes a;
-    if (hipFuncGetAttributes(&a, fast_kernel_ptr<RMAX>(flavour == 2, flavour >= 1, false)) != hipSuccess) return 128;
+    const void* f = mix ? fast_kernel_ptr_mix<RMAX>(flavour == 2, false) : fast_kernel_ptr<RMAX>(flavour == 2, flavour >= 1, false);
+    if (hipFuncGetAttributes(&a, f) != hipSuccess) return 128;
     return a.numRegs;
 }
 
-int mvhdp_sweep_kernel_regs(int cls, int flavour)
+int mvhdp_sweep_kernel_regs(int cls, int flavour, bool mix)
 {
     switch (cls) {
-    case 0: return regs_fast<1>(flavour);
-    case 1: return regs_fast<2>(flavour);
-    case 2: return regs_fast<4>(flavour);
-    case 3: return regs_fast<8>(flavour);
-    case 4: return regs_fast<16>(flavour);
-    default: return mvhdp_sweep_generic_regs(flavour == 2);
+    case 0: return regs_fast<1>(flavour, mix);
+    case 1: return regs_fast<2>(flavour, mix);
+    case 2: return regs_fast<4>(flavour, mix);
+    case 3: return regs_fast<8>(flavour, mix);
+    case 4: return regs_fast<16>(flavour, mix);
+    default: return mvhdp_sweep_generic_regs(flavour == 2, mix);
     }
 }

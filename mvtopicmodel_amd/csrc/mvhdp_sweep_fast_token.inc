@@ -6,6 +6,9 @@
                     int g[RMAX];
 #pragma unroll
                     for (int r = 0; r < RMAX; r++) g[r] = TOK_G[r];
+                    mixg_t mg[RMAX];                                         // (MIX, view 0: mix[w][k] of the slots, gathered with the counts; else unused)
+#pragma unroll
+                    for (int r = 0; r < RMAX; r++) mg[r] = (MIX && mixv) ? TOK_MG[r] : (mixg_t)0;
                     // live-rows form: a token that may reach the tree branch (its u1 reaches the view's threshold) loads its word's row NOW, ahead of
                     // the next token's gather: vmcnt counts in order, and a load issued once the branch is known would wait behind that gather
                     const int wfull_t = LIVEROWS ? bcast_i(w_l, TOK_T) : 0;
@@ -38,6 +41,11 @@
                             const gptr_t cnp = scalar_row(nwk_v, (unsigned int)W_ROW(wn), (unsigned int)K * 4u);
 #pragma unroll
                             for (int r = 0; r < RMAX; r++) TOK_G[r] = gather_cell<int32_t>(cnp + (unsigned int)koff[r]);
+                        }
+                        if (MIX && mixv) {                                   // view 0 with a mix: RMAX more loads, on every path through here like the counts'
+                            const gptr_t mnp = scalar_row(mix_v, (unsigned int)W_ROW(wn), (unsigned int)K * (unsigned int)sizeof(mixg_t));
+#pragma unroll
+                            for (int r = 0; r < RMAX; r++) TOK_MG[r] = gather_mix<mixg_t>(mnp + ((unsigned int)koff[r] << MIXSH));
                         }
                     }
                     const int w = W_ROW(bcast_i(w_l, TOK_T));                // (a known type: the loop's mask holds no other)
@@ -75,6 +83,12 @@
                     // which the reference's fp64 sequence matches to 2^-45.  When any comparison is closer than that (2 to 5 tokens in 10 000 on
                     // C4 and C5: profiles/r03_screened_count.txt) the fp64 path below decides, itself certified against the sequential sum:
                     // the decisions -- hence every integer -- are the reference's, by construction.
+                    // MIX, view 0: p_wt = mix + (1 - lambda) * (g + beta) / den.  (1 - lambda), rounded to fp32, is folded into the two per-slot constants
+                    // -- each gains that rounding and the product's, 2 more on the longest chain: 7 for beta/den, 8 with the fused step --, then
+                    // the slot's mix value rounded to fp32 (1) and its addition (1): a term carries at most M + 16 roundings, a comparison below
+                    // 60 in all for M <= 8, RMAX <= 16 -- still under the 128 of tol, which stays as it is.  Every term stays non-negative
+                    // (0 <= lambda <= 1, mix >= 0 and finite: mvhdp_set_vectors_mix refuses anything else), which the certified scan below rests on.
+                    // The screening reads an fp32 copy of the table (MvModel::mix32, 80 MB more at C4: half the lines of a mix row per view-0 token).
                     double term[RMAX] = {};             // (fp64 terms: formed by the fp64 path only; read again by the debug trace)
                     bool need64 = DEBUG || exact_only || !SCREEN;
                     if (SCREEN && !need64) {
@@ -82,7 +96,8 @@
                         float t32[RMAX], c32v[RMAX];
 #pragma unroll
                         for (int r = 0; r < RMAX; r++) {
-                            const float pw = __builtin_fmaf((float)g[r], rden32[r], brden32[r]);    // WRK:507: (g + beta) / den
+                            float pw = __builtin_fmaf((float)g[r], rden32[r], brden32[r]);          // WRK:507: (g + beta) / den  (MIX, view 0: times 1 - lambda)
+                            if (MIX && mixv) pw += (float)mg[r];                                    // WRK:504 (the cell of the fp32 copy)
                             const float a32 = __builtin_fmaf(pmm32, (float)cn[r], oth32[r]);        // WRK:509
                             t32[r] = __builtin_amdgcn_inverse_ballot_w64(live_m[r]) ? a32 * pw : 0.0f;
                         }
@@ -145,6 +160,12 @@
                             }
                         }
                         need64 = close;
+                        // MIX, view 0: the budget above counts roundings relative to the total, which takes fp32's NORMAL range.  Without a mix every
+                        // term carries (g + beta) / den and stays there; at lambda near 1 a term is a32 * (float)mix alone, and a table may hold
+                        // p_emb(w|k) of 1e-40 or 0 under every listed topic: cells, mass and root denormal or flushed, a tolerance of 2^-17 * total
+                        // without meaning.  A total below 2^-100 goes to fp64 (one scalar compare, this flavour only); above it a flushed cell is
+                        // wrong by less than 2^-126 * a32, a32 < 2^21: nothing beside 2^-17 * total.
+                        if (MIX && mixv) need64 = need64 || !(totalf >= 0x1.0p-100f);
                     }
                     if (need64) {
 #ifdef MVHDP_COUNT_SCREENED                                  /* measurement build: tokens the screening handed to fp64, reported with the exact fallbacks */
@@ -155,6 +176,16 @@
                     // one DPP prefix scan of the lane totals (certified below); the reference's sequential
                     // left-to-right sum only when a comparison is too close to call.
                     double cum[RMAX];
+                    // MIX, view 0, under the screening: the loop carries the fp32 cells; the rare token that comes here reads its slots' fp64 cells now
+                    // (the wait for them is a wait for everything in flight: in order -- once in a few thousand tokens)
+                    double mg64[RMAX];
+#pragma unroll
+                    for (int r = 0; r < RMAX; r++) mg64[r] = (double)mg[r];
+                    if (MIX && SCREEN && mixv) {
+                        const gptr_t m64p = scalar_row(mix64_v, (unsigned int)w, (unsigned int)K * 8u);
+#pragma unroll
+                        for (int r = 0; r < RMAX; r++) mg64[r] = gather_mix<double>(m64p + ((unsigned int)koff[r] << 1));
+                    }
 #pragma unroll
                     for (int r = 0; r < RMAX; r++) {
                         term[r] = 0.0;
@@ -162,6 +193,7 @@
                             double o = oth[r], dn = den[r];
                             if (SCREEN) slot_consts(r, o, dn);
                             double p_wt = div_inrange((double)g[r] + beta_m, dn);          // WRK:507
+                            if (MIX && mixv) p_wt = mg64[r] + oml * p_wt;                  // WRK:504-505 (unfused: -ffp-contract=off)
                             term[r] = (p_mm * (double)cn[r] + o) * p_wt;                   // WRK:509
                         }
                     }

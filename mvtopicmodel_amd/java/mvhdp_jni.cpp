@@ -881,4 +881,32 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbRelease(JN
 { ShardPin pin_(p); Shard* s = pin_.s; if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
   int rc = mvhdp_emb_release(s->h); if (rc) { throw_rt(env, s->h, rc, "mvhdp_emb_release"); return; } s->embR = 0; s->embC = 0; s->embK = 0; }
 
+// useVectorsLambda (PTM:1199-1207): lambda = 0 switches the mix off; expDot [K*V_0] / sumExp [K] in the reference's layout, or both null:
+// the handle's own softmax table as the last embSoftmax left it
+JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetVectorsMix(JNIEnv* env, jclass, jlong p, jdouble lambda, jdoubleArray expDot, jdoubleArray sumExp)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    if ((expDot == nullptr) != (sumExp == nullptr)) { throw_msg(env, "java/lang/IllegalArgumentException", "setVectorsMix: expDot and sumExp go together"); return; }
+    if ((expDot && bad_len(env, expDot, (jlong)s->K * s->V[0], "setVectorsMix expDot [K*V_0]")) || (sumExp && bad_len(env, sumExp, s->K, "setVectorsMix sumExp"))) return;
+    Doubles e(env, expDot, JNI_ABORT), m(env, sumExp, JNI_ABORT);
+    if (e.failed() || m.failed()) return;
+    int rc = mvhdp_set_vectors_mix(s->h, lambda, e.p, m.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_set_vectors_mix");
+}
+
+// returns lambda (0: off); mix [V_0*K] or null: lambda * (e / S) as the device holds it
+JNIEXPORT jdouble JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetVectorsMix(JNIEnv* env, jclass, jlong p, jdoubleArray mix)
+{
+    ShardPin pin_(p); Shard* s = pin_.s;
+    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return 0.0; }
+    if (mix && bad_len(env, mix, (jlong)s->V[0] * s->K, "getVectorsMix mix [V_0*K]")) return 0.0;
+    Doubles t(env, mix, 0);
+    if (t.failed()) return 0.0;
+    double lambda = 0.0;
+    int rc = mvhdp_get_vectors_mix(s->h, &lambda, t.p);
+    if (rc) throw_rt(env, s->h, rc, "mvhdp_get_vectors_mix");
+    return lambda;
+}
+
 }  // extern "C"

@@ -141,6 +141,13 @@ public final class NativeSampler implements AutoCloseable {
     /** findClosest TWE:485-540: the n (1..64) closest words and topics by cosine, IDSorter order. */
     public void embNearest(double[] query, int n, int[] words, double[] wordSims, int[] topics, double[] topicSims) { nEmbNearest(handle, query, n, words, wordSims, topics, topicSims); }
     public void embRelease() { nEmbRelease(handle); }
+    /**
+     * useVectorsLambda (WRK:504-507, PTM:2673-2678): lambda = 0 switches the mix off, 0 &lt; lambda &lt;= 1 on.  expDotFlat [K*V_0] / sumExp [K] are
+     * expDotProductValues / sumExpValues; both null: the table the last embSoftmax left on the device.  Invalidates the F+trees.
+     */
+    public void setVectorsMix(double lambda, double[] expDotFlat, double[] sumExp) { nSetVectorsMix(handle, lambda, expDotFlat, sumExp); }
+    /** lambda (0: off); mixFlat [V_0*K] or null receives lambda * (e / S) as the device holds it. */
+    public double getVectorsMix(double[] mixFlat) { return nGetVectorsMix(handle, mixFlat); }
 
     /**
      * The sweep's own choices (mvhdp_tuning): none of them changes a result.  learntWalkStep / treeBranchShare are what the
@@ -340,4 +347,6 @@ public final class NativeSampler implements AutoCloseable {
     private static native void nEmbSoftmax(long h, boolean resetSums, double[] expDot, double[] sumExp);
     private static native void nEmbNearest(long h, double[] query, int n, int[] words, double[] wordSims, int[] topics, double[] topicSims);
     private static native void nEmbRelease(long h);
+    private static native void nSetVectorsMix(long h, double lambda, double[] expDot, double[] sumExp);
+    private static native double nGetVectorsMix(long h, double[] mix);
 }

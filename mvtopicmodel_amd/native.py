@@ -474,6 +474,30 @@ class NativeSampler:
         self._ck(self.L.mvhdp_emb_release(self.h))
         self._emb_shape = None
 
+    # -- useVectorsLambda: the embeddings' p(w|t) mixed into the view-0 sampler (WRK:504-507, PTM:2673-2678) ------
+    def set_vectors_mix(self, lam, exp_dot=None, sum_exp=None):
+        """lam = 0: off.  0 < lam <= 1: on, with the host's expDotProductValues [K][V_0] / sumExpValues [K], or (both None) the
+        handle's own softmax table as the last emb_softmax left it.  Invalidates the F+trees."""
+        if (exp_dot is None) != (sum_exp is None):
+            raise ValueError("exp_dot and sum_exp go together")
+        e = s = None
+        if exp_dot is not None:
+            e = np.ascontiguousarray(exp_dot, dtype=np.float64)
+            s = np.ascontiguousarray(sum_exp, dtype=np.float64)
+            if e.shape != (self.K, self.V[0]) or s.shape != (self.K,):
+                raise ValueError(f"exp_dot must be [{self.K}][{self.V[0]}] and sum_exp [{self.K}]")
+        self._ck(self.L.mvhdp_set_vectors_mix(self.h, float(lam), _ptr(e), _ptr(s)))
+
+    def get_vectors_mix(self, want_table=True):
+        """(lambda, the device's table lambda * (e / S) as [V_0][K], or None when the mix is off or want_table is False)."""
+        lam = C.c_double()
+        self._ck(self.L.mvhdp_get_vectors_mix(self.h, C.byref(lam), None))
+        if lam.value == 0.0 or not want_table:
+            return lam.value, None
+        t = np.empty((self.V[0], self.K), dtype=np.float64)
+        self._ck(self.L.mvhdp_get_vectors_mix(self.h, None, _ptr(t)))
+        return lam.value, t
+
     # -- the hot path ---------------------------------------------------------
     def sweep(self, sweep_idx, seed, flags=0, p=None, want_dbg=False, trace=None) -> SweepStats:
         st = SweepStatsC()
@@ -688,6 +712,10 @@ class NativeGroup:
     def set_hyper(self, hy):
         for s in self.members:
             s.set_hyper(hy)                     # (keeps the arrays alive per member; same effect as mvhdp_group_set_hyper)
+
+    def set_vectors_mix(self, lam, exp_dot=None, sum_exp=None):
+        for s in self.members:                  # (every member carries its own copy of the table; the group checks that they agree)
+            s.set_vectors_mix(lam, exp_dot, sum_exp)
 
     def model_log_likelihood(self):
         M = self.members[0].M
