@@ -199,8 +199,14 @@ typedef struct {
 typedef enum {
     MVHDP_BUF_COUNTS = 0,  /* int32 [sumV*K + M*K]: n_wk rows of every view, then n_k */
     MVHDP_BUF_DELTA  = 1,  /* int32 [sumV*K + M*K]: the last sweep's deltas, same layout */
-    MVHDP_BUF_BIRTH_KEYS = 2  /* int64 [K]: written by every NO_APPLY sweep: keys[k] = the first delta (MVHDP_ACT_KEY) that reached topic k
+    MVHDP_BUF_BIRTH_KEYS = 2, /* int64 [K]: written by every NO_APPLY sweep: keys[k] = the first delta (MVHDP_ACT_KEY) that reached topic k
                                  if k was inactive and was reached, MVHDP_ACT_KEY_NONE otherwise (see MVHDP_SWEEP_SHARD_BIRTHS) */
+    /* read-only views for tests and diagnostics, not for collectives: what the last tree build left (deferred sweeps gather from them).
+       UNSTABLE: the packed layout and the class bits are internals of the sweep kernels and may change with any release; a host must not
+       build on them. */
+    MVHDP_BUF_COUNTS12 = 3,   /* bytes [sumV][128 * ceil(K / 85)]: the 12-bit image of n_wk, a row valid where its class says so (DESIGN.md
+                                 section 3); MVHDP_ERR_INVALID_ARG on a handle that keeps none (short rows, a view of 2^28 types or more) */
+    MVHDP_BUF_ROW_CLASS = 4   /* bytes [sumV]: bits 1:0 the row's weight class (0 small, 1 heavy, 2 big), bit 2: the row is in the 12-bit image */
 } mvhdp_buffer;
 
 /* ---- lifetime ---- */
@@ -475,7 +481,7 @@ int mvhdp_get_view_weights(mvhdp_handle h, double* p /*[D][M][M]*/);
  * (mvhdp_get_tuning) and hand them to another -- a document shard, a resumed chain -- and it does not search again. */
 typedef struct {
     int32_t force_primary;                       /* 0: the library chooses; 1,2,4,8,16: primary register variant; 32: generic kernel only */
-    int32_t narrow;                              /* -1: 16-bit mirror of n_wk wherever legal (default); 0: never; 1: for the 1-round kernel variant only */
+    int32_t narrow;                              /* -1: 16-bit mirror of n_wk wherever legal (default); 0: never; 1: for the 1-round kernel variant only; 2 (mvhdp_plan_probe only): as -1, and the probe plans for a handle that keeps the 12-bit image (views below 2^28 types); mvhdp_set_tuning takes 2 as -1: whether a handle keeps the image is decided at mvhdp_create */
     int32_t walk_fixed;                          /* 1: walk_theta[] as given, no search */
     int32_t single_stream;                       /* 1: all class kernels on the handle's stream (diagnostics) */
     int32_t live16;                              /* MVHDP_SWEEP_LIVE keeps the light n_wk rows current in the 16-bit mirror (half-width gathers): -1 where K >= 256 (default), 0 never, 1 always */

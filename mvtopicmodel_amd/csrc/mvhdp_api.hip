@@ -57,6 +57,7 @@ static void read_environment(mvhdp_ctx* h)
     if (const char* f = getenv("MVHDP_LIVE_ROWS_SEGMENTS")) h->tu.live_rows_segments = std::max(1, std::min(255, atoi(f)));
     if (const char* f = getenv("MVHDP_WIDEST_ON_MAIN")) h->tu.widest_on_main = atoi(f) != 0;
     if (const char* f = getenv("MVHDP_NARROW_WIDE")) h->tu.narrow_wide = atoi(f) != 0;
+    if (const char* f = getenv("MVHDP_SLIM")) h->tu.slim = std::max(0, std::min(2, atoi(f)));    // 0: no 12-bit image of n_wk (A/B runs); 2: wherever its rows have fewer lines than the mirror's
     if (const char* f = getenv("MVHDP_LIVE_TREE_EVERY")) h->live_tree_every = std::max(1, atoi(f));   // (diagnostics: a live sweep rebuilds its trees at every n-th segment border only)
     if (const char* f = getenv("MVHDP_GATE_PCT")) { const int v = atoi(f); if (v >= 5 && v <= 95) h->gate_pct = v; }   // how far through a live segment the next one is prepared
     if (const char* f = getenv("MVHDP_FOUR_ROUND_ON_C")) h->tu.four_round_on_c = atoi(f);         // -1 by its token share (default), 0 / 1
@@ -176,6 +177,15 @@ extern "C" int mvhdp_create(const mvhdp_config* cfg, mvhdp_handle* out)
     for (int c = 0; c < MVHDP_N_CLASSES; c++)
         for (int f = 0; f < 3; f++) { h->regs.regs[c][f] = mvhdp_sweep_kernel_regs(c, f); h->regs.regs_mix[c][f] = mvhdp_sweep_kernel_regs(c, f ? f : 1, true); }
     read_environment(h);
+    {
+        // the 12-bit image of n_wk (mvhdp_slim.h): only where a plan can use it (38 MB at C4)
+        int vmax = 0;
+        for (int m = 0; m < M; m++) vmax = std::max(vmax, (int)cfg->num_types[m]);
+        if (plan_slim_table(K, vmax, h->tu.slim)) {
+            CREATE_HIP(hipMalloc(&mm.counts12, (size_t)nrows * mvhdp_slim_row_bytes(K)));
+            CREATE_HIP(hipMemset(mm.counts12, 0, (size_t)nrows * mvhdp_slim_row_bytes(K)));
+        }
+    }
     mm.alpha = h->d_alpha;
     mm.inactive = h->d_inactive;
     h->h_alpha.assign((size_t)M * (K + 1), 0.0);
@@ -195,7 +205,7 @@ static void release_device_resources(mvhdp_ctx* h)
     if (h->stream) hipStreamSynchronize(h->stream);
     auto fr = [](auto*& p) { if (p) { hipFree((void*)p); p = nullptr; } };
     for (int m = 0; m < MVHDP_MAXM; m++) { fr(h->d_doc_off[m]); fr(h->d_tok[m]); fr(h->d_z[m]); fr(h->d_carry[m]); fr(h->d_present[m]); }
-    fr(h->mm.counts); fr(h->mm.delta16); fr(h->mm.counts16); fr(h->mm.heavy); fr(h->mm.delta); fr(h->mm.trees); fr(h->mm.root); fr(h->mm.coef); fr(h->mm.mass0); fr(h->d_births); fr(h->d_birth_keys); fr(h->d_birth_table); fr(h->mm.dtab); fr(h->mm.p);
+    fr(h->mm.counts); fr(h->mm.delta16); fr(h->mm.counts16); fr(h->mm.counts12); fr(h->mm.heavy); fr(h->mm.delta); fr(h->mm.trees); fr(h->mm.root); fr(h->mm.coef); fr(h->mm.mass0); fr(h->d_births); fr(h->d_birth_keys); fr(h->d_birth_table); fr(h->mm.dtab); fr(h->mm.p);
     fr(h->d_alpha); fr(h->d_inactive); fr(h->d_ctl);
     fr(h->d_mix); fr(h->d_mix32); h->mm.mix = nullptr; h->mm.mix32 = nullptr; h->mix_lambda = 0.0;
     mvhdp_emb_free(h);
@@ -835,6 +845,9 @@ static void fill_plan_in(mvhdp_ctx* h, uint32_t flags, bool debug, bool batch, P
     in.vectors_mix = mm.mix != nullptr && !(flags & MVHDP_SWEEP_FROZEN);      // (the inferencer's worker has lambda = 0: INF:251-252)
     in.num_cus = h->num_cus; in.max_lds = h->max_lds;
     in.regs = h->regs;
+    in.slim_table = mm.counts12 != nullptr;
+    in.max_types = 0;
+    for (int m = 0; m < mm.M; m++) in.max_types = std::max(in.max_types, (int)mm.V[m]);
 }
 
 static int alloc_debug(mvhdp_ctx* h, const mvhdp_debug* dbg, DebugBufs& db)
@@ -1428,7 +1441,7 @@ static void debug_print_plan(const mvhdp_ctx* h, const SweepPlan& p, uint32_t sw
     for (int c = 0; c < MVHDP_N_CLASSES; c++)
         if (p.cls[c].used)
             fprintf(stderr, " [class %d %s grid %d wpb %d lds %zu stream %d%s%s theta0 %.2f ents %llu]", c, p.cls[c].fast ? "fast" : "generic", p.cls[c].grid, p.cls[c].wpb, p.cls[c].lds,
-                    p.cls[c].stream, p.cls[c].walk ? " walk" : "", p.cls[c].narrow ? " narrow" : "", p.cls[c].theta[0], (unsigned long long)h->last_ent[c]);
+                    p.cls[c].stream, p.cls[c].walk ? " walk" : "", p.cls[c].narrow == 2 ? " slim" : p.cls[c].narrow ? " narrow" : "", p.cls[c].theta[0], (unsigned long long)h->last_ent[c]);
     fprintf(stderr, "\n");
 }
 
@@ -1715,6 +1728,7 @@ extern "C" int mvhdp_plan_probe(const mvhdp_plan_input* pi, const mvhdp_tuning* 
     // (a probe that names no register counts for the mix flavours sizes them as the plain ones)
     for (int c = 0; c < MVHDP_N_CLASSES; c++) for (int f = 0; f < 3; f++) in.regs.regs_mix[c][f] = pi->kernel_registers_mix[c][f] > 0 ? pi->kernel_registers_mix[c][f] : pi->kernel_registers[c][f];
     in.vectors_mix = pi->vectors_mix != 0 && !(pi->flags & MVHDP_SWEEP_FROZEN);
+    in.slim_table = t && t->narrow == 2;                  // (a probe whose tuning says narrow = 2: a handle that keeps the 12-bit image; views below 2^28 types)
     PlanTuning tu;
     WalkTuner wt;
     wt.init_defaults(in.K);
@@ -1781,7 +1795,9 @@ extern "C" int mvhdp_device_buffer(mvhdp_handle h, mvhdp_buffer which, void** de
     if (which == MVHDP_BUF_COUNTS) { *dev_ptr = h->mm.counts; *bytes = b; return MVHDP_OK; }
     if (which == MVHDP_BUF_DELTA) { *dev_ptr = h->mm.delta; *bytes = b; return MVHDP_OK; }
     if (which == MVHDP_BUF_BIRTH_KEYS) { *dev_ptr = h->d_birth_table; *bytes = (size_t)h->mm.K * sizeof(long long); return MVHDP_OK; }
-    FAIL(h, MVHDP_ERR_INVALID_ARG, "device_buffer: unknown buffer");
+    if (which == MVHDP_BUF_COUNTS12 && h->mm.counts12) { *dev_ptr = h->mm.counts12; *bytes = (size_t)h->mm.rowbase[h->mm.M] * mvhdp_slim_row_bytes(h->mm.K); return MVHDP_OK; }
+    if (which == MVHDP_BUF_ROW_CLASS) { *dev_ptr = h->mm.heavy; *bytes = (size_t)h->mm.rowbase[h->mm.M]; return MVHDP_OK; }
+    FAIL(h, MVHDP_ERR_INVALID_ARG, "device_buffer: unknown buffer (or a handle without that table)");
 }
 
 extern "C" int mvhdp_counts_written(mvhdp_handle h)

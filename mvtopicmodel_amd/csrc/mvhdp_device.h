@@ -73,6 +73,10 @@ struct MvModel {
     const float* mix32;                // [V_0][K] the same values rounded to fp32: what the fp32 screening of the register kernels gathers (a cell at
                                        //   the byte offset of its count cell, half the lines of a mix row); the fp64 table serves the rare token that goes to fp64
     double oml;
+    // The 12-bit image of n_wk (mvhdp_slim.h: line-aligned rows of ceil(K / 85) lines, 85 cells a line), or nullptr: written with the mirror,
+    // row by row, for every row whose cells are all at most 4095 at that moment (MVHDP_ROW_SLIM in MvModel::heavy); read by the deferred
+    // NARROW = 2 kernel flavour.  Nothing updates it in place: the passes that add deltas into the mirror, and live sweeps, never use it.
+    uint8_t* counts12;
 };
 
 // SweepLaunch::flags, internal: a live sweep waits for its chunk-end atomics and invalidates the CU's L1 before it goes on (with one
@@ -80,8 +84,13 @@ struct MvModel {
 #define MVHDP_SL_STRICT_LIVE 0x8000u
 // MvModel::heavy values: 0 = light and small, MVHDP_ROW_HEAVY = more than 65534 tokens (not in the mirror), MVHDP_ROW_BIG = light, but
 // more than 32767 tokens (mirror yes, 16-bit deltas no).  Written by build_trees_kernel from the row's sum.
+// MVHDP_ROW_SLIM: one more BIT beside that value -- every cell of the row was at most 4095 when its mirror was last written, and the row
+// is in the 12-bit image (MvModel::counts12).  By the row's largest CELL, not its sum: a diffuse frequent word is big (or heavy) and slim at once.
+// Whoever asks for the weight class reads it through MVHDP_ROW_CLASS.
 #define MVHDP_ROW_HEAVY 1
 #define MVHDP_ROW_BIG 2
+#define MVHDP_ROW_SLIM 4
+#define MVHDP_ROW_CLASS(h) ((h) & 3)
 
 struct SweepLaunch {
     uint32_t sweep_idx;
@@ -115,7 +124,7 @@ struct SweepLaunch {
     // arithmetic, same result.  0 = walk every token.
     double walk_theta[MVHDP_MAXM];
     int32_t walk;                      // 1: launch the kernel flavour that knows about thresholds (and counts the per-view statistics)
-    int32_t narrow;                    // 1: the flavour that gathers n_wk from the 16-bit mirror
+    int32_t narrow;                    // 1: the flavour that gathers n_wk from the 16-bit mirror; 2 (deferred sweeps): slim rows from the 12-bit image, the others as with 1
     int32_t delta16;                   // 1 (deferred sweep, narrow flavour): the n_wk deltas of rows without MVHDP_ROW_BIG go to MvModel::delta16
     int32_t live16;                    // 1 (MVHDP_SWEEP_LIVE with narrow): the sweep's n_wk atomics of LIGHT rows go to the mirror itself, which is then the
                                        //   authoritative copy of those rows until the next tree build / widen pass; heavy rows: the 32-bit table as ever

@@ -124,7 +124,7 @@ __global__ __launch_bounds__(256) void pack_rows_kernel(const int32_t* __restric
     for (int64_t row = r0 + (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); row < r1; row += wstride) {
         const int32_t* d = delta + row * K;
         int32_t* o = xp + woff[row];
-        if (heavy[row] == 0) {
+        if (MVHDP_ROW_CLASS(heavy[row]) == 0) {
             const int nw = (K + 1) >> 1;
             for (int j = lane; j < nw; j += 64) { const int a = d[2 * j], b = (2 * j + 1 < K) ? d[2 * j + 1] : 0; o[j] = a + b * 65536; }
         } else for (int k = lane; k < K; k += 64) o[k] = d[k];
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void unpack_rows_kernel(int32_t* __restrict__ 
     for (int64_t row = r0 + (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); row < r1; row += wstride) {
         int32_t* d = delta + row * K;
         const int32_t* o = xp + woff[row];
-        if (heavy[row] == 0) {
+        if (MVHDP_ROW_CLASS(heavy[row]) == 0) {
             const int nw = (K + 1) >> 1;
             for (int j = lane; j < nw; j += 64) {
                 const int w = o[j];
@@ -551,6 +551,7 @@ static int pack_prepare(mvhdp_group_ctx* g)
     std::vector<uint8_t> cls((size_t)rows);
     GHIP(g, hipSetDevice(L0->device));
     GHIP(g, hipMemcpy(cls.data(), L0->mm.heavy, (size_t)rows, hipMemcpyDeviceToHost));
+    for (auto& c : cls) c = (uint8_t)MVHDP_ROW_CLASS(c);                      // (the weight class alone: MVHDP_ROW_SLIM moves from sweep to sweep)
     g->woff.assign((size_t)rows + 1, 0);
     for (int64_t r = 0; r < rows; r++) g->woff[(size_t)r + 1] = g->woff[(size_t)r] + (cls[(size_t)r] == 0 ? (K + 1) / 2 : K);
     if (g->d_woff.empty()) { g->d_woff.assign(g->leaders.size(), nullptr); g->d_cls.assign(g->leaders.size(), nullptr); g->xpack.assign(g->leaders.size(), nullptr); }

@@ -13,6 +13,7 @@
 // Build with -ffp-contract=off: every fp64 expression below is evaluated in the
 // reference's order with one rounding per operation (Java never fuses a*b+c).
 #include "mvhdp_device.h"
+#include "mvhdp_slim.h"
 #include "../../include/mvhdp.h"
 
 #include "mvhdp_wave.h"
@@ -146,7 +147,7 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
     int neg = 0;
     __builtin_amdgcn_s_setprio(3);                 // (a live sweep rebuilds the next segment's trees beside the current segment's samplers)
     for (int64_t row = row_begin + blockIdx.x; row < row_end; row += gridDim.x) {
-        if (only_heavy && mm.heavy[row] != MVHDP_ROW_HEAVY) continue;   // (live-rows form: every other word samples its tree branch from its live row)
+        if (only_heavy && MVHDP_ROW_CLASS(mm.heavy[row]) != MVHDP_ROW_HEAVY) continue;   // (live-rows form: every other word samples its tree branch from its live row)
         int m = 0;
         while (m + 1 < mm.M && row >= mm.rowbase[m + 1]) m++;
         int32_t* cnt = mm.counts + row * K;
@@ -155,16 +156,20 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
         const double* al = mm.alpha + (int64_t)m * (K + 1);
         const double beta = mm.beta[m], beta_sum = mm.beta_sum[m], gamma = mm.gamma[m];
         uint16_t* c16 = mm.counts16 + row * K;
-        const bool light_src = from_mirror && mm.heavy[row] != MVHDP_ROW_HEAVY;
+        const bool light_src = from_mirror && MVHDP_ROW_CLASS(mm.heavy[row]) != MVHDP_ROW_HEAVY;
         const bool mixed = MIX && m == 0 && !inference_leaves;
         const double* mixrow = mixed ? mm.mix + row * K : nullptr;        // (view 0 starts at row 0: its row index is the type)
-        bool hv = false;
+        bool hv = false, slim = false;
         // Both passes over the row read in batches of TB cells a lane, every load of a batch issued before the first is used: one wave
         // works on one row, so a loop that loads, divides and stores cell by cell pays a cache round trip per iteration -- 20 us a row
         // at K = 400, which is what bounded this kernel (0.19 ms for 60 000 rows with 25 rows in flight per CU; round 4).
         // first pass over the row: the updater's catch-up (apply_first), the row's weight class, the mirror
+        // (from_mirror: MvModel::heavy stays as it is, MVHDP_ROW_SLIM included, and the 12-bit image is not rewritten -- both are STALE from
+        // then on; only a later build with from_mirror false makes them valid again.  Safe because such a build sits inside a live16 sweep,
+        // which never plans narrow = 2 and ends with the trees marked not current: the next deferred sweep rebuilds before it reads either.)
         if (!from_mirror) {
             long long sum = 0;
+            int big = 0;                                                   // the row's largest cell (a negative one counts as too large for any narrow image)
             for (int k0 = 0; k0 < K; k0 += WAVE * TB) {
                 int cv[TB], dv[TB];
 #pragma unroll
@@ -183,14 +188,17 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
                             if (d) { c += d; cnt[k] = c; dl[k] = 0; neg += c < 0; }    // UPD:202-215 logs a negative count; here it is reported
                         }
                         sum += c < 0 ? 70000 : c;                          // (a negative count is an error reported elsewhere: keep the row out of the mirror)
+                        big = max(big, c < 0 ? 70000 : c);
                     }
                 }
             }
 #pragma unroll
-            for (int sft = 32; sft >= 1; sft >>= 1) sum += __shfl_xor(sum, sft, WAVE);
+            for (int sft = 32; sft >= 1; sft >>= 1) { sum += __shfl_xor(sum, sft, WAVE); big = max(big, __shfl_xor(big, sft, WAVE)); }
             hv = sum > 65534;
+            // the 12-bit image takes the row when every cell fits (whatever its sum: a heavy row's gather saves the most lines)
+            slim = mm.counts12 != nullptr && big <= MVHDP_SLIM_MAX;
             // (between the two: a light row whose deltas of one sweep may pass +-32767 -- they stay in the 32-bit delta table, SweepLaunch::delta16)
-            if (lane == 0) mm.heavy[row] = hv ? MVHDP_ROW_HEAVY : (sum > 32767 ? MVHDP_ROW_BIG : 0);
+            if (lane == 0) mm.heavy[row] = (uint8_t)((hv ? MVHDP_ROW_HEAVY : (sum > 32767 ? MVHDP_ROW_BIG : 0)) | (slim ? MVHDP_ROW_SLIM : 0));
         }
         for (int k0 = 0; k0 < K; k0 += WAVE * TB) {
             int cv[TB], nkv[TB];
@@ -213,6 +221,7 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
                     const int c = cv[u];
                     if (light_src) cnt[k] = c;                             // the mirror is the authority for this row: write it through
                     else if (!from_mirror) c16[k] = hv ? (uint16_t)65535 : (uint16_t)c;
+                    if (slim) ((int*)t)[k] = c;                            // (staged for the 12-bit image below: t[0 .. K) is not in use before the tree is summed)
                     double leaf;
                     if (inference_leaves) {                                // INF:576: p_wt alone
                         leaf = ((double)c + beta) / ((double)nkv[u] + beta_sum);
@@ -226,6 +235,25 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
                     t[K + k] = leaf;
                 }
             }
+        }
+        if (slim) {
+            // the row of the 12-bit image, a 32-bit word a lane, whole lines per store: word w of line j holds bits 32w .. 32w + 31 of the
+            // line's 85 cells laid end to end, 12 bits each (mvhdp_slim.h) -- parts of up to four cells, read from the staged copy
+            __syncthreads();
+            const int* cs = (const int*)t;
+            unsigned int* out12 = (unsigned int*)(mm.counts12 + (size_t)row * mvhdp_slim_row_bytes(K));
+            const int nwords = (int)(mvhdp_slim_row_bytes(K) >> 2);
+            for (int w = lane; w < nwords; w += WAVE) {
+                const int j = w >> 5, bit0 = (w & 31) * 32;
+                unsigned int v = 0;
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    const int i = bit0 / 12 + q, k = j * MVHDP_SLIM_CELLS + i, sh = 12 * i - bit0;      // sh in (-12, 32)
+                    if (i < MVHDP_SLIM_CELLS && k < K && sh < 32) { const unsigned int c = (unsigned int)cs[k]; v |= sh >= 0 ? c << sh : c >> -sh; }
+                }
+                out12[w] = v;
+            }
+            __syncthreads();
         }
         tree_from_leaves(mm, row, t, lane, write_full);
     }
@@ -321,7 +349,7 @@ __global__ __launch_bounds__(256) void apply2_counts_kernel(MvModel mm, const in
         if (!d) continue;
         const int old = __hip_atomic_fetch_add(&mm.counts[i], d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         neg += old + d < 0;
-        if (use_mirror && i < n_cells && mm.heavy[i / K] != MVHDP_ROW_HEAVY) __hip_atomic_fetch_add(&m32[i >> 1], (unsigned int)d << ((i & 1) * 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (use_mirror && i < n_cells && MVHDP_ROW_CLASS(mm.heavy[i / K]) != MVHDP_ROW_HEAVY) __hip_atomic_fetch_add(&m32[i >> 1], (unsigned int)d << ((i & 1) * 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (neg && negatives) atomicAdd(negatives, (unsigned long long)neg);
 }
@@ -347,7 +375,7 @@ __global__ __launch_bounds__(256) void apply_sparse_kernel(MvModel mm, int32_t* 
         if (!dl) continue;
         mm.counts[i] += dl;
         d[i] = 0;
-        if (use_mirror && i < n_cells && mm.heavy[i / K] != MVHDP_ROW_HEAVY) __hip_atomic_fetch_add(&m32[i >> 1], (unsigned int)dl << ((i & 1) * 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (use_mirror && i < n_cells && MVHDP_ROW_CLASS(mm.heavy[i / K]) != MVHDP_ROW_HEAVY) __hip_atomic_fetch_add(&m32[i >> 1], (unsigned int)dl << ((i & 1) * 16), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 }
 
@@ -388,7 +416,7 @@ __global__ __launch_bounds__(256) void widen_mirror_kernel(MvModel mm)
     const int lane = threadIdx.x & 63;
     const int64_t wstride = (int64_t)gridDim.x * (blockDim.x >> 6);
     for (int64_t row = (int64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); row < nrows; row += wstride) {
-        if (mm.heavy[row] == MVHDP_ROW_HEAVY) continue;
+        if (MVHDP_ROW_CLASS(mm.heavy[row]) == MVHDP_ROW_HEAVY) continue;
         const uint16_t* c16 = mm.counts16 + row * K;
         int32_t* cnt = mm.counts + row * K;
         for (int k = lane; k < K; k += WAVE) cnt[k] = (int)c16[k];
@@ -449,7 +477,7 @@ __global__ __launch_bounds__(64) void live_rows_prepare_kernel(MvModel mm, bool 
         const int Kp = (K + 7) & ~7;
         const float* cf = mm.coef + (int64_t)m * Kp;
         const float smp_total = mm.coef[(int64_t)mm.M * Kp + (int64_t)m * K + K - 1];   // S_m: the smoothing parts of the view's leaves, summed
-        const bool light_src = from_mirror && mm.heavy[row] != MVHDP_ROW_HEAVY;
+        const bool light_src = from_mirror && MVHDP_ROW_CLASS(mm.heavy[row]) != MVHDP_ROW_HEAVY;
         bool hv = false;
         if (!from_mirror) {                                          // the row's weight class, as build_trees_kernel decides it
             long long sum = 0;
@@ -491,7 +519,7 @@ __global__ __launch_bounds__(64) void live_rows_prepare_kernel(MvModel mm, bool 
         for (int sft = 32; sft >= 1; sft >>= 1) { acc += __shfl_xor(acc, sft, WAVE); acc0 += __shfl_xor(acc0, sft, WAVE); }
         if (lane == 0) { mm.root[row] = (double)smp_total + acc; mm.mass0[row] = (float)acc0; }
         // the HEAVY rows (a few hundred at most: each holds more than 65534 tokens), listed for the kernel that keeps their stored trees current
-        if (lane == 0 && heavy_list && mm.heavy[row] == MVHDP_ROW_HEAVY) {
+        if (lane == 0 && heavy_list && MVHDP_ROW_CLASS(mm.heavy[row]) == MVHDP_ROW_HEAVY) {
             const unsigned int i = atomicAdd(heavy_n, 1u);
             if ((int)i < heavy_cap) heavy_list[i] = (int32_t)row;
         }

@@ -16,6 +16,7 @@
 #include <cstring>
 
 #include "mvhdp_device.h"
+#include "mvhdp_slim.h"
 #include "../../include/mvhdp.h"
 
 // Streams of one sweep: the primary variant on the handle's stream, every wider class that carries weight on a side stream of its own
@@ -55,7 +56,17 @@ struct PlanIn {
     int num_cus = 256;
     size_t max_lds = 160 * 1024;
     PlanRegs regs{};
+    bool slim_table = false;                    // the handle keeps the 12-bit image of n_wk (MvModel::counts12; plan_slim_table says when it can pay)
+    int max_types = 0;                          // types of the largest view (the 12-bit flavour keeps a row's class in bit 28 of the type id)
 };
+
+// The 12-bit image of n_wk (mvhdp_slim.h): a row is ceil(K / 85) whole lines, a row of the 16-bit mirror spans at least ceil(K / 64).
+// Worth keeping where that is fewer (K = 400: 5 against 7; K = 1000: 12 against 16; not K = 100: 2 and 2) and the type ids leave bit 28 free.
+// K = 200 (3 against 4) is left on the mirror: its sweep is bound by latency, not by lines (C3, profiles/slim_rows.md) -- `level` 2 takes
+// the table wherever the lines are fewer (measurements), 0 never.
+enum { PLAN_SLIM_MAX_CLASS = 2 };               // the 1-, 2- and 4-round variants have the flavour; the 8- and 16-round ones sit at their register limit and stay on the mirror
+static inline bool plan_slim_table(int K, int max_types, int level) { return mvhdp_slim_pays(K, max_types, level) != 0; }   // (one definition: mvhdp_slim.h, which the CPU test compiles)
+
 
 struct ClassLaunch {
     bool used = false;                          // a kernel of this class is launched
@@ -67,7 +78,7 @@ struct ClassLaunch {
     size_t lds = 0;
     int grid = 0;                               // resident blocks (the launch takes min(grid, what its entities need))
     int stream = PLAN_STREAM_MAIN;
-    int walk = 0, narrow = 0;                   // kernel flavour
+    int walk = 0, narrow = 0;                   // kernel flavour (narrow: 0 the 32-bit table, 1 the 16-bit mirror, 2 the 12-bit image for the rows it holds and the mirror for the others)
     double theta[MVHDP_MAXM] = {0};             // walk thresholds per view
 };
 
@@ -137,6 +148,7 @@ struct PlanTuning {
     int four_round_on_c = -1;                   // the 4-round class behind the 2-round one on stream C: -1 where it holds under 3 % of the tokens, 0 never, 1 always
     int delta16 = 1;                            // 1: 16-bit delta cells for the rows that cannot overflow them (plain deferred sweeps); 0: never
     int narrow_wide = 1;                        // 1: deferred sweeps gather from the mirror in the wider variants too (0: the 1-round variant only)
+    int slim = 1;                               // deferred sweeps gather slim rows from the 12-bit image: 1 where plan_slim_table says it pays, 2 wherever its rows have fewer lines, 0 never
     int fork_delay_us = 0;                      // microseconds the handle's stream is held between the fork event and the primary kernel (0: none)
     int widest_on_main = 0;                     // 1: the widest class on the handle's stream, the primary on a side stream (diagnostics)
     int live_overlap = -1;                      // live sweeps: segments overlapped (two in flight); 0: one after the other
@@ -511,6 +523,11 @@ static inline void plan_sweep(const PlanIn& in, const PlanTuning& tu, WalkTuner&
     if (mirror_ok && !p.live && p.cls[0].used && p.cls[0].fast && p.cls[0].walk) p.cls[0].narrow = 1;
     if (mirror_ok && !p.live && tu.narrow_wide && tu.narrow != 1)                      // the wider variants too (since the row's weight class travels with the type id: 1 % on C4)
         for (int c = 1; c < 5; c++) if (p.cls[c].used && p.cls[c].fast && p.cls[c].walk) p.cls[c].narrow = 1;
+    // The 12-bit image for the rows it holds (narrow = 2): deferred sweeps only -- a live sweep's atomics land in the mirror, and so do the deltas
+    // of overlapped segments, neither of which packed 12-bit cells can take --, never with a mix or debug outputs (no such flavour), and in the
+    // 1-, 2- and 4-round variants only.  The image is written with the mirror, so whatever makes the mirror this sweep's start counts makes it so too.
+    if (mirror_ok && !p.live && !p.overlap && !in.vectors_mix && !in.debug && in.slim_table && plan_slim_table(K, in.max_types, tu.slim))
+        for (int c = 0; c <= PLAN_SLIM_MAX_CLASS; c++) if (p.cls[c].used && p.cls[c].fast && p.cls[c].narrow == 1) p.cls[c].narrow = 2;
     // A live sweep updates n_wk while it samples: the mirror stays usable only if the sweep's own atomics keep it current, which takes
     // every kernel of the sweep in the NARROW (hence walk) flavour -- no generic kernel among them.
     // The deltas of a plain deferred sweep (one segment, applied by this call) in 16-bit cells where the row allows it: the kernels of the

@@ -26,6 +26,7 @@
 #include "mvhdp_device.h"
 #include "../../include/mvhdp.h"
 #include "mvhdp_wave.h"
+#include "mvhdp_slim.h"
 
 // The 8- and 16-round variants keep the per-view slot counts as 16-bit values (its kernel diverts an entity with
 // a view of more than 65535 tokens): 78 KB instead of 120 KB per block at K = 1000 with 5 views, i.e. the
@@ -76,9 +77,8 @@ size_t mvhdp_sweep_fast_wave_bytes(int M, int S_cap, int rmax)
 // NARROW (walk flavour only): the n_wk gather reads the 16-bit mirror of the counts (MvModel::counts16, written with the trees at
 // the start of the sweep) -- half the lines of the row -- for a light row, and the 32-bit table for a heavy one (MvModel::heavy: a
 // type with more than 65534 tokens, whose mirror cells all read 65535); the row's class travels with the token's type id (W_HEAVY),
-// so the choice is a scalar branch at the gather and the values need no check when they are used.  Same numbers, so same results.  A deferred sweep uses it for the 1-round variant only (the 2-round variant is 4 %
-// slower with it: two 2-byte loads per lane cost it more than the lines are worth).  A live sweep (SweepLaunch::live16) uses it for
-// every variant: there the chunk-end atomics of the light rows land IN the mirror -- two 16-bit cells per 32-bit word, +-1 or +-65536,
+// so the choice is a scalar branch at the gather and the values need no check when they are used.  Same numbers, so same results.  A deferred sweep uses it for every variant
+// (PlanTuning::narrow_wide, since the row's class travels with the type id), and so does a live sweep (SweepLaunch::live16): there the chunk-end atomics of the light rows land IN the mirror -- two 16-bit cells per 32-bit word, +-1 or +-65536,
 // which cannot carry: a light row's cell stays below 65535 and a decrement only ever takes back a token that was counted -- so the
 // mirror is what every later token of the sweep reads (UPD:197-207 applied while the workers sample), at half the gather traffic.
 // How a live sweep's gathers see the other waves' atomics (diagnostics; tools/microbench/live_staleness.hip):
@@ -104,7 +104,22 @@ template <typename T>
 __device__ __forceinline__ T gather_mix(gptr_t p) { return *(const __attribute__((address_space(1))) T*)p; }
 #define W_HEAVY 0x40000000                      // bit 30 of a lane's type id: the row is heavy (type ids stay below 2^29: mvhdp_create checks)
 #define W_BIG   0x20000000                      // bit 29: the row's deltas do not fit 16 bits for sure (MVHDP_ROW_BIG or heavy): they go to the 32-bit delta table
-#define W_ROW(w) ((w) & 0x1fffffff)
+#define W_SLIM  0x10000000                      // bit 28 (NARROW = 2 only): the row is in the 12-bit image (MVHDP_ROW_SLIM) -- that flavour's type ids stay below 2^28: the plan sees to it
+#define W_ROW(w) ((w) & (NARROW == 2 ? 0x0fffffff : 0x1fffffff))      // (inside sweep_fast_kernel)
+// NARROW = 2 (deferred sweeps only; never LIVEROWS, live16, MIX or DEBUG): a slim row's cells come from the 12-bit image of the counts
+// (MvModel::counts12, mvhdp_slim.h) -- ceil(K / 85) whole lines a row instead of the 6.25 .. 7 a row of the mirror spans at K = 400 --, any
+// other row's as with NARROW = 1.  A slot's place in a 12-bit row is one register, byte offset << 5 | shift, formed once per entity and
+// view: v_bfe_u32 reads bits 4:0 of its offset operand, so the gather is a shift for the address, a 2-byte load (at an odd address for
+// half the cells) and the extraction.  The extraction belongs to the token that USES the cells (slim_cell, at the top of its turn), not to the
+// gather that asks for them a token ahead: done at the gather it waits for the load it has just issued, and the pipeline is gone (C4: 23.8 ->
+// 26.5 ms, profiles/slim_rows.md).  Same integers in g[], so everything downstream is what it was.  A flavour of its own so that every other
+// one stays what it is, register for register.
+typedef unsigned short u16_any_t __attribute__((aligned(1)));
+__device__ __forceinline__ int gather_slim(gptr_t row, int packed)       // the 16 bits that hold the cell, as they are
+{
+    return (int)*(const __attribute__((address_space(1))) u16_any_t*)(row + ((unsigned int)packed >> 5));
+}
+__device__ __forceinline__ int slim_cell(int raw, int packed) { return (int)__builtin_amdgcn_ubfe((unsigned int)raw, (unsigned int)packed, 12u); }
 // The tree branch of a live sweep in its live-rows form (SweepLaunch::live_rows; WRK:533-535 against what UPD:242-260 keeps current):
 // a topic with probability proportional to leaf_k = coef_k * (n_wk + beta) over ALL K topics, from the word's LIVE row.  The leaf splits
 // into a smoothing part coef_k * beta -- the same for every word of the view: its running sums smp[k] are a table of the segment -- and a
@@ -297,10 +312,11 @@ __device__ __forceinline__ int row_sample_live(rowq_t q0, bool have_q0, bool in_
 // a scalar branch).  A flavour of its own so that the kernels of a handle without a mix stay what they were, register for register.  The 1- and
 // 2-round variants are compiled for 6 waves per SIMD (80 registers) instead of 7: each slot brings two registers for its mix value and two for
 // the one in flight (MVHDP_LB_MIX; 7 waves with the spills that takes: the same at C4, 3 % slower at C3, profiles/vectors_mix.md).
-template <int RMAX, bool DEBUG, bool WALK, bool NARROW, bool ROOMY = false, int LIVEROWS = 0, bool MIX = false>
+template <int RMAX, bool DEBUG, bool WALK, int NARROW, bool ROOMY = false, int LIVEROWS = 0, bool MIX = false>
 __global__ __launch_bounds__(256, ((MIX && RMAX <= 2) ? MVHDP_LB_MIX : RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB4 : (RMAX == 2 ? (ROOMY ? MVHDP_LB2_ROOMY : (LIVEROWS ? MVHDP_LB_ROWS : MVHDP_LB2)) : (RMAX == 1 ? (LIVEROWS ? MVHDP_LB_ROWS : WALK ? MVHDP_LB1W : MVHDP_LB1) : MVHDP_LB16))))) void sweep_fast_kernel(MvModel mm, SweepLaunch sl)
 {
     static_assert(!MIX || (WALK && LIVEROWS == 0 && !ROOMY), "the mix flavours: walk flavour, stored trees");
+    static_assert(NARROW != 2 || (WALK && !DEBUG && LIVEROWS == 0 && !MIX), "the 12-bit image: deferred sweeps of the walk flavour only");
     extern __shared__ __align__(16) unsigned char smem[];
 #ifdef MVHDP_TIMING
     const unsigned long long t_begin0 = __builtin_amdgcn_s_memtime();
@@ -591,9 +607,14 @@ __global__ __launch_bounds__(256, ((MIX && RMAX <= 2) ? MVHDP_LB_MIX : RMAX == 8
             const int64_t row0 = mm.rowbase[m];
             const char* nwk_v = (const char*)(nwk + row0 * K);           // the view's rows of the counts, and of their 16-bit mirror
             const char* nwk16_v = (const char*)(nwk16 + row0 * K);
+            const char* nwk12_v = (NARROW == 2) ? (const char*)mm.counts12 + (size_t)row0 * mvhdp_slim_row_bytes(K) : nullptr;   // ... and of the 12-bit image
+            const unsigned int row12_bytes = (unsigned int)mvhdp_slim_row_bytes(K);
             int koffh[RMAX];                                             // (the slot's byte offset inside a mirror row)
 #pragma unroll
             for (int r = 0; r < RMAX; r++) koffh[r] = koff[r] >> 1;
+            int kslim[RMAX];                                             // NARROW = 2: the slot's place inside a 12-bit row, byte offset << 5 | shift (gather_slim)
+#pragma unroll
+            for (int r = 0; r < RMAX; r++) { const int k = koff[r] >> 2; kslim[r] = (NARROW == 2) ? (int)((mvhdp_slim_byte(k) << 5) | mvhdp_slim_shift(k)) : 0; }
             const int Vm = mm.V[m];
             const double walk_theta = sl.walk_theta[m];
             const unsigned int v_tok0 = n_tok, v_tree0 = c_tree;
@@ -625,8 +646,9 @@ __global__ __launch_bounds__(256, ((MIX && RMAX <= 2) ? MVHDP_LB_MIX : RMAX == 8
                 // only in the 32-bit table, MvModel::heavy), so that the gather of a token's row knows the table to read from a scalar of
                 // the broadcast it does anyway -- nothing to check or resolve when the values are used.  (W_ROW strips the bit.)
                 if (NARROW && w_l >= 0) {
-                    const int hv = mm.heavy[row0 + w_l];
+                    const int hb = mm.heavy[row0 + w_l], hv = MVHDP_ROW_CLASS(hb);
                     if (hv) w_l |= (hv == MVHDP_ROW_HEAVY) ? (W_HEAVY | W_BIG) : W_BIG;
+                    if (NARROW == 2 && (hb & MVHDP_ROW_SLIM)) w_l |= W_SLIM;       // (whatever its weight class: the gather asks for this one first)
                 }
                 const float u1f_l = (float)u1_l;                             // (may round to 1.0f: the screening then hands the token to fp64)
                 int znew_l = z_l;
@@ -730,10 +752,14 @@ __global__ __launch_bounds__(256, ((MIX && RMAX <= 2) ? MVHDP_LB_MIX : RMAX == 8
                     const int w0 = bcast_i(w_l, ra ? (int)__builtin_ctzll(ra) : t_first);
                     const unsigned int r0 = (unsigned int)W_ROW(max(w0, 0));
                     const bool h0 = w0 >= 0 && (w0 & W_HEAVY);
-                    if (NARROW && !h0) {
+                    if (NARROW == 2 && w0 >= 0 && (w0 & W_SLIM)) {
+                        const gptr_t c0s = scalar_row(nwk12_v, r0, row12_bytes);
+#pragma unroll
+                        for (int r = 0; r < RMAX; r++) { const int v = gather_slim(c0s, kslim[r]); if (a == 0) gn[r] = v; else gn2[r] = v; }
+                    } else if (NARROW && !h0) {
                         const gptr_t c0q = scalar_row(nwk16_v, r0, (unsigned int)K * 2u);
 #pragma unroll
-                        for (int r = 0; r < RMAX; r++) { const int v = gather_cell<uint16_t>(c0q + (unsigned int)koffh[r]); if (a == 0) gn[r] = v; else gn2[r] = v; }
+                        for (int r = 0; r < RMAX; r++) { const int v = gather_cell<uint16_t>(c0q + (NARROW == 2 ? (unsigned int)koff[r] >> 1 : (unsigned int)koffh[r])); if (a == 0) gn[r] = v; else gn2[r] = v; }
                     } else {
                         const gptr_t c0p = scalar_row(nwk_v, r0, (unsigned int)K * 4u);
 #pragma unroll
@@ -906,6 +932,9 @@ __global__ __launch_bounds__(256, ((MIX && RMAX <= 2) ? MVHDP_LB_MIX : RMAX == 8
 #undef sn_get
 #undef sn_set
 
+// The 12-bit flavour (NARROW = 2) is compiled for the 1-, 2- and 4-round variants; the 8- and 16-round variants sit at their register
+// limit and stay on the mirror (the plan knows: PLAN_SLIM_MAX_CLASS)
+#define MVHDP_SLIM_RMAX 4
 // debug launches always take the WALK flavour (one instantiation fewer per variant; a threshold of 0 walks every token)
 static bool roomy_build(int rmax, int K) { return rmax == 2 && K >= 512; }
 // live-rows flavour with the two-batch shortcut: a row of the 16-bit mirror in exactly two register batches of 512 cells (the roomy 2-round
@@ -921,7 +950,7 @@ static const void* fast_kernel_ptr_mix(bool debug, bool narrow)
 }
 
 template <int RMAX>
-static const void* fast_kernel_ptr(bool debug, bool walk, bool narrow, int K = 0, bool live_rows = false)
+static const void* fast_kernel_ptr(bool debug, bool walk, bool narrow, int K = 0, bool live_rows = false, bool slim = false)
 {
     if (live_rows && !debug) {
         if constexpr (RMAX == 2) { if (narrow && roomy_build(RMAX, K)) return (const void*)sweep_fast_kernel<2, false, true, true, true, 2>; }
@@ -929,6 +958,12 @@ static const void* fast_kernel_ptr(bool debug, bool walk, bool narrow, int K = 0
         return narrow ? (const void*)sweep_fast_kernel<RMAX, false, true, true, false, 1> : (const void*)sweep_fast_kernel<RMAX, false, true, false, false, 1>;
     }
     if (narrow && walk && !debug) {
+        if constexpr (RMAX <= MVHDP_SLIM_RMAX) {
+            if (slim) {
+                if constexpr (RMAX == 2) { if (roomy_build(RMAX, K)) return (const void*)sweep_fast_kernel<2, false, true, 2, true>; }
+                return (const void*)sweep_fast_kernel<RMAX, false, true, 2>;
+            }
+        }
         if constexpr (RMAX == 2) { if (roomy_build(RMAX, K)) return (const void*)sweep_fast_kernel<2, false, true, true, true>; }
         return (const void*)sweep_fast_kernel<RMAX, false, true, true>;
     }
@@ -943,6 +978,8 @@ static hipError_t launch_fast(const MvModel& mm, const SweepLaunch& sl, int grid
     dim3 block(64 * sl.waves_per_block);
     const bool narrow = sl.narrow && sl.walk && !debug;
     const bool rows = sl.live_rows && sl.walk && !debug;
+    const bool slim = narrow && sl.narrow == 2;
+    if (slim && (RMAX > MVHDP_SLIM_RMAX || rows || sl.live16 || mm.mix || !mm.counts12)) return hipErrorInvalidValue;   // (the plan asks for it where it exists)
     if (mm.mix) {
         if (rows || !sl.walk) return hipErrorInvalidValue;                 // (the plan gives a sweep with a mix stored trees and the walk flavour)
         if (lds > 65536) {
@@ -955,7 +992,7 @@ static hipError_t launch_fast(const MvModel& mm, const SweepLaunch& sl, int grid
         return hipGetLastError();
     }
     if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute(fast_kernel_ptr<RMAX>(debug, sl.walk != 0, narrow, mm.K, rows), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipError_t e = hipFuncSetAttribute(fast_kernel_ptr<RMAX>(debug, sl.walk != 0, narrow, mm.K, rows, slim), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return e;
     }
     if (debug)        hipLaunchKernelGGL((sweep_fast_kernel<RMAX, true, true, false>), dim3(grid_blocks), block, lds, s, mm, sl);
@@ -964,6 +1001,12 @@ static hipError_t launch_fast(const MvModel& mm, const SweepLaunch& sl, int grid
         else if (narrow && two_batch_rows(mm.K)) hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, true, false, 2>), dim3(grid_blocks), block, lds, s, mm, sl);
         else if (narrow) hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, true, false, 1>), dim3(grid_blocks), block, lds, s, mm, sl);
         else             hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, false, false, 1>), dim3(grid_blocks), block, lds, s, mm, sl);
+    }
+    else if (slim) {
+        if constexpr (RMAX <= MVHDP_SLIM_RMAX) {
+            if (roomy_build(RMAX, mm.K)) { if constexpr (RMAX == 2) hipLaunchKernelGGL((sweep_fast_kernel<2, false, true, 2, true>), dim3(grid_blocks), block, lds, s, mm, sl); }
+            else hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, 2>), dim3(grid_blocks), block, lds, s, mm, sl);
+        }
     }
     else if (narrow && roomy_build(RMAX, mm.K)) {
         // (the plan sized the grid for the 72-register build: the seventh block of a CU waits for a free slot and finds the queue empty)

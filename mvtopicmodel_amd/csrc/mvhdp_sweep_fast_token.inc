@@ -21,7 +21,7 @@
                         // is issued would mean waiting for the row load as well -- the counter is in order)
 #pragma unroll
                         for (int r = 0; r < RMAX; r++) asm volatile("" : "+v"(g[r]));
-                        if (spec_t) rowq = row_batch_load<NARROW>(rowp_t, K, bsel_t, lane);
+                        if (spec_t) rowq = row_batch_load<(NARROW != 0)>(rowp_t, K, bsel_t, lane);
                     }
                     // the buffer is free again: gather for the token NB positions ahead.  With two buffers the
                     // gather is issued on every path and for every slot round (past the chunk's end it re-reads the
@@ -30,13 +30,17 @@
                     // (`rem` = the tokens still to visit, this one already taken out: the token NB ahead is its NB-th set bit)
                     const unsigned long long rem_n = (NB == 2) ? (rem & (rem - 1)) : rem;
 #pragma unroll
-                    for (int r = 0; r < RMAX; r++) { touch_lane_off(koff[r]); if (NARROW) touch_lane_off(koffh[r]); }
+                    for (int r = 0; r < RMAX; r++) { touch_lane_off(koff[r]); if (NARROW == 1) touch_lane_off(koffh[r]); if (NARROW == 2) touch_lane_off(kslim[r]); }
                     if (NB == 2 || LIVEROWS || rem_n) {                     // (live-rows form: always -- the wait for the token's row counts the loads issued behind it)
                         const int wn = bcast_i(w_l, rem_n ? (int)__builtin_ctzll(rem_n) : TOK_T);
-                        if (NARROW && !(wn & W_HEAVY)) {                     // a light row: the 16-bit mirror holds its counts
+                        if (NARROW == 2 && (wn & W_SLIM)) {                  // a slim row: the 12-bit image holds its counts, in fewer lines
+                            const gptr_t cns = scalar_row(nwk12_v, (unsigned int)W_ROW(wn), row12_bytes);
+#pragma unroll
+                            for (int r = 0; r < RMAX; r++) TOK_G[r] = gather_slim(cns, kslim[r]);
+                        } else if (NARROW && !(wn & W_HEAVY)) {              // a light row: the 16-bit mirror holds its counts
                             const gptr_t cnq = scalar_row(nwk16_v, (unsigned int)W_ROW(wn), (unsigned int)K * 2u);
 #pragma unroll
-                            for (int r = 0; r < RMAX; r++) TOK_G[r] = gather_cell<uint16_t>(cnq + (unsigned int)koffh[r]);
+                            for (int r = 0; r < RMAX; r++) TOK_G[r] = gather_cell<uint16_t>(cnq + (NARROW == 2 ? (unsigned int)koff[r] >> 1 : (unsigned int)koffh[r]));
                         } else {
                             const gptr_t cnp = scalar_row(nwk_v, (unsigned int)W_ROW(wn), (unsigned int)K * 4u);
 #pragma unroll
@@ -48,7 +52,12 @@
                             for (int r = 0; r < RMAX; r++) TOK_MG[r] = gather_mix<mixg_t>(mnp + ((unsigned int)koff[r] << MIXSH));
                         }
                     }
-                    const int w = W_ROW(bcast_i(w_l, TOK_T));                // (a known type: the loop's mask holds no other)
+                    const int wcur = bcast_i(w_l, TOK_T);
+                    const int w = W_ROW(wcur);                               // (a known type: the loop's mask holds no other)
+                    if (NARROW == 2 && (wcur & W_SLIM)) {                    // this token's cells came from the 12-bit image: 16 bits each, the cell inside them
+#pragma unroll
+                        for (int r = 0; r < RMAX; r++) g[r] = slim_cell(g[r], kslim[r]);
+                    }
                     const int so = bcast_i(so_l, TOK_T);
                     const int64_t row = row0 + w;
 
@@ -341,7 +350,7 @@
 #endif
                             if (sl.flags & 0x2000u) znew = bcast_i(z_l, TOK_T);      // (0x2000: measurement only, MVHDP_NO_ROW_SAMPLE)
                             else
-                            znew = uniform_i(row_sample_live<NARROW, LIVEROWS == 2>(rowq, spec_t, coef_s != nullptr, (const __attribute__((address_space(3))) float*)coef_s + m * Kp, mm.coef + (int64_t)m * Kp, smp_m, smS, rowp_t, K,
+                            znew = uniform_i(row_sample_live<(NARROW != 0), LIVEROWS == 2>(rowq, spec_t, coef_s != nullptr, (const __attribute__((address_space(3))) float*)coef_s + m * Kp, mm.coef + (int64_t)m * Kp, smp_m, smS, rowp_t, K,
                                                                      bcast_f(u2f_l, TOK_T), bcast_f(root32_l, TOK_T), bsel_t, (LIVEROWS == 2 && bsel_t) ? mm.mass0[row] : 0.0f /* (a scalar load: the address is wave-uniform) */, lane, &t_rs1));
                             if (znew < 0) znew = K - 1;                      // WRK:549-552
 #ifdef MVHDP_TIMING

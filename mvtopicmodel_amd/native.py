@@ -38,6 +38,8 @@ EMB_SERIAL = 0x1
 BUF_COUNTS = 0
 BUF_DELTA = 1
 BUF_BIRTH_KEYS = 2
+BUF_COUNTS12 = 3        # read-only views for tests and diagnostics: the 12-bit image of n_wk and the row classes
+BUF_ROW_CLASS = 4
 ACT_KEY_NONE = (1 << 63) - 1
 
 
