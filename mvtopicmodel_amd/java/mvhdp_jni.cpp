@@ -1,8 +1,9 @@
 // mvhdp_jni.cpp — JNI shim between org.madgik.MVTopicModel.NativeSampler and the C ABI
-// of libmvhdp.so (include/mvhdp.h).  NOT compiled in the build image (no JDK there):
+// of libmvhdp.so (include/mvhdp.h).  NOT part of the build (no JDK there); a host builds it with
 //   g++ -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -Iinclude
 //       mvtopicmodel_amd/java/mvhdp_jni.cpp -Lmvtopicmodel_amd/lib -lmvhdp -o libmvhdp_jni.so      (one command line)
-// (tests/test_jni_shim.py type-checks it against a declaration-only jni.h stub.)
+// The tests compile this file unmodified against a declaration-only jni.h (tests/native/jni_stub), link it against a test-side
+// JNIEnv (tests/native/fake_jvm.cpp) and run every entry: tests/test_jni_fake_jvm.py without a device, tests/test_gpu_jni.py with one.
 //
 // Arrays cross with Get<Type>ArrayElements / Release<Type>ArrayElements, never with GetPrimitiveArrayCritical: every
 // mvhdp_* call may block (hipMalloc, synchronous copies, a whole sweep), and JNI forbids blocking -- or any other JNI
@@ -108,21 +109,23 @@ bool bad_len(JNIEnv* env, jarray a, jlong want, const char* what)
 }
 
 // RAII over Get/Release<Type>ArrayElements (mode 0: copy back and free; JNI_ABORT: input only)
+// Several of them are declared side by side: once one Get has failed (OutOfMemoryError pending) the next ones take nothing -- JNI allows
+// no Get while an exception is pending -- and report failed() as well.
 struct Ints {
     JNIEnv* env; jintArray a; jint* p; jint mode;
-    Ints(JNIEnv* e, jintArray arr, jint m) : env(e), a(arr), p(arr ? e->GetIntArrayElements(arr, nullptr) : nullptr), mode(m) {}
+    Ints(JNIEnv* e, jintArray arr, jint m) : env(e), a(arr), p(arr && !e->ExceptionCheck() ? e->GetIntArrayElements(arr, nullptr) : nullptr), mode(m) {}
     ~Ints() { if (a && p) env->ReleaseIntArrayElements(a, p, mode); }
     bool failed() const { return a && !p; }
 };
 struct Longs {
     JNIEnv* env; jlongArray a; jlong* p; jint mode;
-    Longs(JNIEnv* e, jlongArray arr, jint m) : env(e), a(arr), p(arr ? e->GetLongArrayElements(arr, nullptr) : nullptr), mode(m) {}
+    Longs(JNIEnv* e, jlongArray arr, jint m) : env(e), a(arr), p(arr && !e->ExceptionCheck() ? e->GetLongArrayElements(arr, nullptr) : nullptr), mode(m) {}
     ~Longs() { if (a && p) env->ReleaseLongArrayElements(a, p, mode); }
     bool failed() const { return a && !p; }
 };
 struct Doubles {
     JNIEnv* env; jdoubleArray a; jdouble* p; jint mode;
-    Doubles(JNIEnv* e, jdoubleArray arr, jint m) : env(e), a(arr), p(arr ? e->GetDoubleArrayElements(arr, nullptr) : nullptr), mode(m) {}
+    Doubles(JNIEnv* e, jdoubleArray arr, jint m) : env(e), a(arr), p(arr && !e->ExceptionCheck() ? e->GetDoubleArrayElements(arr, nullptr) : nullptr), mode(m) {}
     ~Doubles() { if (a && p) env->ReleaseDoubleArrayElements(a, p, mode); }
     bool failed() const { return a && !p; }
 };
@@ -243,7 +246,10 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetHyper(JNIE
         jdoubleArray r = static_cast<jdoubleArray>(env->GetObjectArrayElement(alpha, m));
         jdoubleArray pa = static_cast<jdoubleArray>(env->GetObjectArrayElement(p_a, m));
         jdoubleArray pb = static_cast<jdoubleArray>(env->GetObjectArrayElement(p_b, m));
-        if (bad_len(env, r, K1, "setHyper alpha[m] (K+1 entries, PTM:196)") || bad_len(env, pa, M, "setHyper p_a[m]") || bad_len(env, pb, M, "setHyper p_b[m]")) return;
+        if (bad_len(env, r, K1, "setHyper alpha[m] (K+1 entries, PTM:196)") || bad_len(env, pa, M, "setHyper p_a[m]") || bad_len(env, pb, M, "setHyper p_b[m]")) {
+            env->DeleteLocalRef(r); env->DeleteLocalRef(pa); env->DeleteLocalRef(pb);    // (a refusal leaves no row reference behind either)
+            return;
+        }
         env->GetDoubleArrayRegion(r, 0, K1, a.data() + static_cast<size_t>(m) * K1);
         env->GetDoubleArrayRegion(pa, 0, M, hy.p_a[m]);
         env->GetDoubleArrayRegion(pb, 0, M, hy.p_b[m]);
@@ -313,7 +319,9 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSweep(JNIEnv*
 {
     ShardPin pin_(p); Shard* s = pin_.s;
     if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
-    if (pOverride && bad_len(env, pOverride, s->D * s->M * s->M, "sweep pOverride [D][M][M]")) return;
+    // (D is -1 until setCorpus: there is no [D][M][M] to check against yet, and the library would refuse the sweep anyway)
+    if (pOverride && s->D < 0) { throw_msg(env, "java/lang/IllegalStateException", "sweep pOverride: setCorpus has not been called"); return; }
+    if (pOverride && bad_len(env, pOverride, s->D * static_cast<jlong>(s->M) * s->M, "sweep pOverride [D][M][M]")) return;
     mvhdp_sweep_stats st;
     int rc;
     {
@@ -401,14 +409,16 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetTuning(JNI
     jint iv[8]; jdouble dv[17];
     env->GetIntArrayRegion(ints, 0, 8, iv);
     env->GetDoubleArrayRegion(doubles, 0, 17, dv);
+    // from the handle's own block: a field the Java block does not carry (single_wave, live_overlap, live_rows, whatever the struct
+    // grows next) keeps the value the handle holds instead of being zeroed behind the host's back
     mvhdp_tuning t;
-    std::memset(&t, 0, sizeof t);
+    int rc = mvhdp_get_tuning(s->h, &t);
+    if (rc) { throw_rt(env, s->h, rc, "mvhdp_get_tuning"); return; }
     t.force_primary = iv[0]; t.narrow = iv[1]; t.walk_fixed = iv[2]; t.single_stream = iv[3]; t.live16 = iv[4];
-    t.learnt_walk_step[0] = iv[5]; t.learnt_walk_step[1] = iv[6]; t.learnt_walk_step[2] = iv[7]; t.learnt_walk_step[3] = -1;
-    t.live_overlap = -1;                                     // (the library's default: overlapped segments in live sweeps)
+    t.learnt_walk_step[0] = iv[5]; t.learnt_walk_step[1] = iv[6]; t.learnt_walk_step[2] = iv[7];
     t.primary_min_share = dv[0];
     for (int m = 0; m < 8; m++) { t.walk_theta[m] = dv[1 + m]; t.tree_branch_share[m] = dv[9 + m]; }
-    int rc = mvhdp_set_tuning(s->h, &t);
+    rc = mvhdp_set_tuning(s->h, &t);
     if (rc) throw_rt(env, s->h, rc, "mvhdp_set_tuning");
 }
 
@@ -764,7 +774,9 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbInit(JNIEn
     Doubles w(env, weights, JNI_ABORT);
     if (w.failed()) return;
     int rc = mvhdp_emb_init(s->h, &c, w.p, static_cast<uint64_t>(seed));
-    if (rc) { s->embR = 0; throw_rt(env, s->h, rc, "mvhdp_emb_init"); return; }
+    // a refused configuration (MVHDP_ERR_INVALID_ARG) is refused before the library touches the embedding it holds: that one, and its
+    // shape here, stand; any later failure has freed it
+    if (rc) { if (rc != MVHDP_ERR_INVALID_ARG) { s->embR = 0; s->embC = 0; s->embK = 0; } throw_rt(env, s->h, rc, "mvhdp_emb_init"); return; }
     s->embR = R; s->embC = c.num_columns; s->embK = c.with_topics ? s->K : 0;
 }
 

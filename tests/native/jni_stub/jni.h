@@ -1,7 +1,8 @@
-/* jni.h -- DECLARATION-ONLY STUB for type-checking mvtopicmodel_amd/java/mvhdp_jni.cpp in an image without a JDK
- * (tests/test_jni_shim.py compiles the shim with -fsyntax-only against it).  It declares the few JNI names the shim
- * uses, with the signatures of the JNI specification; it implements nothing, nothing links against it, and it is not
- * part of any build.  A real build uses $JAVA_HOME/include/jni.h. */
+/* jni.h -- DECLARATION-ONLY STUB of the few JNI names mvtopicmodel_amd/java/mvhdp_jni.cpp uses, with the signatures of the JNI
+ * specification, for an image without a JDK.  tests/test_jni_shim.py type-checks the shim against it (-fsyntax-only), and
+ * tests/jni_harness.py compiles the shim against it and LINKS it with tests/native/fake_jvm.cpp, which defines every JNIEnv member
+ * declared here: a test-side JVM the unmodified shim runs on.  A name added here needs its definition there.  It is not part of any
+ * build of the product; a real build uses $JAVA_HOME/include/jni.h. */
 #ifndef MVHDP_TEST_JNI_STUB_H
 #define MVHDP_TEST_JNI_STUB_H
 #include <stdint.h>
@@ -17,7 +18,7 @@ typedef _jlongArray* jlongArray; typedef _jdoubleArray* jdoubleArray; typedef _j
 typedef _jbyteArray* jbyteArray;
 struct _jfieldID; typedef _jfieldID* jfieldID;
 struct JNIEnv {
-    jclass FindClass(const char*); jint ThrowNew(jclass, const char*); jsize GetArrayLength(jarray);
+    jclass FindClass(const char*); jint ThrowNew(jclass, const char*); jboolean ExceptionCheck(); jsize GetArrayLength(jarray);
     jobject GetObjectArrayElement(jobjectArray, jsize); void DeleteLocalRef(jobject); jclass GetObjectClass(jobject);
     jfieldID GetFieldID(jclass, const char*, const char*);
     void SetLongField(jobject, jfieldID, jlong); void SetIntField(jobject, jfieldID, jint); void SetDoubleField(jobject, jfieldID, jdouble);

@@ -1,6 +1,8 @@
 """The Java layer of the embeddings (no JDK here, so by inspection; tests/test_jni_shim.py type-checks the whole shim): every mvhdp_emb_*
 entry point of include/mvhdp.h is reached from a JNI entry of mvtopicmodel_amd/java/mvhdp_jni.cpp, each of those has its native in
-NativeSampler.java, and every array an entry takes is checked against the handle's shape before the library sees it."""
+NativeSampler.java, and every array an entry takes is checked against the handle's shape before the library sees it.
+(tests/test_jni_fake_jvm.py now RUNS every one of those length checks, one element short and one long, against a stand-in library, and
+tests/test_gpu_jni.py runs the entries on a device: the regular expressions here stay as the check that needs no compiler.)"""
 import os
 import re
 

@@ -1,7 +1,9 @@
 """The JNI shim (mvtopicmodel_amd/java/mvhdp_jni.cpp) cannot be built here (no JDK).  What can be checked without one:
 it type-checks against the JNI signatures it uses (a declaration-only stub, -fsyntax-only: nothing is built or linked),
 it never opens a critical region (every mvhdp_* call may block), and every native method the Java class
-declares has its Java_..._n* entry in the shim and vice versa."""
+declares has its Java_..._n* entry in the shim and vice versa.
+(The shim is also built and run: tests/test_jni_fake_jvm.py compares the full signatures of the natives, the entries and the ctypes
+prototype table, which subsumes the name match here; the type check and the critical-region check stay what they are.)"""
 import os
 import re
 import shutil
