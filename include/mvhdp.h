@@ -282,6 +282,74 @@ int mvhdp_antoniak_draws(mvhdp_handle h, int32_t n, const int32_t* items /*[n]*/
  * len[m] of the last earlier entity of this handle that had it (zeros before the first). */
 int mvhdp_doc_topic_proportions(mvhdp_handle h, const double* view_weights /*[M]*/, int64_t d0, int64_t d1, double* out /*[d1-d0][K]*/);
 
+/* ---- after training: what SciTopicFlow does with a trained model (FLOW = MVTopicModel/SciTopicFlow.java, FLOW:246-260) ----
+ * saveTopicsPerDoc PTM:2821-2926 (the inferencer's printDocumentTopics INF:332-490) -> the thresholded, sorted topic list per entity;
+ * CalcEntityTopicDistributionsAndTrends FLOW:807-1083 -> those lists summed per author / project / venue / batch / corpus and normalised;
+ * calcSimilarities FLOW:1320-1532 and CalcTopicSimilarities FLOW:1084-1196 -> every pair of the resulting vectors compared. */
+
+/* PTM:2890-2926: the topic list of entities [d0, d1).  The proportions have exactly the bits of mvhdp_doc_topic_proportions (its
+ * missing-view carry-over included).  Per entity the topics are ordered as IDSorter.compareTo orders them (mallet-2.0.8 class file):
+ * weight descending, equal weights by DESCENDING topic id; the reference sets entry k of its IDSorter array to (k, weight) for every
+ * document (PTM:2890-2901), so nothing carries over between documents.  The list is cut at the first weight < threshold (PTM:2911) and
+ * at max entries (max < 0 or max > K: K, PTM:2867-2869).  Weights are unrounded (the (double) Math.round(w * 10000) / 10000 of PTM:2919 is
+ * the caller's, or mvhdp_entity_topic_distributions').  row_off[d - d0] .. row_off[d - d0 + 1] index topics / weights.
+ * Capacity: topics and weights NULL with cap = 0 returns *count (and row_off, unless NULL) only; more than cap entries:
+ * MVHDP_ERR_INVALID_ARG, *count set, the arrays untouched.  Preconditions as mvhdp_doc_topic_proportions. */
+int mvhdp_doc_topics_top(mvhdp_handle h, const double* view_weights /*[M]*/, int64_t d0, int64_t d1, double threshold, int32_t max,
+                         int64_t cap, int64_t* row_off /*[d1-d0+1]*/, int32_t* topics, double* weights, int64_t* count);
+/* FLOW:807-1083 on the lists above.  The flow stores floor(w * 10^4 + 0.5) / 10^4 of every kept weight (PTM:2919) and lets SQL sum them
+ * per group and divide by the group's total (FLOW:880-1010); an SQL engine's summation order is not reproducible, so THIS definition is
+ * ours: for group g, out[g][k] = sum over members[member_off[g] .. member_off[g+1]), in that order, of the rounded kept weight of topic k;
+ * the total is one chain over the members in that order and, within a member, its kept topics in ascending topic id; every sum is
+ * divided by the total and, unless round_digits is -1, rounded as floor(v * 10^digits + 0.5) / 10^digits (round_digits 0..15; the SQL
+ * uses 5).  Fixed order, no floating-point atomics: two calls give the same bits.  A group with total 0 (or no member) is a row of
+ * zeros.  members are entity ids of this handle, in any order, repeated across (or within) groups at will. */
+int mvhdp_entity_topic_distributions(mvhdp_handle h, const double* view_weights, double threshold, int32_t max, int32_t round_digits /*-1: none*/,
+                                     int64_t n_groups, const int64_t* member_off /*[n_groups+1]*/, const int64_t* members /*entity ids, may repeat across groups*/,
+                                     double* out /*[n_groups][K]*/);
+
+/* calcSimilarities FLOW:1320-1532 (threshold 0.15) / CalcTopicSimilarities FLOW:1084-1196 (0.3): all pairs i < j of the n rows of x with
+ * sim(i, j) > threshold -- strictly, as FLOW:1146,1462,1484 -- sorted by (i, j), sim unrounded (the flow's (double) Math.round(sim * 1000) /
+ * 1000, FLOW:1152,1467,1488, is the caller's).  An entry x[r][c] <= min_weight counts as 0 (the NormWeight > 0.03 of the SQL at FLOW:1341;
+ * -inf: none).  Entries are expected finite.
+ * Cosine metrics, bit for bit the reference's arithmetic (read from mallet-2.0.8's class files): dot = the unfused fp64 chain
+ * s = s + a_k * b_k over ascending k (SparseVector.dotProductInternal walks the first vector's locations in ascending index, dmul then
+ * dadd; an absent entry is an exact zero product, so the dense chain has the same bits; MatrixOps.dotProduct is the dense loop itself),
+ * |a| = Math.sqrt of the same chain of squares (SparseVector.twoNorm, MatrixOps.twoNorm), then dot / (|a| * |b|)
+ * (NormalizedDotProductMetric.distance = 1 - that; org.madgik.utils.Utils.cosineSimilarity :18-22), then for COS_FOLDED 1 - |1 - c|.
+ * FLOW:1144 takes max(cosine, 0) before its test; with threshold >= 0 that changes no decision and no emitted value.
+ * Two stages.  (a) Screen, on the matrix cores: rows normalised in fp64, stored as fp32, multiplied in 128 x 128 tiles (on and above the
+ * diagonal only) with v_mfma_f32_32x32x2_f32, an exact k-ordered fp32 fma chain; a pair is a candidate when
+ * screen > threshold - margin, margin(dim) = (dim + 4) * 2^-23: the normalised rows have sum |a_k b_k| <= 1, rounding the inputs to fp32
+ * moves the sum by at most 2 * 2^-24 of that and a chain of dim fp32 terms by at most dim * 2^-24; the margin is twice the sum of the
+ * two.  dim > 65536: MVHDP_ERR_UNSUPPORTED (the margin stays below 0.01).  (b) Exact: every candidate recomputed by the fp64 chain and
+ * tested.  The screen never decides a pair.  The bound holds where fp64 neither under- nor overflows: a row with a non-zero |entry|
+ * outside [2^-500, 2^500] is not screened at all -- each of its pairs is a candidate.  A row whose norm is 0, Inf or NaN never yields a
+ * pair (in Java NaN compares false and 0 is not > threshold >= 0) and is left out of both stages.
+ * MVHDP_SIM_JSD: Maths.jensenShannonDivergence (class file): m_k = (p_k + q_k) / 2, (KL(p, m) + KL(q, m)) / 2,
+ * KL(p, m) = (sum over ascending k with p_k != 0 of p_k * Math.log(p_k / m_k)) / Math.log(2), +inf when such an m_k is 0.  A plain fp64
+ * kernel, no screen; Math.log and the device's log may differ by an ulp, so values agree with Java to a few ulp per term, not bit for
+ * bit.  Rows of norm 0 / Inf / NaN are left out as above.
+ * What the reference does differently, and we do not follow: its JSD vectors are filled in SQL row-arrival order, not by topic id
+ * (FLOW:1422-1431: similarityVectors[cnt++]), so they are ill-defined -- ours are indexed by topic; its read loop never stores the last
+ * entity it reads (FLOW:1418-1433); its pair order is that of a HashMap's key set.
+ * Work proceeds in stripes of stripe_rows rows (0: 4096), each with a candidate buffer of candidate_capacity entries (0: 2^22); a stripe
+ * that overflows it is redone with a buffer of the size it asked for (stats.regrown counts those).
+ * i, j, sim NULL with cap = 0: *count only.  More than cap pairs: MVHDP_ERR_INVALID_ARG, *count set, i / j / sim untouched.  threshold must
+ * be finite and >= 0 (else MVHDP_ERR_INVALID_ARG).  The handle supplies device, stream and mvhdp_last_error; no model state is read. */
+typedef enum { MVHDP_SIM_COS_FOLDED = 0,  /* 1 - |1 - dot/(|a||b|)|   FLOW:1483, NormalizedDotProductMetric.distance */
+               MVHDP_SIM_COS        = 1,  /* dot/(|a||b|)             FLOW:1144, Utils.cosineSimilarity (MatrixOps) */
+               MVHDP_SIM_JSD        = 2   /* Maths.jensenShannonDivergence, log base 2   FLOW:1461 */ } mvhdp_sim_metric;
+typedef struct { int32_t metric; int32_t n, dim; const double* x /*[n][dim] host*/; double min_weight; double threshold;
+                 int32_t stripe_rows /*0: auto*/; int64_t candidate_capacity /*0: auto*/; } mvhdp_sim_args;
+typedef struct { int64_t pairs_screened /* matrix cells the first stage computes: 128 x 128 per launched tile (JSD: 16 x 16) */,
+                 candidates, emitted; int32_t stripes, regrown; double margin; } mvhdp_sim_stats;
+int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int64_t cap, int32_t* i, int32_t* j, double* sim,
+                        int64_t* count, mvhdp_sim_stats* stats /* or NULL */);
+/* Pure host function, no device: margin, stripes and pairs_screened of a cosine call of that shape (the other fields 0).
+ * MVHDP_ERR_INVALID_ARG for n < 0, dim < 1, stripe_rows < 0 or a NULL out; MVHDP_ERR_UNSUPPORTED for dim > 65536. */
+int mvhdp_sim_probe(int32_t n, int32_t dim, int32_t stripe_rows, mvhdp_sim_stats* out);
+
 /* ---- topic diagnostics: the step after training (FastQMVWVTopicModelDiagnostics, DIAG = MVTopicModel/FastQMVWVTopicModelDiagnostics.java;
  * SciTopicFlow builds it with N = 20 right after the save, whose saveExperiment / saveTopicsandExperiment call
  * calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230 from PTM:1370 / PTM:1507 and getSortedWords PTM:1792-1811 per view).

@@ -15,6 +15,7 @@ ABI_SYMBOLS = [
     "mvhdp_build_inference_trees", "mvhdp_init_assignments_from_trees",
     "mvhdp_get_counts", "mvhdp_set_counts", "mvhdp_get_tree", "mvhdp_get_doc_topic_hist",
     "mvhdp_get_count_histogram", "mvhdp_view_overlap_sums", "mvhdp_model_log_likelihood", "mvhdp_doc_topic_proportions",
+    "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
@@ -133,6 +134,19 @@ class EmbStatsC(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+SIM_COS_FOLDED, SIM_COS, SIM_JSD = 0, 1, 2          # mvhdp_sim_metric
+
+
+class SimArgsC(C.Structure):
+    _fields_ = [("metric", C.c_int32), ("n", C.c_int32), ("dim", C.c_int32), ("x", C.c_void_p), ("min_weight", C.c_double),
+                ("threshold", C.c_double), ("stripe_rows", C.c_int32), ("candidate_capacity", C.c_int64)]
+
+
+class SimStatsC(C.Structure):
+    _fields_ = [("pairs_screened", C.c_int64), ("candidates", C.c_int64), ("emitted", C.c_int64), ("stripes", C.c_int32),
+                ("regrown", C.c_int32), ("margin", C.c_double)]
+
+
 _lib = None
 _preloaded = []            # keeps the handles of the runtime libraries loaded on the library's behalf alive
 
@@ -241,6 +255,10 @@ def load_library():
     L.mvhdp_view_overlap_sums.argtypes = [vp, vp]
     L.mvhdp_model_log_likelihood.argtypes = [vp, vp]
     L.mvhdp_doc_topic_proportions.argtypes = [vp, vp, i64, i64, vp]
+    L.mvhdp_doc_topics_top.argtypes = [vp, vp, i64, i64, C.c_double, i32, i64, vp, vp, vp, C.POINTER(i64)]
+    L.mvhdp_entity_topic_distributions.argtypes = [vp, vp, C.c_double, i32, i32, i64, vp, vp, vp]
+    L.mvhdp_similar_pairs.argtypes = [vp, C.POINTER(SimArgsC), i64, vp, vp, vp, C.POINTER(i64), C.POINTER(SimStatsC)]
+    L.mvhdp_sim_probe.argtypes = [i32, i32, i32, C.POINTER(SimStatsC)]
     L.mvhdp_gamma_doc_statistics.argtypes = [vp, i32, C.c_double, u64, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mvhdp_dp_table_statistics.argtypes = [vp, i32, vp, i32, vp, u64, u32, vp, vp]
     L.mvhdp_antoniak_draws.argtypes = [vp, i32, vp, vp, u64, u32, vp]

@@ -1875,18 +1875,16 @@ extern "C" int mvhdp_view_overlap_sums(mvhdp_handle h, double* sums)
     return mvhdp_view_overlap_accumulate(h, sums);
 }
 
-extern "C" int mvhdp_doc_topic_proportions(mvhdp_handle h, const double* view_weights, int64_t d0, int64_t d1, double* out)
+// What the proportions need before their kernel runs: every view's corpus, the hyper-parameters, and per view the carry-over map of
+// PTM:2873-2886 (built once per corpus).  Shared with the thresholded lists and entity distributions of mvhdp_sim.hip.
+int mvhdp_doc_topic_prepare(mvhdp_ctx* h, DocTopicCarry& carry)
 {
-    CHECK_H(h);
     MvModel& mm = h->mm;
     int rc = require_corpus(h); if (rc) return rc;
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "doc_topic_proportions before set_hyper");
-    if (!view_weights || !out || d0 < 0 || d1 > mm.D || d0 > d1) FAIL(h, MVHDP_ERR_INVALID_ARG, "doc_topic_proportions: bad range or null buffer");
-    if (d1 == d0) return MVHDP_OK;
     HIPC(h, hipSetDevice(h->device));
-    DocTopicCarry carry{};
     for (int m = 0; m < mm.M; m++) {
-        if (!h->d_carry[m]) {                              // PTM:2873-2886: a missing view keeps the previous entity's counts
+        if (!h->d_carry[m] && mm.D > 0) {                  // PTM:2873-2886: a missing view keeps the previous entity's counts
             std::vector<int64_t> src((size_t)mm.D);
             int64_t last = -1;
             for (int64_t d = 0; d < mm.D; d++) {
@@ -1899,6 +1897,19 @@ extern "C" int mvhdp_doc_topic_proportions(mvhdp_handle h, const double* view_we
         }
         carry.src[m] = h->d_carry[m];
     }
+    return MVHDP_OK;
+}
+
+extern "C" int mvhdp_doc_topic_proportions(mvhdp_handle h, const double* view_weights, int64_t d0, int64_t d1, double* out)
+{
+    CHECK_H(h);
+    MvModel& mm = h->mm;
+    int rc = require_corpus(h); if (rc) return rc;
+    if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "doc_topic_proportions before set_hyper");
+    if (!view_weights || !out || d0 < 0 || d1 > mm.D || d0 > d1) FAIL(h, MVHDP_ERR_INVALID_ARG, "doc_topic_proportions: bad range or null buffer");
+    if (d1 == d0) return MVHDP_OK;
+    DocTopicCarry carry{};
+    rc = mvhdp_doc_topic_prepare(h, carry); if (rc) return rc;
     double *d_w = nullptr, *d_out = nullptr;
     const size_t n = (size_t)(d1 - d0) * mm.K;
     hipError_t e = hipMalloc(&d_w, (size_t)mm.M * sizeof(double));

@@ -202,6 +202,9 @@ int mvhdp_diag_model(mvhdp_ctx* h, int N, DiagModel& dm);
 int mvhdp_diag_docs(mvhdp_ctx* h, const DiagModel& dm, DiagAcc& acc);
 int mvhdp_diag_finish(mvhdp_ctx* h, const DiagModel& dm, const DiagAcc& acc, const mvhdp_diag_args* args, const mvhdp_diag_out* out);
 
+// mvhdp_doc_topic_proportions' preconditions and carry-over maps (mvhdp_api.hip), for the callers in mvhdp_sim.hip
+int mvhdp_doc_topic_prepare(mvhdp_ctx* h, DocTopicCarry& carry);
+
 // frees h->emb and its device buffers (mvhdp_emb.hip; release_device_resources calls it)
 void mvhdp_emb_free(mvhdp_ctx* h);
 // the walk-threshold search the coming sweep belongs to: the mix flavours keep their own

@@ -12,7 +12,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   EmbConfigC, EmbStatsC, GroupInfoC, HyperC, MvhdpError, SweepStatsC, TuningC, load_library)
+                   EmbConfigC, EmbStatsC, GroupInfoC, HyperC, MvhdpError, SimArgsC, SimStatsC, SweepStatsC, TuningC, load_library,
+                   SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
 SWEEP_REUSE_TREES = 0x1
 SWEEP_NO_APPLY = 0x2
@@ -105,6 +106,38 @@ class SweepStats:
     reserved: int = 0
     dbg: list = field(default=None, repr=False)
     trace: np.ndarray = field(default=None, repr=False)
+
+
+@dataclass
+class SimStats:
+    """mvhdp_sim_stats: what a similar_pairs call did.  pairs_screened: matrix cells of the first stage (128 x 128 per launched tile)."""
+    pairs_screened: int = 0
+    candidates: int = 0
+    emitted: int = 0
+    stripes: int = 0
+    regrown: int = 0
+    margin: float = 0.0
+
+
+SIM_METRICS = {"cos_folded": SIM_COS_FOLDED, "cos": SIM_COS, "jsd": SIM_JSD}
+
+
+def _sim_stats(c):
+    return SimStats(**{f: getattr(c, f) for f, _ in SimStatsC._fields_})
+
+
+def sim_probe(n, dim, stripe_rows=0):
+    """mvhdp_sim_probe: margin, stripes and pairs_screened of a cosine similar_pairs call of that shape.  No device."""
+    st = SimStatsC()
+    rc = load_library().mvhdp_sim_probe(int(n), int(dim), int(stripe_rows), C.byref(st))
+    if rc != 0:
+        raise MvhdpError(rc, "sim_probe: bad shape" if rc == -1 else "sim_probe: dim > 65536")
+    return _sim_stats(st)
+
+
+def round_similarity(sim):
+    """The flow's (double) Math.round(similarity * 1000) / 1000 (FLOW:1152,1467,1488) for the non-negative values it stores."""
+    return np.floor(np.asarray(sim, dtype=np.float64) * 1000 + 0.5) / 1000
 
 
 @dataclass
@@ -372,6 +405,69 @@ class NativeSampler:
         out = np.zeros((max(d1 - int(d0), 0), self.K), dtype=np.float64)
         self._ck(self.L.mvhdp_doc_topic_proportions(self.h, _ptr(w), int(d0), d1, _ptr(out)))
         return out
+
+    # -- after training: thresholded topic lists, entity distributions, all-pairs similarity (FLOW:246-260) --
+    def doc_topics_top(self, view_weights, threshold, max_topics=-1, d0=0, d1=None):
+        """PTM:2890-2926: (row_off [d1-d0+1], topics, weights) -- per entity the topics by weight descending (ties: larger topic id first),
+        cut at the first weight < threshold and at max_topics (< 0 or > K: K).  Weights unrounded."""
+        d0 = int(d0)
+        d1 = self.D if d1 is None else int(d1)
+        w = np.ascontiguousarray(view_weights, dtype=np.float64)
+        if w.shape != (self.M,):
+            raise ValueError("view_weights must be [M]")
+        cnt = C.c_int64()
+        off = np.zeros(max(d1 - d0, 0) + 1, dtype=np.int64)
+        self._ck(self.L.mvhdp_doc_topics_top(self.h, _ptr(w), d0, d1, float(threshold), int(max_topics), 0, _ptr(off), None, None, C.byref(cnt)))
+        n = cnt.value
+        topics = np.zeros(n, dtype=np.int32)
+        weights = np.zeros(n, dtype=np.float64)
+        if n:
+            self._ck(self.L.mvhdp_doc_topics_top(self.h, _ptr(w), d0, d1, float(threshold), int(max_topics), n, _ptr(off), _ptr(topics), _ptr(weights), C.byref(cnt)))
+        return off, topics, weights
+
+    def entity_topic_distributions(self, view_weights, threshold, groups, max_topics=-1, round_digits=5):
+        """FLOW:807-1083 as include/mvhdp.h defines it: groups is a list of entity-id lists (or (member_off, members)); [n_groups][K]."""
+        w = np.ascontiguousarray(view_weights, dtype=np.float64)
+        if w.shape != (self.M,):
+            raise ValueError("view_weights must be [M]")
+        if isinstance(groups, tuple):
+            moff = np.ascontiguousarray(groups[0], dtype=np.int64)
+            mem = np.ascontiguousarray(groups[1], dtype=np.int64)
+        else:
+            moff = np.zeros(len(groups) + 1, dtype=np.int64)
+            moff[1:] = np.cumsum([len(g) for g in groups])
+            mem = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.int64) for g in groups]) if len(groups) else [], dtype=np.int64)
+        if moff.ndim != 1 or len(moff) < 1 or len(mem) != int(moff[-1]):
+            raise ValueError("member_off / members shape mismatch")
+        ng = len(moff) - 1
+        out = np.zeros((ng, self.K), dtype=np.float64)
+        self._ck(self.L.mvhdp_entity_topic_distributions(self.h, _ptr(w), float(threshold), int(max_topics), int(round_digits), ng, _ptr(moff),
+                                                         _ptr(mem) if len(mem) else None, _ptr(out) if ng else None))
+        return out
+
+    def similar_pairs(self, x, metric, threshold, min_weight=-np.inf, stripe_rows=0, candidate_capacity=0, count_only=False):
+        """calcSimilarities FLOW:1320-1532 / CalcTopicSimilarities FLOW:1084-1196: all pairs i < j of the rows of x [n][dim] with
+        sim > threshold, sorted by (i, j): (i, j, sim, stats).  metric: "cos_folded" (1 - |1 - cos|, the entity similarities), "cos" (the
+        topic similarities) or "jsd", or the MVHDP_SIM_* value.  count_only: (count, stats)."""
+        x = np.ascontiguousarray(x, dtype=np.float64)
+        if x.ndim != 2:
+            raise ValueError("x must be [n][dim]")
+        a = SimArgsC(int(SIM_METRICS.get(metric, metric)), x.shape[0], x.shape[1], x.ctypes.data, float(min_weight), float(threshold),
+                     int(stripe_rows), int(candidate_capacity))
+        cnt, st = C.c_int64(), SimStatsC()
+        if count_only:
+            self._ck(self.L.mvhdp_similar_pairs(self.h, C.byref(a), 0, None, None, None, C.byref(cnt), C.byref(st)))
+            return cnt.value, _sim_stats(st)
+        cap = 1 << 20                                          # a first guess; a call that finds more says how many and is repeated once
+        while True:
+            i, j, sim = np.zeros(cap, np.int32), np.zeros(cap, np.int32), np.zeros(cap, np.float64)
+            rc = self.L.mvhdp_similar_pairs(self.h, C.byref(a), cap, _ptr(i), _ptr(j), _ptr(sim), C.byref(cnt), C.byref(st))
+            if rc == -1 and cnt.value > cap:
+                cap = cnt.value
+                continue
+            self._ck(rc)
+            n = cnt.value
+            return i[:n].copy(), j[:n].copy(), sim[:n].copy(), _sim_stats(st)
 
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
     def top_words(self, m, n):
