@@ -1,5 +1,5 @@
 // mvhdp_ctx.h — the state behind an mvhdp_handle and the internal interfaces shared by the host-side sources of libmvhdp.so
-// (mvhdp_api.hip: the C ABI of one handle; mvhdp_group.hip: document shards on several GPUs).  Not installed: include/mvhdp.h is the ABI.
+// (mvhdp_api.hip: the C ABI of one handle; mvhdp_enqueue.hip: its sweep; mvhdp_group.hip: document shards on several GPUs).  Not installed: include/mvhdp.h is the ABI.
 #pragma once
 #include "mvhdp_device.h"
 #include "../../include/mvhdp.h"
@@ -75,6 +75,11 @@ struct mvhdp_ctx {
     hipStream_t rf_stream = nullptr; hipEvent_t ev_rf_go = nullptr, ev_rf_done = nullptr;
     int live_tree_every = 1;                 // diagnostics (MVHDP_LIVE_TREE_EVERY): tree rebuilds of a live sweep at every n-th segment border only
     int gate_pct = 60;                       // overlapped live segments: the next segment's trees and kernels are enqueued when this share of the current one's queue is taken
+    struct Diag {                            // measurement switches of the environment, read at create like the rest
+        bool overlap_serial = false;         //   MVHDP_OVERLAP_SERIAL: overlapped segments, the same schedule on one stream
+        bool no_row_sample = false;          //   MVHDP_NO_ROW_SAMPLE: MVHDP_SL_NO_ROW_SAMPLE in every live-rows sweep
+        bool no_heavy_refresh = false;       //   MVHDP_NO_HEAVY_REFRESH: live-rows sweeps without heavy_refresh_kernel beside the samplers
+    } diag;
     bool delta16_used = false;               // MvModel::delta16 holds deltas of the last sweep (until the apply pass)
     int side_priority = 2;                   // side streams A and B at high priority (a hardware-queue pool of their own)
     hipStream_t side[PLAN_N_STREAMS]{};      // side streams of the wider kernel classes (created on first use; [0] unused: the handle's stream)
@@ -129,6 +134,7 @@ bool mvhdp_is_live(mvhdp_ctx* h);
 #define FAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
 
 enum { MVHDP_HEAVY_CAP = 8192 };             // heavy rows a live sweep keeps trees for (each holds 65535 tokens or more: beyond any corpus that fits a GPU)
+enum { MVHDP_REFRESH_BLOCKS = 16 };          // one-wave blocks of heavy_refresh_kernel, which keeps those trees current beside the samplers
 enum { MVHDP_TAIL_WORDS = 4 };               // int32 words allocated behind counts_len() in the counts and delta buffers ([0]: a group's status word)
 static int64_t counts_len(const mvhdp_ctx* h) { return h->mm.rowbase[h->mm.M] * h->mm.K + (int64_t)h->mm.M * h->mm.K; }
 
@@ -170,6 +176,13 @@ struct PendingSweep {
 };
 int mvhdp_sweep_begin(mvhdp_ctx* h, uint32_t sweep_idx, uint64_t seed, uint32_t flags, const double* p_override, const mvhdp_debug* dbg, PendingSweep& ps);
 int mvhdp_sweep_finish(mvhdp_ctx* h, PendingSweep& ps, mvhdp_sweep_stats* stats);
+// helpers of mvhdp_api.hip that the sweep (mvhdp_enqueue.hip) needs too, and the activation the sweep's births share with mvhdp_activate_births
+int require_corpus(mvhdp_ctx* h);
+int64_t compute_max_doc_tokens(mvhdp_ctx* h);
+int apply_activation(mvhdp_ctx* h, int32_t activated_topic, int32_t activated_modality);
+int activate_born(mvhdp_ctx* h, const std::vector<std::pair<int32_t, long long>>& born, SweepOutcome& oc);
+// a non-blocking stream; high_priority: at the greatest priority where the runtime has priorities (a hardware-queue pool of its own, mvhdp_plan.h), else an ordinary one
+hipError_t make_stream(hipStream_t* out, bool high_priority);
 // mvhdp_activate_births, and what it did: *n_born topics, the lowest-index one's key in *first_key (MVHDP_ACT_KEY_NONE if none)
 int mvhdp_activate_births_ex(mvhdp_ctx* h, const int64_t* keys, int* n_born, long long* first_key);
 // pieces of the statistics either side of the sweep that a group of document shards composes (mvhdp_api.hip; see there)

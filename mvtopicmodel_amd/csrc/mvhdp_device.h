@@ -1,5 +1,5 @@
 // mvhdp_device.h — kernel argument block and launch prototypes shared by the
-// HIP kernels (mvhdp_kernels.hip) and the C-ABI host side (mvhdp_api.hip).
+// HIP kernels (mvhdp_kernels.hip) and the C-ABI host side (mvhdp_api.hip, mvhdp_enqueue.hip).
 // gfx950 only: 64-lane wavefronts are assumed everywhere.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -82,6 +82,7 @@ struct MvModel {
 // SweepLaunch::flags, internal: a live sweep waits for its chunk-end atomics and invalidates the CU's L1 before it goes on (with one
 // resident wave the sweep is then the sequential algorithm: mvhdp_tuning.single_wave)
 #define MVHDP_SL_STRICT_LIVE 0x8000u
+#define MVHDP_SL_NO_ROW_SAMPLE 0x2000u       // measurement only (MVHDP_NO_ROW_SAMPLE): the live-rows tree branch keeps the token's topic instead of scanning the row
 // MvModel::heavy values: 0 = light and small, MVHDP_ROW_HEAVY = more than 65534 tokens (not in the mirror), MVHDP_ROW_BIG = light, but
 // more than 32767 tokens (mirror yes, 16-bit deltas no).  Written by build_trees_kernel from the row's sum.
 // MVHDP_ROW_SLIM: one more BIT beside that value -- every cell of the row was at most 4095 when its mirror was last written, and the row

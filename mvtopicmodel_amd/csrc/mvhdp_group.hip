@@ -841,11 +841,7 @@ static int async_buffers(mvhdp_group_ctx* g)
         GHIP(g, hipSetDevice(g->members[l]->device));
         // the collective of the asynchronous exchange runs BESIDE the next sweep: a high-priority stream has a hardware queue outside the
         // pool the sweep's streams share (mvhdp_plan.h) -- on a normal one it could land in the sweep kernels' queue and wait for them
-        int least = 0, greatest = 0;
-        st = nullptr;
-        if (hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && greatest < least &&
-            hipStreamCreateWithPriority(&st, hipStreamNonBlocking, greatest) != hipSuccess) { (void)hipGetLastError(); st = nullptr; }
-        if (!st) GHIP(g, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        GHIP(g, make_stream(&st, true));
         g->comm.push_back(st);
         GHIP(g, hipEventCreateWithFlags(&ev, hipEventDisableTiming)); g->ev_xfer.push_back(ev);
     }

@@ -311,7 +311,7 @@ hipError_t mvhdp_launch_build_trees_from_mirror(const MvModel& mm, bool write_fu
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// Overlapped segments (MVHDP_SWEEP_SEGMENT_OVERLAP, mvhdp_api.hip enqueue_overlapped): the updater's catch-up for one
+// Overlapped segments (MVHDP_SWEEP_SEGMENT_OVERLAP, mvhdp_enqueue.hip enqueue_overlapped): the updater's catch-up for one
 // segment runs BESIDE the sampling of the next.  The model is kept twice (counts, mirror, descent tables); this kernel
 // brings the copy that segment s + 2 will read up to date from the deltas of segments s - 1 and s:
 //     dst += dA (+ dB), dB = 0            (apply2_counts_kernel below; the trees stay those of the sweep start: a form that also rebuilt
@@ -542,9 +542,6 @@ __global__ __launch_bounds__(64) void heavy_refresh_kernel(MvModel mm, const int
     const int32_t* nk_all = mm.counts + nrows * K;
     const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
     const int n = min((int)__hip_atomic_load(&ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), heavy_cap);
-#ifdef MVHDP_REFRESH_PRINT
-    if (blockIdx.x == 0 && lane == 0) printf("[refresher] %d heavy rows\n", n);
-#endif
     for (int pass = 0; pass < 1000000; pass++) {
         for (int i = blockIdx.x; i < n; i += gridDim.x) {
             const int64_t row = heavy_list[i];
@@ -560,11 +557,6 @@ __global__ __launch_bounds__(64) void heavy_refresh_kernel(MvModel mm, const int
             }
             tree_from_leaves<true>(mm, row, t, lane, write_full);
         }
-#ifdef MVHDP_REFRESH_SLEEP_ONLY      /* experiment: idle waves that touch no memory, for 3 ms */
-        if (__builtin_amdgcn_s_memrealtime() - t0 > 300000ull) break;
-        __builtin_amdgcn_s_sleep(127);
-        continue;
-#endif
         if (n <= (int)blockIdx.x) break;                                      // (a block without a row of its own has nothing to do)
         if (__hip_atomic_load(&ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) break;
         if (__builtin_amdgcn_s_memrealtime() - t0 > 200000000ull) break;     // 2 s of the 100 MHz counter
@@ -573,7 +565,7 @@ __global__ __launch_bounds__(64) void heavy_refresh_kernel(MvModel mm, const int
 
 hipError_t mvhdp_launch_heavy_refresh(const MvModel& mm, const int32_t* heavy_list, const unsigned int* ctl, int heavy_cap, int blocks, hipStream_t s)
 {
-    hipLaunchKernelGGL(heavy_refresh_kernel, dim3(blocks), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, heavy_list, ctl, heavy_cap, getenv("MVHDP_REFRESH_FULL") != nullptr);
+    hipLaunchKernelGGL(heavy_refresh_kernel, dim3(blocks), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, heavy_list, ctl, heavy_cap, false);
     return hipGetLastError();
 }
 

@@ -5,7 +5,7 @@
 //                  which stream, with which walk thresholds, grids and LDS sizes
 //   WalkTuner      the clock-driven search of the chunk head's walk threshold: propose() before a sweep, observe() after
 //
-// mvhdp_sweep() = plan_sweep() -> enqueue (mvhdp_api.hip: launches only) -> finish (read-back, WalkTuner::observe).
+// mvhdp_sweep() = plan_sweep() -> enqueue (mvhdp_enqueue.hip: launches only) -> finish (read-back, WalkTuner::observe).
 // Both are reachable without a GPU through mvhdp_plan_probe / mvhdp_tuner_probe (include/mvhdp.h) so that the CPU tests
 // can feed them recorded inputs (tests/test_plan.py).
 #pragma once
@@ -360,7 +360,7 @@ static inline void plan_sweep(const PlanIn& in, const PlanTuning& tu, WalkTuner&
     // last entity are empty -- so that document shards of different sizes walk through the same number of exchanges)
     if ((int64_t)nseg > in.D && p.only_seg < 0) nseg = (int)std::max<int64_t>(1, in.D);
     p.nseg = nseg;
-    // two segments in flight (mvhdp_api.hip enqueue_overlapped): asked for (SEGMENT_OVERLAP), or a live sweep of several segments
+    // two segments in flight (mvhdp_enqueue.hip enqueue_overlapped): asked for (SEGMENT_OVERLAP), or a live sweep of several segments
     // whose borders need no host (no inactive topic waiting for its activation, no debug output)
     p.overlap = nseg > 1 && p.only_seg < 0 &&
                 ((flags & MVHDP_SWEEP_SEGMENT_OVERLAP) || (p.live && !want_rows && !tu.single_wave && tu.live_overlap != 0 && in.first_inactive < 0 && !in.debug));

@@ -348,7 +348,7 @@
 #ifdef MVHDP_TIMING
                             const unsigned long long t_rs0 = __builtin_amdgcn_s_memtime();
 #endif
-                            if (sl.flags & 0x2000u) znew = bcast_i(z_l, TOK_T);      // (0x2000: measurement only, MVHDP_NO_ROW_SAMPLE)
+                            if (sl.flags & MVHDP_SL_NO_ROW_SAMPLE) znew = bcast_i(z_l, TOK_T);      // (measurement only, MVHDP_NO_ROW_SAMPLE)
                             else
                             znew = uniform_i(row_sample_live<(NARROW != 0), LIVEROWS == 2>(rowq, spec_t, coef_s != nullptr, (const __attribute__((address_space(3))) float*)coef_s + m * Kp, mm.coef + (int64_t)m * Kp, smp_m, smS, rowp_t, K,
                                                                      bcast_f(u2f_l, TOK_T), bcast_f(root32_l, TOK_T), bsel_t, (LIVEROWS == 2 && bsel_t) ? mm.mass0[row] : 0.0f /* (a scalar load: the address is wave-uniform) */, lane, &t_rs1));

@@ -1,0 +1,115 @@
+"""What a handle says about its trees (mvhdp_trees_current) after every way of putting a sweep on the device, and that the handle is in
+an ordinary state afterwards: the plain deferred sweep that follows is the oracle's.  The sweep's host side (csrc/mvhdp_enqueue.hip) keeps
+have_trees / full_trees / delta_clean / delta_pending by hand along several paths; this pins what a caller can observe of them."""
+import numpy as np
+import pytest
+
+from mvtopicmodel_amd.native import (Hyper, SWEEP_LIVE, SWEEP_LIVE_SEGMENTS, SWEEP_NO_APPLY, SWEEP_REUSE_TREES, SWEEP_SEGMENT_APPLY,
+                                     SWEEP_SEGMENT_OVERLAP)
+from tests.helpers import assert_same_state, make_native, make_oracle, small_corpus
+from tests.test_gpu_live import _check_counts_are_counts_of_z
+from tests.test_gpu_segmented import oracle_overlapped_sweep, oracle_segmented_sweep
+
+pytestmark = pytest.mark.gpu
+
+# trees_current() after each call, in the order of the test: what this sequence returned when it was run on an MI355X against the library
+# of the commit before the sweep's host side moved into mvhdp_enqueue.hip (bd6a366).  Not reasoned out from the code under test.
+EXPECTED = [
+    ("sweep", False),
+    ("build_trees", True),
+    ("sweep REUSE_TREES", False),
+    ("sweep LIVE", False),
+    ("sweep LIVE, 3 segments, stored trees", False),
+    ("sweep LIVE | NO_APPLY", False),
+    ("apply_delta", False),
+    ("sweep SEGMENT_APPLY, 3 segments", False),
+    ("sweep SEGMENT_APPLY | SEGMENT_OVERLAP, 3 segments", False),
+    ("sweep_many deferred", False),
+    ("sweep_many LIVE", False),
+    ("sweep_many SEGMENT_APPLY | SEGMENT_OVERLAP", False),
+]
+
+
+def test_trees_current_and_the_next_deferred_sweep_after_every_kind_of_sweep():
+    """EXPECTED holds what a run of this very sequence against the parent commit's library returned.  After a deterministic call the
+    oracle has been driven through the same schedule and every integer agrees; a live sweep is racy by design, so it is held to the live
+    test's invariants and the oracle then takes over the sampler's assignments.  Either way one plain deferred sweep follows on both."""
+    from oracle.binding import SWEEP_REUSE_TREES as ORC_REUSE_TREES
+    K, V, seed = 24, [120], 8
+    c = small_corpus(K, V, 70, [18], 61)
+    hy = Hyper.defaults(K, V)
+    o = make_oracle(c, hy)
+    s = make_native(c, hy, [o.get_assignments(0)])
+    got = []
+    it = [0]
+
+    def idx(n=1):
+        it[0] += n
+        return it[0] - n
+
+    def note(what):
+        got.append((what, s.trees_current()))
+
+    def then_a_deferred_sweep(racy=False):
+        if racy:
+            _check_counts_are_counts_of_z(c, s, K)
+            o.set_assignments(0, s.get_assignments(0)); o.build_counts()
+        assert_same_state(o, s, 1)
+        i = idx()
+        so = o.sweep(i, seed)["stats"]; st = s.sweep(i, seed)
+        assert (st.tokens, st.changed) == (so["tokens"], so["changed"])
+        assert_same_state(o, s, 1)
+
+    i = idx(); o.sweep(i, seed); s.sweep(i, seed)
+    note("sweep"); then_a_deferred_sweep()
+
+    s.build_trees(); o.build_trees()
+    note("build_trees")
+    i = idx(); o.sweep(i, seed, flags=ORC_REUSE_TREES); s.sweep(i, seed, flags=SWEEP_REUSE_TREES)
+    note("sweep REUSE_TREES"); then_a_deferred_sweep()
+
+    st = s.sweep(idx(), seed, flags=SWEEP_LIVE)
+    assert st.tokens == c.total_tokens and st.aborted_docs == 0
+    note("sweep LIVE"); then_a_deferred_sweep(racy=True)
+
+    s.set_tuning(live_rows=0)                                    # stored trees rebuilt per segment: two segments in flight
+    st = s.sweep(idx(), seed, flags=SWEEP_LIVE | SWEEP_LIVE_SEGMENTS(3))
+    s.set_tuning(live_rows=-1)
+    assert st.tokens == c.total_tokens and st.aborted_docs == 0
+    assert st.new_mass_cnt + st.topic_doc_mass_cnt + st.word_ftree_mass_cnt == st.tokens
+    note("sweep LIVE, 3 segments, stored trees"); then_a_deferred_sweep(racy=True)
+
+    before = s.get_counts(0)
+    st = s.sweep(idx(), seed, flags=SWEEP_LIVE | SWEEP_NO_APPLY)
+    assert st.tokens == c.total_tokens
+    assert all(np.array_equal(a, b) for a, b in zip(s.get_counts(0), before))     # the snapshot again
+    note("sweep LIVE | NO_APPLY")
+    s.apply_delta(-1, -1)
+    note("apply_delta"); then_a_deferred_sweep(racy=True)
+
+    i = idx(); oracle_segmented_sweep(o, c, i, seed, 3); s.sweep(i, seed, flags=SWEEP_SEGMENT_APPLY | SWEEP_LIVE_SEGMENTS(3))
+    note("sweep SEGMENT_APPLY, 3 segments"); then_a_deferred_sweep()
+
+    ofl = SWEEP_SEGMENT_APPLY | SWEEP_SEGMENT_OVERLAP | SWEEP_LIVE_SEGMENTS(3)
+    i = idx(); oracle_overlapped_sweep(o, c, i, seed, 3); s.sweep(i, seed, flags=ofl)
+    note("sweep SEGMENT_APPLY | SEGMENT_OVERLAP, 3 segments"); then_a_deferred_sweep()
+
+    i = idx(3)
+    for j in range(3):
+        o.sweep(i + j, seed)
+    s.sweep_many(i, 3, seed)
+    note("sweep_many deferred"); then_a_deferred_sweep()
+
+    sts = s.sweep_many(idx(3), 3, seed, flags=SWEEP_LIVE)
+    assert all(st.tokens == c.total_tokens and st.aborted_docs == 0 for st in sts)
+    note("sweep_many LIVE"); then_a_deferred_sweep(racy=True)
+
+    i = idx(3)
+    for j in range(3):
+        oracle_overlapped_sweep(o, c, i + j, seed, 3)
+    s.sweep_many(i, 3, seed, flags=ofl)
+    note("sweep_many SEGMENT_APPLY | SEGMENT_OVERLAP"); then_a_deferred_sweep()
+
+    print("trees_current:", got)
+    assert got == EXPECTED
+    s.close()

@@ -172,9 +172,10 @@ def test_overlapped_segmented_sweep_bit_exact(nseg, force, mode, monkeypatch):
     s.close()
 
 
-def test_overlapped_segmented_sweep_small_shapes_oov_and_batches():
+def test_overlapped_segmented_sweep_small_shapes_oov_and_batches(monkeypatch):
     """One view, types outside the alphabet, unassigned tokens at the start (the mirror stays out while row totals can grow), more
-    segments than a kernel has waves' worth of entities, and the same sweeps as one mvhdp_sweep_many batch on a twin handle."""
+    segments than a kernel has waves' worth of entities, the same sweeps as one mvhdp_sweep_many batch on a twin handle, and once more
+    on a handle created under MVHDP_OVERLAP_SERIAL (read at create): the lag-two schedule on one stream is still the oracle's."""
     from mvtopicmodel_amd.native import SWEEP_SEGMENT_OVERLAP
     K, V = 24, [120]
     c = small_corpus(K, V, 70, [18], 61)
@@ -193,7 +194,13 @@ def test_overlapped_segmented_sweep_small_shapes_oov_and_batches():
     assert_same_state(o, b, 1)
     with pytest.raises(MvhdpError):
         a.sweep(5, 8, flags=SWEEP_SEGMENT_OVERLAP)                          # goes with SEGMENT_APPLY only
-    a.close(); b.close()
+    monkeypatch.setenv("MVHDP_OVERLAP_SERIAL", "1")
+    s1 = make_native(c, hy, z)
+    monkeypatch.delenv("MVHDP_OVERLAP_SERIAL")
+    for it in range(3):
+        s1.sweep(it, 8, flags=fl)
+    assert_same_state(o, s1, 1)
+    a.close(); b.close(); s1.close()
 
 
 def test_overlapped_segmented_sweep_refuses_inactive_topics():

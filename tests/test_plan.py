@@ -150,6 +150,10 @@ def test_forced_variants_flags_and_errors():
     assert (po.segments, po.live_rows) == (1, 1) and all(po.class_walk[c] for c in range(6) if po.class_used[c])
     po = probe(flags=SWEEP_LIVE, tuning=dict(live_rows=0))
     assert (po.segments, po.live_rows) == (4, 0)
+    po = probe(flags=SWEEP_LIVE, tuning=dict(live_rows=0, live_overlap=-1))                   # (what tests/test_gpu_live.py runs with rows = 0, nseg = 0)
+    assert (po.status, po.segments, po.live_rows) == (0, 4, 0)
+    po = probe(flags=SWEEP_LIVE | (3 << 16), tuning=dict(live_rows=0, live_overlap=-1))       # (what tests/test_gpu_live.py runs with rows = 0)
+    assert (po.status, po.segments, po.live_rows) == (0, 3, 0)
     assert probe(flags=SWEEP_LIVE | (3 << 16)).segments == 3 and probe(flags=SWEEP_LIVE | (3 << 16)).live_rows == 1
     assert probe(flags=SWEEP_LIVE, debug=1).live_rows == 0 and probe(flags=SWEEP_LIVE | SWEEP_REUSE_TREES, trees_current=1).live_rows == 0
     assert probe(K=2048, M=2, D=1000, mdt=5000, longer=(1000, 900, 800, 500, 100), flags=SWEEP_LIVE).live_rows == 0      # (the generic kernel can be reached)
