@@ -189,7 +189,7 @@ extern "C" int mvhdp_create(const mvhdp_config* cfg, mvhdp_handle* out)
     h->d_doc_counter = h->d_ctl + ST_COUNT + 1 + META_WORDS64;                       // one work-queue head per kernel class
     CREATE_HIP(hipHostMalloc((void**)&h->h_ctl, CTL_WORDS * sizeof(unsigned long long), hipHostMallocDefault));   // pinned: the read-back never blocks the host
     for (int c = 0; c < MVHDP_N_CLASSES; c++)
-        for (int f = 0; f < 3; f++) { h->regs.regs[c][f] = mvhdp_sweep_kernel_regs(c, f); h->regs.regs_mix[c][f] = mvhdp_sweep_kernel_regs(c, f ? f : 1, true); }
+        for (int f = 0; f < MVHDP_N_FLAVOURS; f++) { h->regs.regs[c][f] = mvhdp_sweep_kernel_regs(c, f); h->regs.regs_mix[c][f] = mvhdp_sweep_kernel_regs(c, f == MVHDP_FLAVOUR_PLAIN ? MVHDP_FLAVOUR_WALK : f, true); }
     read_environment(h);
     {
         // the 12-bit image of n_wk (mvhdp_slim.h): only where a plan can use it (38 MB at C4)

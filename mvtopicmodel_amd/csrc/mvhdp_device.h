@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "mvhdp_flavour.h"
 
 #define MVHDP_MAXM 8
 #define MVHDP_WALK_BINS 20                      /* walk thresholds are multiples of 1/MVHDP_WALK_BINS */
@@ -193,6 +194,7 @@ hipError_t mvhdp_launch_birth_table(const int32_t* births, const long long* birt
 hipError_t mvhdp_launch_live_helper(const MvModel& mm, int which, unsigned long long* stats, hipStream_t s);
 hipError_t mvhdp_launch_doc_topic_hist(const MvModel& mm, int m, int32_t* hist, int32_t hist_len,
                                        int32_t* doc_len_counts, int32_t len_len, hipStream_t s);
+// the generic sweep kernel (every flavour of it) may take this much dynamic LDS: asked once where a plan goes beyond 64 KiB
 hipError_t mvhdp_sweep_set_max_lds(size_t bytes);
 hipError_t mvhdp_launch_count_hist(const MvModel& mm, int m, int32_t* hist, int32_t len, hipStream_t s);
 hipError_t mvhdp_launch_view_overlap(const MvModel& mm, double* out, hipStream_t s);
@@ -221,11 +223,11 @@ struct ClassifyArgs {
 };
 hipError_t mvhdp_launch_classify(const MvModel& mm, const ClassifyArgs& ca, hipStream_t s);
 size_t mvhdp_sweep_fast_wave_bytes(int M, int S_cap, int rmax);
+// the register-resident variant of rmax slot rounds, in the flavour that sl, mm and debug ask for (mvhdp_flavour.h: one rule, one list
+// of the compiled kernels); hipErrorInvalidValue for a request no plan makes
 hipError_t mvhdp_launch_sweep_fast(const MvModel& mm, const SweepLaunch& sl, int rmax, int grid_blocks, bool debug, hipStream_t s);
-int mvhdp_sweep_fast_occupancy(int rmax, bool debug, bool walk, int block_threads, size_t lds_bytes);
-int mvhdp_sweep_generic_occupancy(bool debug, int block_threads, size_t lds_bytes);
-// VGPRs of the compiled sweep kernel of class c (0..4 register-resident, 5 generic); flavour 0: plain, 1: walk, 2: debug
-// mix: the flavours compiled with the useVectorsLambda mix (MvModel::mix), which a sweep launches when a mix is set
+// VGPRs of the compiled sweep kernel of class c (0..4 register-resident, 5 generic) in flavour MVHDP_FLAVOUR_PLAIN / _WALK / _DEBUG, on
+// the 32-bit table; mix: of the flavours compiled with the useVectorsLambda mix (MvModel::mix), which a sweep launches when a mix is set
 int mvhdp_sweep_kernel_regs(int cls, int flavour, bool mix = false);
 int mvhdp_sweep_generic_regs(bool debug, bool mix = false);
 

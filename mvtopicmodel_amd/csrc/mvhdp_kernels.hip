@@ -264,50 +264,39 @@ __global__ __launch_bounds__(64) void build_trees_kernel(MvModel mm, bool infere
     }
 }
 
-#define LAUNCH_TREES(TB, ...) do { if (mm.mix) hipLaunchKernelGGL((build_trees_kernel<TB, true>), __VA_ARGS__); \
-                                   else hipLaunchKernelGGL((build_trees_kernel<TB, false>), __VA_ARGS__); } while (0)
+// build_trees_kernel<TB, MIX> for TB rows in flight a block and a handle with or without a mix, over the rows [row_begin, row_end):
+// a block per row (a tenth of that many blocks looping over rows was measured 6 % slower)
+static hipError_t launch_trees(int tb, const MvModel& mm, bool inference_leaves, bool write_full, int64_t row_begin, int64_t row_end,
+                               bool apply_first, unsigned long long* negatives, bool from_mirror, hipStream_t s, bool only_heavy = false)
+{
+    const int64_t nrows = row_end - row_begin;
+    if (nrows <= 0) return hipSuccess;
+    const bool mix = mm.mix != nullptr;
+    const void* f = tb == 1 ? (mix ? (const void*)build_trees_kernel<1, true> : (const void*)build_trees_kernel<1, false>)
+                  : tb == 4 ? (mix ? (const void*)build_trees_kernel<4, true> : (const void*)build_trees_kernel<4, false>)
+                  : tb == 8 ? (mix ? (const void*)build_trees_kernel<8, true> : (const void*)build_trees_kernel<8, false>) : nullptr;
+    if (!f) return hipErrorInvalidValue;
+    void* args[] = {(void*)&mm, &inference_leaves, &write_full, &row_begin, &row_end, &apply_first, &negatives, &from_mirror, &only_heavy};
+    (void)hipLaunchKernel(f, dim3((unsigned)(nrows < 65536 ? nrows : 65536)), dim3(64), args, (size_t)2 * mm.K * sizeof(double), s);
+    return hipGetLastError();
+}
 
+// TB: 1 beside the samplers, else 8 for K > 512 and 4 below
 hipError_t mvhdp_launch_build_trees(const MvModel& mm, bool inference_leaves, bool write_full, hipStream_t s, bool beside_samplers)
 {
     if (!beside_samplers) return mvhdp_launch_build_trees_rows(mm, inference_leaves, write_full, 0, mm.rowbase[mm.M], false, nullptr, s);
-    const int64_t nrows = mm.rowbase[mm.M];
-    if (nrows <= 0) return hipSuccess;
-    int grid = (int)(nrows < 65536 ? nrows : 65536);
-    LAUNCH_TREES(1, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
-                       (int64_t)0, nrows, false, (unsigned long long*)nullptr, false);
-    return hipGetLastError();
+    return launch_trees(1, mm, inference_leaves, write_full, 0, mm.rowbase[mm.M], false, nullptr, false, s);
 }
 
 hipError_t mvhdp_launch_build_trees_rows(const MvModel& mm, bool inference_leaves, bool write_full, int64_t row_begin, int64_t row_end,
                                          bool apply_first, unsigned long long* negatives, hipStream_t s)
 {
-    int64_t nrows = row_end - row_begin;
-    if (nrows <= 0) return hipSuccess;
-    int grid = (int)(nrows < 65536 ? nrows : 65536);          // (a block per row: a tenth of that many blocks looping over rows is 6 % slower, gpurun_out/r5c)
-    if (mm.K > 512)
-        LAUNCH_TREES(8, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
-                           row_begin, row_end, apply_first, negatives, false);
-    else
-        LAUNCH_TREES(4, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, inference_leaves, write_full,
-                           row_begin, row_end, apply_first, negatives, false);
-    return hipGetLastError();
+    return launch_trees(mm.K > 512 ? 8 : 4, mm, inference_leaves, write_full, row_begin, row_end, apply_first, negatives, false, s);
 }
 
 hipError_t mvhdp_launch_build_trees_from_mirror(const MvModel& mm, bool write_full, hipStream_t s, bool beside_samplers)
 {
-    const int64_t nrows = mm.rowbase[mm.M];
-    if (nrows <= 0) return hipSuccess;
-    int grid = (int)(nrows < 65536 ? nrows : 65536);
-    if (beside_samplers)
-        LAUNCH_TREES(1, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
-                           (int64_t)0, nrows, false, (unsigned long long*)nullptr, true);
-    else if (mm.K > 512)
-        LAUNCH_TREES(8, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
-                           (int64_t)0, nrows, false, (unsigned long long*)nullptr, true);
-    else
-        LAUNCH_TREES(4, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, write_full,
-                           (int64_t)0, nrows, false, (unsigned long long*)nullptr, true);
-    return hipGetLastError();
+    return launch_trees(beside_samplers ? 1 : mm.K > 512 ? 8 : 4, mm, false, write_full, 0, mm.rowbase[mm.M], false, nullptr, true, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -587,9 +576,7 @@ hipError_t mvhdp_launch_live_rows_prepare(const MvModel& mm, bool from_mirror, b
     else hipLaunchKernelGGL(live_rows_prepare_kernel<4>, dim3(grid), dim3(64), 0, s, mm, from_mirror, heavy_list, heavy_ctl, heavy_cap, batch_cells);
     // the HEAVY words (more than 65534 tokens: a few hundred rows at most) keep a stored tree, built from the 32-bit table where their
     // counts live; the flags are those the pass above has just written (or kept)
-    if (with_heavy_trees)
-        LAUNCH_TREES(4, dim3(grid), dim3(64), (size_t)2 * mm.K * sizeof(double), s, mm, false, false, (int64_t)0, nrows, false,
-                           (unsigned long long*)nullptr, true, true);
+    if (with_heavy_trees) return launch_trees(4, mm, false, false, 0, nrows, false, nullptr, true, s, true);
     return hipGetLastError();
 }
 
@@ -1112,51 +1099,33 @@ __global__ __launch_bounds__(256) void sweep_kernel(MvModel mm, SweepLaunch sl)
     }
 }
 
+static const void* generic_sweep_kernel(bool debug, bool mix)
+{
+    return mix ? (debug ? (const void*)sweep_kernel<true, true> : (const void*)sweep_kernel<false, true>)
+               : (debug ? (const void*)sweep_kernel<true, false> : (const void*)sweep_kernel<false, false>);
+}
+
 hipError_t mvhdp_sweep_set_max_lds(size_t bytes)
 {
-    for (const void* f : {(const void*)sweep_kernel<false>, (const void*)sweep_kernel<true>, (const void*)sweep_kernel<false, true>, (const void*)sweep_kernel<true, true>}) {
-        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+    for (int i = 0; i < 4; i++) {
+        hipError_t e = hipFuncSetAttribute(generic_sweep_kernel(i & 1, i >> 1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-int mvhdp_sweep_generic_occupancy(bool debug, int block_threads, size_t lds_bytes)
-{
-    hipFuncAttributes a;
-    const void* f = debug ? (const void*)sweep_kernel<true> : (const void*)sweep_kernel<false>;
-    if (hipFuncGetAttributes(&a, f) != hipSuccess) return 1;
-    int regs = (a.numRegs + 7) / 8 * 8;
-    int waves_simd = regs > 0 ? 512 / regs : 8;
-    if (waves_simd > 8) waves_simd = 8;
-    if (waves_simd < 1) waves_simd = 1;
-    int wpb = block_threads / 64;
-    int b = waves_simd * 4 / wpb;
-    int by_lds = (int)((160 * 1024) / (lds_bytes > 0 ? lds_bytes : 1));
-    if (by_lds < b) b = by_lds;
-    if (32 / wpb < b) b = 32 / wpb;
-    return b < 1 ? 1 : b;
-}
-
 int mvhdp_sweep_generic_regs(bool debug, bool mix)
 {
     hipFuncAttributes a;
-    const void* f = mix ? (debug ? (const void*)sweep_kernel<true, true> : (const void*)sweep_kernel<false, true>)
-                        : (debug ? (const void*)sweep_kernel<true> : (const void*)sweep_kernel<false>);
-    if (hipFuncGetAttributes(&a, f) != hipSuccess) return 128;
+    if (hipFuncGetAttributes(&a, generic_sweep_kernel(debug, mix)) != hipSuccess) return 128;
     return a.numRegs;
 }
 
 hipError_t mvhdp_launch_sweep(const MvModel& mm, const SweepLaunch& sl, int grid_blocks, bool debug, hipStream_t s)
 {
-    size_t lds = sl.block_shared_bytes + (size_t)sl.waves_per_block * sl.wave_bytes;
-    dim3 block(64 * sl.waves_per_block);
-    if (mm.mix) {
-        if (debug) hipLaunchKernelGGL((sweep_kernel<true, true>), dim3(grid_blocks), block, lds, s, mm, sl);
-        else       hipLaunchKernelGGL((sweep_kernel<false, true>), dim3(grid_blocks), block, lds, s, mm, sl);
-    }
-    else if (debug) hipLaunchKernelGGL(sweep_kernel<true>, dim3(grid_blocks), block, lds, s, mm, sl);
-    else            hipLaunchKernelGGL(sweep_kernel<false>, dim3(grid_blocks), block, lds, s, mm, sl);
+    const size_t lds = sl.block_shared_bytes + (size_t)sl.waves_per_block * sl.wave_bytes;
+    void* args[] = {(void*)&mm, (void*)&sl};
+    (void)hipLaunchKernel(generic_sweep_kernel(debug, mm.mix != nullptr), dim3(grid_blocks), dim3(64 * sl.waves_per_block), args, lds, s);
     return hipGetLastError();
 }
 

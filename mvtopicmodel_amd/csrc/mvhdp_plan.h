@@ -34,9 +34,9 @@
 enum { PLAN_STREAM_MAIN = 0, PLAN_STREAM_A = 1, PLAN_STREAM_B = 2, PLAN_STREAM_C = 3, PLAN_STREAM_D = 4, PLAN_N_STREAMS = 5 };
 
 // Register counts of the compiled kernels (hipFuncGetAttributes at mvhdp_create; typical values in the CPU tests):
-// [class 0..4][0: plain, 1: walk flavour, 2: debug], [5][0/2]: the generic kernel
-// regs_mix: the same for the flavours compiled with the useVectorsLambda mix ([.][0] unused: a sweep with a mix always takes the walk flavour)
-struct PlanRegs { int regs[MVHDP_N_CLASSES][3]; int regs_mix[MVHDP_N_CLASSES][3]; };
+// [class 0..4][MVHDP_FLAVOUR_PLAIN / _WALK / _DEBUG], [5][_PLAIN / _DEBUG]: the generic kernel
+// regs_mix: the same for the flavours compiled with the useVectorsLambda mix ([.][_PLAIN] unused: a sweep with a mix always takes the walk flavour)
+struct PlanRegs { int regs[MVHDP_N_CLASSES][MVHDP_N_FLAVOURS]; int regs_mix[MVHDP_N_CLASSES][MVHDP_N_FLAVOURS]; };
 
 struct PlanIn {
     int K = 0, M = 0;
@@ -65,6 +65,7 @@ struct PlanIn {
 // K = 200 (3 against 4) is left on the mirror: its sweep is bound by latency, not by lines (C3, profiles/slim_rows.md) -- `level` 2 takes
 // the table wherever the lines are fewer (measurements), 0 never.
 enum { PLAN_SLIM_MAX_CLASS = 2 };               // the 1-, 2- and 4-round variants have the flavour; the 8- and 16-round ones sit at their register limit and stay on the mirror
+static_assert((1 << PLAN_SLIM_MAX_CLASS) == MVHDP_SLIM_MAX_ROUNDS, "the plan asks for the 12-bit flavour where mvhdp_flavour.h lists one");
 static inline bool plan_slim_table(int K, int max_types, int level) { return mvhdp_slim_pays(K, max_types, level) != 0; }   // (one definition: mvhdp_slim.h, which the CPU test compiles)
 
 
@@ -429,8 +430,8 @@ static inline void plan_sweep(const PlanIn& in, const PlanTuning& tu, WalkTuner&
         g.lds = p.block_shared_bytes + (size_t)g.wpb * g.wave_bytes;
         if (g.lds > in.max_lds) return false;
         // (the grids of the mix flavours from THEIR register counts)
-        const int (*rg)[3] = in.vectors_mix ? in.regs.regs_mix : in.regs.regs;
-        const int regs = is_fast ? rg[c][in.debug ? 2 : (walk ? 1 : 0)] : rg[5][in.debug ? 2 : 0];
+        const int (*rg)[MVHDP_N_FLAVOURS] = in.vectors_mix ? in.regs.regs_mix : in.regs.regs;
+        const int regs = is_fast ? rg[c][in.debug ? MVHDP_FLAVOUR_DEBUG : (walk ? MVHDP_FLAVOUR_WALK : MVHDP_FLAVOUR_PLAIN)] : rg[5][in.debug ? MVHDP_FLAVOUR_DEBUG : MVHDP_FLAVOUR_PLAIN];
         const int bpc = plan_blocks_per_cu(regs, 64 * g.wpb, g.lds);
         const int64_t need = (in.D + (int64_t)g.wpb * MVHDP_DOC_BATCH - 1) / ((int64_t)g.wpb * MVHDP_DOC_BATCH);
         // (two segments in flight: one block per CU stays free for the updater's kernels and the next segment's first blocks)

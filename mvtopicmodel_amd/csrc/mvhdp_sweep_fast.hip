@@ -71,6 +71,18 @@ size_t mvhdp_sweep_fast_wave_bytes(int M, int S_cap, int rmax)
 #ifndef MVHDP_LB8
 #define MVHDP_LB8 1          // 3 waves/SIMD (168 VGPRs) spills 100 B/lane and is 13 % slower on C5 than 2 waves at 199
 #endif
+// ... and which of them an instantiation of sweep_fast_kernel is compiled with
+static constexpr int fast_launch_bound(int rmax, bool walk, bool roomy, int liverows, bool mix)
+{
+    if (mix && rmax <= 2) return MVHDP_LB_MIX;
+    switch (rmax) {
+    case 1: return liverows ? MVHDP_LB_ROWS : walk ? MVHDP_LB1W : MVHDP_LB1;
+    case 2: return roomy ? MVHDP_LB2_ROOMY : liverows ? MVHDP_LB_ROWS : MVHDP_LB2;
+    case 4: return MVHDP_LB4;
+    case 8: return MVHDP_LB8;
+    default: return MVHDP_LB16;
+    }
+}
 // WALK: the flavour with the thresholded tree walk of the chunk head (SweepLaunch::walk_theta), the walk on demand in the token
 // loop and the per-view branch statistics the threshold search feeds on.  Without it every token is walked up front and nothing
 // is counted: where the best threshold is 0 (C2, C3) that code is 2-5 % faster for not carrying the rest.
@@ -313,7 +325,7 @@ __device__ __forceinline__ int row_sample_live(rowq_t q0, bool have_q0, bool in_
 // 2-round variants are compiled for 6 waves per SIMD (80 registers) instead of 7: each slot brings two registers for its mix value and two for
 // the one in flight (MVHDP_LB_MIX; 7 waves with the spills that takes: the same at C4, 3 % slower at C3, profiles/vectors_mix.md).
 template <int RMAX, bool DEBUG, bool WALK, int NARROW, bool ROOMY = false, int LIVEROWS = 0, bool MIX = false>
-__global__ __launch_bounds__(256, ((MIX && RMAX <= 2) ? MVHDP_LB_MIX : RMAX == 8 ? MVHDP_LB8 : (RMAX == 4 ? MVHDP_LB4 : (RMAX == 2 ? (ROOMY ? MVHDP_LB2_ROOMY : (LIVEROWS ? MVHDP_LB_ROWS : MVHDP_LB2)) : (RMAX == 1 ? (LIVEROWS ? MVHDP_LB_ROWS : WALK ? MVHDP_LB1W : MVHDP_LB1) : MVHDP_LB16))))) void sweep_fast_kernel(MvModel mm, SweepLaunch sl)
+__global__ __launch_bounds__(256, fast_launch_bound(RMAX, WALK, ROOMY, LIVEROWS, MIX)) void sweep_fast_kernel(MvModel mm, SweepLaunch sl)
 {
     static_assert(!MIX || (WALK && LIVEROWS == 0 && !ROOMY), "the mix flavours: walk flavour, stored trees");
     static_assert(NARROW != 2 || (WALK && !DEBUG && LIVEROWS == 0 && !MIX), "the 12-bit image: deferred sweeps of the walk flavour only");
@@ -932,161 +944,42 @@ __global__ __launch_bounds__(256, ((MIX && RMAX <= 2) ? MVHDP_LB_MIX : RMAX == 8
 #undef sn_get
 #undef sn_set
 
-// The 12-bit flavour (NARROW = 2) is compiled for the 1-, 2- and 4-round variants; the 8- and 16-round variants sit at their register
-// limit and stay on the mirror (the plan knows: PLAN_SLIM_MAX_CLASS)
-#define MVHDP_SLIM_RMAX 4
-// debug launches always take the WALK flavour (one instantiation fewer per variant; a threshold of 0 walks every token)
-static bool roomy_build(int rmax, int K) { return rmax == 2 && K >= 512; }
-// live-rows flavour with the two-batch shortcut: a row of the 16-bit mirror in exactly two register batches of 512 cells (the roomy 2-round
-// build, which exists for K >= 512 only, is always that flavour: the shortcut checks the batch count at run time as well)
-static bool two_batch_rows(int K) { return K > 512 && K <= 1024; }
+// The instantiations that exist -- mvhdp_flavour.h lists them, once -- each with its key; what a launch and a register query look up
+struct FastKernel { FastFlavour key; const void* fn; };
+#define FAST_KERNEL_ROW(R, D, W, N, RO, L, MX) {{R, D, W, N, RO, L, MX}, (const void*)sweep_fast_kernel<R, D, W, N, RO, L, MX>},
+static const FastKernel fast_kernels[] = { MVHDP_FAST_FLAVOURS(FAST_KERNEL_ROW) };
+#undef FAST_KERNEL_ROW
 
-// the mix flavours (MvModel::mix set): always the walk flavour (a threshold of 0 walks every token), no ROOMY build of their own
-template <int RMAX>
-static const void* fast_kernel_ptr_mix(bool debug, bool narrow)
+// the kernel of a request; null: a request no plan makes, or (an internal error) a flavour the rule names and the list does not hold
+static const void* fast_kernel(const FastRequest& q)
 {
-    if (debug) return (const void*)sweep_fast_kernel<RMAX, true, true, false, false, 0, true>;
-    return narrow ? (const void*)sweep_fast_kernel<RMAX, false, true, true, false, 0, true> : (const void*)sweep_fast_kernel<RMAX, false, true, false, false, 0, true>;
-}
-
-template <int RMAX>
-static const void* fast_kernel_ptr(bool debug, bool walk, bool narrow, int K = 0, bool live_rows = false, bool slim = false)
-{
-    if (live_rows && !debug) {
-        if constexpr (RMAX == 2) { if (narrow && roomy_build(RMAX, K)) return (const void*)sweep_fast_kernel<2, false, true, true, true, 2>; }
-        if (narrow && two_batch_rows(K)) return (const void*)sweep_fast_kernel<RMAX, false, true, true, false, 2>;
-        return narrow ? (const void*)sweep_fast_kernel<RMAX, false, true, true, false, 1> : (const void*)sweep_fast_kernel<RMAX, false, true, false, false, 1>;
-    }
-    if (narrow && walk && !debug) {
-        if constexpr (RMAX <= MVHDP_SLIM_RMAX) {
-            if (slim) {
-                if constexpr (RMAX == 2) { if (roomy_build(RMAX, K)) return (const void*)sweep_fast_kernel<2, false, true, 2, true>; }
-                return (const void*)sweep_fast_kernel<RMAX, false, true, 2>;
-            }
-        }
-        if constexpr (RMAX == 2) { if (roomy_build(RMAX, K)) return (const void*)sweep_fast_kernel<2, false, true, true, true>; }
-        return (const void*)sweep_fast_kernel<RMAX, false, true, true>;
-    }
-    return debug ? (const void*)sweep_fast_kernel<RMAX, true, true, false>
-                 : walk ? (const void*)sweep_fast_kernel<RMAX, false, true, false> : (const void*)sweep_fast_kernel<RMAX, false, false, false>;
-}
-
-template <int RMAX>
-static hipError_t launch_fast(const MvModel& mm, const SweepLaunch& sl, int grid_blocks, bool debug, hipStream_t s)
-{
-    size_t lds = sl.block_shared_bytes + (size_t)sl.waves_per_block * sl.wave_bytes;
-    dim3 block(64 * sl.waves_per_block);
-    const bool narrow = sl.narrow && sl.walk && !debug;
-    const bool rows = sl.live_rows && sl.walk && !debug;
-    const bool slim = narrow && sl.narrow == 2;
-    if (slim && (RMAX > MVHDP_SLIM_RMAX || rows || sl.live16 || mm.mix || !mm.counts12)) return hipErrorInvalidValue;   // (the plan asks for it where it exists)
-    if (mm.mix) {
-        if (rows || !sl.walk) return hipErrorInvalidValue;                 // (the plan gives a sweep with a mix stored trees and the walk flavour)
-        if (lds > 65536) {
-            hipError_t e = hipFuncSetAttribute(fast_kernel_ptr_mix<RMAX>(debug, narrow), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-        }
-        if (debug)       hipLaunchKernelGGL((sweep_fast_kernel<RMAX, true, true, false, false, 0, true>), dim3(grid_blocks), block, lds, s, mm, sl);
-        else if (narrow) hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, true, false, 0, true>), dim3(grid_blocks), block, lds, s, mm, sl);
-        else             hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, false, false, 0, true>), dim3(grid_blocks), block, lds, s, mm, sl);
-        return hipGetLastError();
-    }
-    if (lds > 65536) {
-        hipError_t e = hipFuncSetAttribute(fast_kernel_ptr<RMAX>(debug, sl.walk != 0, narrow, mm.K, rows, slim), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    if (debug)        hipLaunchKernelGGL((sweep_fast_kernel<RMAX, true, true, false>), dim3(grid_blocks), block, lds, s, mm, sl);
-    else if (rows) {
-        if (narrow && roomy_build(RMAX, mm.K)) { if constexpr (RMAX == 2) hipLaunchKernelGGL((sweep_fast_kernel<2, false, true, true, true, 2>), dim3(grid_blocks), block, lds, s, mm, sl); }
-        else if (narrow && two_batch_rows(mm.K)) hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, true, false, 2>), dim3(grid_blocks), block, lds, s, mm, sl);
-        else if (narrow) hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, true, false, 1>), dim3(grid_blocks), block, lds, s, mm, sl);
-        else             hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, false, false, 1>), dim3(grid_blocks), block, lds, s, mm, sl);
-    }
-    else if (slim) {
-        if constexpr (RMAX <= MVHDP_SLIM_RMAX) {
-            if (roomy_build(RMAX, mm.K)) { if constexpr (RMAX == 2) hipLaunchKernelGGL((sweep_fast_kernel<2, false, true, 2, true>), dim3(grid_blocks), block, lds, s, mm, sl); }
-            else hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, 2>), dim3(grid_blocks), block, lds, s, mm, sl);
-        }
-    }
-    else if (narrow && roomy_build(RMAX, mm.K)) {
-        // (the plan sized the grid for the 72-register build: the seventh block of a CU waits for a free slot and finds the queue empty)
-        if constexpr (RMAX == 2) hipLaunchKernelGGL((sweep_fast_kernel<2, false, true, true, true>), dim3(grid_blocks), block, lds, s, mm, sl);
-    }
-    else if (narrow)  hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, true>), dim3(grid_blocks), block, lds, s, mm, sl);
-    else if (sl.walk) hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, true, false>), dim3(grid_blocks), block, lds, s, mm, sl);
-    else              hipLaunchKernelGGL((sweep_fast_kernel<RMAX, false, false, false>), dim3(grid_blocks), block, lds, s, mm, sl);
-    return hipGetLastError();
+    FastFlavour f;
+    if (!mvhdp_fast_resolve(q, &f)) return nullptr;
+    for (const FastKernel& k : fast_kernels) if (k.key == f) return k.fn;
+    return nullptr;
 }
 
 hipError_t mvhdp_launch_sweep_fast(const MvModel& mm, const SweepLaunch& sl, int rmax, int grid_blocks, bool debug, hipStream_t s)
 {
-    switch (rmax) {
-    case 1: return launch_fast<1>(mm, sl, grid_blocks, debug, s);
-    case 2: return launch_fast<2>(mm, sl, grid_blocks, debug, s);
-    case 3:
-    case 4: return launch_fast<4>(mm, sl, grid_blocks, debug, s);
-    case 8: return launch_fast<8>(mm, sl, grid_blocks, debug, s);
-    case 16: return launch_fast<16>(mm, sl, grid_blocks, debug, s);
-    default: return hipErrorInvalidValue;
+    const void* f = fast_kernel({rmax, mm.K, debug, sl.walk != 0, sl.narrow, sl.live_rows != 0, sl.live16 != 0, mm.mix != nullptr, mm.counts12 != nullptr});
+    if (!f) return hipErrorInvalidValue;
+    const size_t lds = sl.block_shared_bytes + (size_t)sl.waves_per_block * sl.wave_bytes;
+    if (lds > 65536) {
+        hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return e;
     }
-}
-
-// Resident blocks per CU from the kernel's own register count and LDS need (the occupancy API
-// mis-reports both directions for these kernels; an over-estimate only queues blocks, an
-// under-estimate idles SIMDs).
-static int blocks_per_cu_from(const void* func, int threads, size_t lds)
-{
-    hipFuncAttributes a;
-    if (hipFuncGetAttributes(&a, func) != hipSuccess) return 1;
-    int regs = (a.numRegs + 7) / 8 * 8;
-    int waves_simd = regs > 0 ? 512 / regs : 8;
-    if (waves_simd > 8) waves_simd = 8;
-    if (waves_simd < 1) waves_simd = 1;
-    int wpb = threads / 64;
-    int by_regs = waves_simd * 4 / wpb;
-    int by_lds = (int)((160 * 1024) / (lds > 0 ? lds : 1));
-    int by_waves = 32 / wpb;
-    int b = by_regs < by_lds ? by_regs : by_lds;
-    if (by_waves < b) b = by_waves;
-    return b < 1 ? 1 : b;
-}
-
-template <int RMAX>
-static int occ_fast(bool debug, bool walk, int threads, size_t lds)
-{
-    return blocks_per_cu_from(fast_kernel_ptr<RMAX>(debug, walk, false), threads, lds);
-}
-
-int mvhdp_sweep_fast_occupancy(int rmax, bool debug, bool walk, int block_threads, size_t lds_bytes)
-{
-    switch (rmax) {
-    case 1: return occ_fast<1>(debug, walk, block_threads, lds_bytes);
-    case 2: return occ_fast<2>(debug, walk, block_threads, lds_bytes);
-    case 3:
-    case 4: return occ_fast<4>(debug, walk, block_threads, lds_bytes);
-    case 8: return occ_fast<8>(debug, walk, block_threads, lds_bytes);
-    case 16: return occ_fast<16>(debug, walk, block_threads, lds_bytes);
-    default: return 0;
-    }
-}
-
-template <int RMAX>
-static int regs_fast(int flavour, bool mix)
-{
-    hipFuncAttributes a;
-    const void* f = mix ? fast_kernel_ptr_mix<RMAX>(flavour == 2, false) : fast_kernel_ptr<RMAX>(flavour == 2, flavour >= 1, false);
-    if (hipFuncGetAttributes(&a, f) != hipSuccess) return 128;
-    return a.numRegs;
+    // (a roomy build runs in the grid the plan sized for the 72-register one: the seventh block of a CU waits for a free slot and finds the queue empty)
+    void* args[] = {(void*)&mm, (void*)&sl};
+    (void)hipLaunchKernel(f, dim3(grid_blocks), dim3(64 * sl.waves_per_block), args, lds, s);
+    return hipGetLastError();
 }
 
 int mvhdp_sweep_kernel_regs(int cls, int flavour, bool mix)
 {
-    switch (cls) {
-    case 0: return regs_fast<1>(flavour, mix);
-    case 1: return regs_fast<2>(flavour, mix);
-    case 2: return regs_fast<4>(flavour, mix);
-    case 3: return regs_fast<8>(flavour, mix);
-    case 4: return regs_fast<16>(flavour, mix);
-    default: return mvhdp_sweep_generic_regs(flavour == 2, mix);
-    }
+    if (cls < 0 || cls > 4) return mvhdp_sweep_generic_regs(flavour == MVHDP_FLAVOUR_DEBUG, mix);
+    // the build on the 32-bit table: what the plan sizes every flavour's grid from (a sweep with a mix always takes the walk flavour)
+    const void* f = fast_kernel({1 << cls, 0, flavour == MVHDP_FLAVOUR_DEBUG, flavour >= MVHDP_FLAVOUR_WALK || mix, 0, false, false, mix, false});
+    hipFuncAttributes a;
+    if (!f || hipFuncGetAttributes(&a, f) != hipSuccess) return 128;
+    return a.numRegs;
 }

@@ -147,6 +147,25 @@ def test_live16_with_heavy_and_light_rows(force, monkeypatch):
     s.close()
 
 
+def test_live_rows_on_the_32_bit_table_in_the_widest_variant(monkeypatch):
+    """MVHDP_LIVE16 = 0 under a forced 16-round variant (K beyond 512, entities of more than 512 tokens): the live-rows flavour that scans
+    the rows of the 32-bit table, in the widest variant."""
+    monkeypatch.setenv("MVHDP_LIVE16", "0")
+    monkeypatch.setenv("MVHDP_FORCE_RMAX", "16")
+    from tests.test_gpu_parity import wide_corpus
+    c = wide_corpus()
+    hy = Hyper.defaults(c.K, c.V)
+    o = make_oracle(c, hy)
+    s = make_native(c, hy, [o.get_assignments(m) for m in range(c.M)])
+    for it in range(2):
+        st = s.sweep(it, 77, flags=SWEEP_LIVE)
+        assert st.tokens == c.total_tokens and st.aborted_docs == 0 and st.oov_skipped == 0
+        assert st.new_mass_cnt + st.topic_doc_mass_cnt + st.word_ftree_mass_cnt == st.tokens
+        assert 0 < st.changed <= st.tokens
+        _check_counts_are_counts_of_z(c, s, c.K)
+    s.close()
+
+
 def test_live_flag_errors():
     K, V = 10, [50]
     c = small_corpus(K, V, 20, [8], 35)

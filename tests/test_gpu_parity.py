@@ -429,6 +429,37 @@ def test_inactive_topic_activation_across_kernel_classes(mode, force, monkeypatc
     s.close()
 
 
+def wide_corpus():
+    """K beyond 512 and entities of more than 512 tokens: what a forced 8- or 16-round primary variant needs to be the one that runs"""
+    K, V = 600, [2000, 60]
+    rng = np.random.RandomState(9)
+    lens0 = np.array([700, 1100, 40, 300, 560] + [25] * 12, dtype=np.int64)
+    lens1 = rng.randint(0, 9, len(lens0)).astype(np.int64)
+    off = [np.concatenate([[0], np.cumsum(l)]) for l in (lens0, lens1)]
+    from mvtopicmodel_amd.synth import Corpus
+    return Corpus(K, V, off, [rng.randint(0, V[m], off[m][-1]).astype(np.int32) for m in range(2)])
+
+
+@pytest.mark.parametrize("force,what", [("8", "plain"), ("16", "walk"), ("16", "debug")])
+def test_wide_variants_on_the_32_bit_table(force, what, monkeypatch):
+    """Rows of K >= 256 are gathered from the 16-bit mirror, so the flavours of the 8- and 16-round variants that read the 32-bit table run
+    only with the mirror switched off (set_tuning(narrow=0)): the plain one (no view gets a walk threshold -- alpha = 5 sends three
+    tokens in four to the tree branch, and a view is steered only below 0.35 -- so every sweep after the first, which measures, runs it),
+    the walk flavour under a fixed threshold, the debug one.  Deferred sweeps: every integer is the oracle's."""
+    monkeypatch.setenv("MVHDP_FORCE_RMAX", force)
+    c = wide_corpus()
+    hy = Hyper.defaults(c.K, c.V, alpha=5.0 if what == "plain" else 0.1)
+    o = make_oracle(c, hy)
+    s = make_native(c, hy, [o.get_assignments(m) for m in range(c.M)])
+    s.set_tuning(narrow=0, **(dict(walk_fixed=1, walk_theta=[0.3, 0.3]) if what == "walk" else {}))
+    for it in range(3):
+        ro = o.sweep(it, 17)
+        rs = s.sweep(it, 17, want_dbg=(what == "debug"))
+        assert (rs.tokens, rs.changed) == (ro["stats"]["tokens"], ro["stats"]["changed"])
+        assert_same_state(o, s, c.M)
+    s.close()
+
+
 def test_no_entities_and_a_view_without_tokens():
     from mvtopicmodel_amd import NativeSampler
     from mvtopicmodel_amd.synth import Corpus

@@ -116,6 +116,8 @@ def test_every_register_variant_forced(name, R, lam):
         sweeps_against_ref(case, case.hy, case.z0, lam, tuning=dict(force_primary=R), n=2, debug=debug)
     # ... and under the sequential sum, where that variant's debug doubles and traces are the restatement's bit for bit
     sweeps_against_ref(case, case.hy, case.z0, lam, flags=SWEEP_EXACT_CHAIN, tuning=dict(force_primary=R), n=1, debug=True)
+    # ... and with the mirror switched off: the variant's mix flavour on the 32-bit table
+    sweeps_against_ref(case, case.hy, case.z0, lam, tuning=dict(force_primary=R, narrow=0), n=1, debug=False)
 
 
 @pytest.mark.parametrize("narrow", [-1, 0])
