@@ -310,7 +310,6 @@ extern "C" int mvhdp_set_corpus(mvhdp_handle h, int32_t m, int64_t D, const int6
     HIPC(h, hipMalloc(&h->d_z[m], nb));
     if (N > 0) HIPC(h, hipMemcpy(h->d_tok[m], tokens, (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
     HIPC(h, hipMemset(h->d_z[m], 0xff, nb));               // UNASSIGNED_TOPIC (-1), PTM:63
-    h->unassigned[m] = N > 0;
     h->h_doc_off[m].assign(doc_off, doc_off + D + 1);
     h->N[m] = N;
     h->have_corpus[m] = true;
@@ -321,13 +320,12 @@ extern "C" int mvhdp_set_corpus(mvhdp_handle h, int32_t m, int64_t D, const int6
     if (h->d_nslots) { hipFree(h->d_nslots); h->d_nslots = nullptr; }
     mm.nslots = nullptr;
     for (auto& c : h->d_carry) if (c) { hipFree(c); c = nullptr; }
-    h->nslots_valid = false;
     mm.D = D;
     mm.doc_off[m] = (const int64_t*)h->d_doc_off[m];
     mm.tok[m] = (const int32_t*)h->d_tok[m];
     mm.z[m] = (int32_t*)h->d_z[m];
     if (mm.p) { hipFree(mm.p); mm.p = nullptr; }
-    h->have_counts = false; h->have_trees = false;
+    h->st.corpus_replaced(m, N > 0);
     return MVHDP_OK;
 }
 
@@ -352,11 +350,9 @@ extern "C" int mvhdp_set_assignments(mvhdp_handle h, int32_t m, const int32_t* z
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, hipStreamSynchronize(h->stream));
     if (h->N[m] > 0) HIPC(h, hipMemcpy(h->d_z[m], z, (size_t)h->N[m] * sizeof(int32_t), hipMemcpyHostToDevice));
-    h->unassigned[m] = any_unassigned;
-    h->nslots_valid = false;
     // the counts no longer describe these assignments: a sampling sweep is refused until build_counts / set_counts /
     // counts_written says they do again (a frozen sweep, whose counts are a trained model's by design, is not)
-    if (h->have_counts) h->counts_stale = true;
+    h->st.assignments_replaced(m, any_unassigned);
     return MVHDP_OK;
 }
 
@@ -417,7 +413,7 @@ extern "C" int mvhdp_set_hyper(mvhdp_handle h, const mvhdp_hyper* hy)
     HIPC(h, hipMemcpy(h->d_alpha, h->h_alpha.data(), (size_t)M * (K + 1) * sizeof(double), hipMemcpyHostToDevice));
     HIPC(h, hipMemcpy(h->d_inactive, h->h_inactive.data(), (size_t)K, hipMemcpyHostToDevice));
     h->have_hyper = true;
-    h->have_trees = false;
+    h->st.trees_outdated();
     return MVHDP_OK;
 }
 
@@ -436,30 +432,30 @@ extern "C" int mvhdp_build_counts(mvhdp_handle h)
     int rc = require_corpus(h); if (rc) return rc;
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, mvhdp_launch_build_counts(h->mm, h->N, h->stream));
-    if (h->delta_pending) {
+    if (h->st.delta_pending()) {
         // a NO_APPLY sweep's deltas were never applied: z already holds its assignments, so the recount above includes
         // them -- drop the deltas instead of leaving them to be added on top
         HIPC(h, hipMemsetAsync(h->mm.delta, 0, (size_t)counts_len(h) * sizeof(int32_t), h->stream));
-        h->delta_pending = false; h->delta_clean = true;
+        h->st.delta_zeroed();
     }
-    if (h->delta16_used) {
+    if (h->st.delta16_used()) {
         // 16-bit delta cells of a sweep that never reached its apply pass (it failed: the recount is how a host recovers): back to the bias
         HIPC(h, hipMemsetD16Async(h->mm.delta16, (unsigned short)0x8000, (size_t)(h->mm.rowbase[h->mm.M] * h->mm.K), h->stream));
-        h->delta16_used = false;
+        h->st.delta16_rebiased();
     }
     HIPC(h, hipStreamSynchronize(h->stream));
-    h->have_counts = true; h->have_trees = false; h->counts_stale = false;
+    h->st.counts_rebuilt();
     return MVHDP_OK;
 }
 
-// The trees are current (have_trees) but the last sweep refreshed only the descent table: write the FTree.tree
-// arrays as well, from the same counts and hyper-parameters (nothing has changed them since, or have_trees were false).
+// The trees are current (trees_current) but the last sweep refreshed only the descent table: write the FTree.tree
+// arrays as well, from the same counts and hyper-parameters (nothing has changed them since, or trees_current were false).
 static int ensure_full_trees(mvhdp_ctx* h)
 {
-    if (!h->have_trees || h->full_trees) return MVHDP_OK;
-    HIPC(h, mvhdp_launch_build_trees(h->mm, h->trees_inference, true, h->stream));
+    if (!h->st.trees_current() || h->st.full_trees()) return MVHDP_OK;
+    HIPC(h, mvhdp_launch_build_trees(h->mm, h->st.trees_inference(), true, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
-    h->full_trees = true;
+    h->st.full_trees_written();
     return MVHDP_OK;
 }
 
@@ -467,11 +463,11 @@ extern "C" int mvhdp_build_trees(mvhdp_handle h)
 {
     CHECK_H(h);
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "build_trees before set_hyper");
-    if (!h->have_counts) FAIL(h, MVHDP_ERR_STATE, "build_trees before build_counts/set_counts");
+    if (!h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "build_trees before build_counts/set_counts");
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, mvhdp_launch_build_trees(h->mm, false, true, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
-    h->have_trees = true; h->full_trees = true; h->trees_inference = false;
+    h->st.trees_built(true, false);
     return MVHDP_OK;
 }
 
@@ -479,11 +475,11 @@ extern "C" int mvhdp_build_inference_trees(mvhdp_handle h)
 {
     CHECK_H(h);
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "build_inference_trees before set_hyper");
-    if (!h->have_counts) FAIL(h, MVHDP_ERR_STATE, "build_inference_trees before build_counts/set_counts");
+    if (!h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "build_inference_trees before build_counts/set_counts");
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, mvhdp_launch_build_trees(h->mm, true, true, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
-    h->have_trees = true; h->full_trees = true; h->trees_inference = true;
+    h->st.trees_built(true, true);
     return MVHDP_OK;
 }
 
@@ -491,13 +487,11 @@ extern "C" int mvhdp_init_assignments_from_trees(mvhdp_handle h, uint64_t seed)
 {
     CHECK_H(h);
     int rc = require_corpus(h); if (rc) return rc;
-    if (!h->have_trees) FAIL(h, MVHDP_ERR_STATE, "init_assignments_from_trees before build_trees/build_inference_trees");
+    if (!h->st.trees_current()) FAIL(h, MVHDP_ERR_STATE, "init_assignments_from_trees before build_trees/build_inference_trees");
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, mvhdp_launch_init_from_trees(h->mm, (uint32_t)seed, (uint32_t)(seed >> 32), h->stream));     // reads the descent table only
     HIPC(h, hipStreamSynchronize(h->stream));
-    for (int m = 0; m < h->mm.M; m++) h->unassigned[m] = false;                                              // (every token got a topic, INF:169-199)
-    h->nslots_valid = false;
-    if (h->have_counts) h->counts_stale = true;
+    h->st.assignments_replaced(-1, false);                                                                   // (every token got a topic, INF:169-199)
     return MVHDP_OK;
 }
 
@@ -524,7 +518,7 @@ extern "C" int mvhdp_set_counts(mvhdp_handle h, int32_t m, const int32_t* n_wk, 
     const int K = mm.K;
     if (n_wk) HIPC(h, hipMemcpy(mm.counts + mm.rowbase[m] * K, n_wk, (size_t)mm.V[m] * K * sizeof(int32_t), hipMemcpyHostToDevice));
     if (n_k) HIPC(h, hipMemcpy(mm.counts + mm.rowbase[mm.M] * K + (int64_t)m * K, n_k, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice));
-    h->have_counts = true; h->have_trees = false; h->counts_stale = false;
+    h->st.counts_rebuilt();
     return MVHDP_OK;
 }
 
@@ -533,7 +527,7 @@ extern "C" int mvhdp_get_tree(mvhdp_handle h, int32_t m, int32_t type, double* t
     CHECK_H(h);
     MvModel& mm = h->mm;
     if (m < 0 || m >= mm.M || type < 0 || type >= mm.V[m] || !tree) FAIL(h, MVHDP_ERR_INVALID_ARG, "get_tree: bad argument");
-    if (!h->have_trees) FAIL(h, MVHDP_ERR_STATE, "get_tree before build_trees");
+    if (!h->st.trees_current()) FAIL(h, MVHDP_ERR_STATE, "get_tree before build_trees");
     HIPC(h, hipSetDevice(h->device));
     { int rc2 = ensure_full_trees(h); if (rc2) return rc2; }
     HIPC(h, hipStreamSynchronize(h->stream));
@@ -627,8 +621,8 @@ int mvhdp_activate_births_ex(mvhdp_ctx* h, const int64_t* keys, int* n_born, lon
     if (n_born) *n_born = 0;
     if (first_key) *first_key = LLONG_MAX;
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "activate_births before set_hyper");
-    if (h->rows_applied >= 0) FAIL(h, MVHDP_ERR_STATE, "activate_births inside an mvhdp_apply_delta_begin bracket (call mvhdp_apply_delta_end first)");
-    if (h->delta_pending) FAIL(h, MVHDP_ERR_STATE, "activate_births: the NO_APPLY sweep's deltas have not been applied (mvhdp_apply_delta first)");
+    if (h->st.bracket_open()) FAIL(h, MVHDP_ERR_STATE, "activate_births inside an mvhdp_apply_delta_begin bracket (call mvhdp_apply_delta_end first)");
+    if (h->st.delta_pending()) FAIL(h, MVHDP_ERR_STATE, "activate_births: the NO_APPLY sweep's deltas have not been applied (mvhdp_apply_delta first)");
     std::vector<long long> tab((size_t)K);
     HIPC(h, hipSetDevice(h->device));
     if (keys) std::copy(keys, keys + K, tab.begin());
@@ -679,14 +673,12 @@ extern "C" int mvhdp_apply_delta(mvhdp_handle h, int32_t activated_topic, int32_
     MvModel& mm = h->mm;
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, hipMemsetAsync(h->d_stats + ST_NEGATIVE, 0, sizeof(unsigned long long), h->stream));
-    HIPC(h, mvhdp_launch_apply_delta(mm, h->d_stats, h->stream, h->delta16_used));
-    h->delta16_used = false;
+    HIPC(h, mvhdp_launch_apply_delta(mm, h->d_stats, h->stream, h->st.delta16_used()));
+    h->st.delta16_rebiased();
     unsigned long long neg = 0;
     HIPC(h, hipMemcpyAsync(&neg, h->d_stats + ST_NEGATIVE, sizeof neg, hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
-    h->have_trees = false;
-    h->delta_clean = true;                                       // apply_delta_kernel zeroes what it adds
-    h->delta_pending = false;
+    h->st.delta_applied();                                       // apply_delta_kernel zeroes what it adds
     { int rc = apply_activation(h, activated_topic, activated_modality); if (rc) return rc; }
     if (neg) FAIL(h, MVHDP_ERR_NEGATIVE_COUNT, "a topic count went below zero (UPD:202-215)");
     return MVHDP_OK;
@@ -696,12 +688,11 @@ extern "C" int mvhdp_apply_delta(mvhdp_handle h, int32_t activated_topic, int32_
 extern "C" int mvhdp_apply_delta_begin(mvhdp_handle h)
 {
     CHECK_H(h);
-    if (!h->have_hyper || !h->have_counts) FAIL(h, MVHDP_ERR_STATE, "apply_delta_begin before set_hyper / counts");
+    if (!h->have_hyper || !h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "apply_delta_begin before set_hyper / counts");
     HIPC(h, hipSetDevice(h->device));
     HIPC(h, hipMemsetAsync(h->d_stats + ST_NEGATIVE, 0, sizeof(unsigned long long), h->stream));
     HIPC(h, mvhdp_launch_apply_nk(h->mm, h->d_stats + ST_NEGATIVE, h->stream));
-    h->rows_applied = 0;
-    h->have_trees = false;
+    h->st.bracket_begun();
     return MVHDP_OK;
 }
 
@@ -709,11 +700,11 @@ extern "C" int mvhdp_apply_delta_rows(mvhdp_handle h, int64_t row_begin, int64_t
 {
     CHECK_H(h);
     const int64_t nrows = h->mm.rowbase[h->mm.M];
-    if (h->rows_applied < 0) FAIL(h, MVHDP_ERR_STATE, "apply_delta_rows outside an apply_delta_begin / apply_delta_end bracket");
+    if (!h->st.bracket_open()) FAIL(h, MVHDP_ERR_STATE, "apply_delta_rows outside an apply_delta_begin / apply_delta_end bracket");
     if (row_begin < 0 || row_end > nrows || row_begin > row_end) FAIL(h, MVHDP_ERR_INVALID_ARG, "apply_delta_rows: bad row range");
     HIPC(h, hipSetDevice(h->device));
-    HIPC(h, mvhdp_launch_build_trees_rows(h->mm, false, h->last_need_full, row_begin, row_end, true, h->d_stats + ST_NEGATIVE, h->stream));
-    h->rows_applied += row_end - row_begin;
+    HIPC(h, mvhdp_launch_build_trees_rows(h->mm, false, h->st.last_need_full(), row_begin, row_end, true, h->d_stats + ST_NEGATIVE, h->stream));
+    h->st.bracket_rows(row_end - row_begin);
     return MVHDP_OK;
 }
 
@@ -721,17 +712,16 @@ extern "C" int mvhdp_apply_delta_end(mvhdp_handle h, int32_t activated_topic, in
 {
     CHECK_H(h);
     const int64_t nrows = h->mm.rowbase[h->mm.M];
-    if (h->rows_applied != nrows) { h->rows_applied = -1; FAIL(h, MVHDP_ERR_STATE, "apply_delta_end: the row ranges applied do not cover every row exactly once"); }
-    h->rows_applied = -1;
+    if (!h->st.bracket_closed(nrows)) FAIL(h, MVHDP_ERR_STATE, "apply_delta_end: the row ranges applied do not cover every row exactly once");
     HIPC(h, hipSetDevice(h->device));
     unsigned long long neg = 0;
     HIPC(h, hipMemcpyAsync(&neg, h->d_stats + ST_NEGATIVE, sizeof neg, hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
-    h->delta_clean = true; h->delta_pending = false;
+    h->st.delta_zeroed();
     // the trees were rebuilt from the updated counts row by row: current, unless an activation now changes alpha
-    h->have_trees = true; h->full_trees = h->last_need_full; h->trees_inference = false;
+    h->st.trees_built(h->st.last_need_full(), false);
     if (activated_topic >= 0) {
-        h->have_trees = false;
+        h->st.trees_outdated();
         int rc = apply_activation(h, activated_topic, activated_modality);
         if (rc) return rc;
     }
@@ -742,7 +732,7 @@ extern "C" int mvhdp_apply_delta_end(mvhdp_handle h, int32_t activated_topic, in
 extern "C" int mvhdp_trees_current(mvhdp_handle h)
 {
     CHECK_H(h);
-    return h->have_trees ? 1 : 0;
+    return h->st.trees_current() ? 1 : 0;
 }
 
 // ---- tuning: what a host may pin, what the library has learnt (so that a document shard, a resumed chain or another handle on
@@ -874,7 +864,7 @@ extern "C" int mvhdp_device_buffer(mvhdp_handle h, mvhdp_buffer which, void** de
 extern "C" int mvhdp_counts_written(mvhdp_handle h)
 {
     CHECK_H(h);
-    h->have_counts = true; h->have_trees = false; h->counts_stale = false;
+    h->st.counts_rebuilt();
     return MVHDP_OK;
 }
 
@@ -898,7 +888,7 @@ extern "C" int mvhdp_get_count_histogram(mvhdp_handle h, int32_t m, int32_t* his
     CHECK_H(h);
     MvModel& mm = h->mm;
     if (m < 0 || m >= mm.M || !hist || len < 1) FAIL(h, MVHDP_ERR_INVALID_ARG, "get_count_histogram: bad argument");
-    if (!h->have_counts) FAIL(h, MVHDP_ERR_STATE, "get_count_histogram before build_counts/set_counts");
+    if (!h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "get_count_histogram before build_counts/set_counts");
     HIPC(h, hipSetDevice(h->device));
     int32_t* d = nullptr;
     HIPC(h, hipMalloc(&d, (size_t)len * sizeof(int32_t)));
@@ -1103,7 +1093,7 @@ int mvhdp_ll_doc_accumulate(mvhdp_ctx* h, int m, double* ll, int64_t* cnt)
 int mvhdp_ll_model_finish(mvhdp_ctx* h, int m, double ll, int64_t modalityCnt, double* out)
 {
     MvModel& mm = h->mm;
-    if (!h->have_hyper || !h->have_counts) FAIL(h, MVHDP_ERR_STATE, "model_log_likelihood before set_hyper/build_counts");
+    if (!h->have_hyper || !h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "model_log_likelihood before set_hyper/build_counts");
     if (m < 0 || m >= mm.M || !out) FAIL(h, MVHDP_ERR_INVALID_ARG, "model_log_likelihood: bad view");
     const int M = mm.M, K = mm.K;
     ll += modalityCnt * log_gamma_stirling_host((double)mm.gamma[m] * mm.alpha_sum[m]);           // PTM:3373
@@ -1144,7 +1134,7 @@ extern "C" int mvhdp_model_log_likelihood(mvhdp_handle h, double* out)
     CHECK_H(h);
     if (!out) FAIL(h, MVHDP_ERR_INVALID_ARG, "model_log_likelihood: null");
     int rc = require_corpus(h); if (rc) return rc;
-    if (!h->have_hyper || !h->have_counts) FAIL(h, MVHDP_ERR_STATE, "model_log_likelihood before set_hyper/build_counts");
+    if (!h->have_hyper || !h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "model_log_likelihood before set_hyper/build_counts");
     for (int m = 0; m < h->mm.M; m++) {
         double ll = 0;
         int64_t cnt = 0;

@@ -4,6 +4,7 @@
 #include "mvhdp_device.h"
 #include "../../include/mvhdp.h"
 #include "mvhdp_plan.h"
+#include "mvhdp_state.h"
 
 #include <algorithm>
 #include <functional>
@@ -46,13 +47,8 @@ struct mvhdp_ctx {
     uint8_t* d_inactive = nullptr;
     std::vector<double> h_alpha;
     std::vector<uint8_t> h_inactive;
-    bool have_hyper = false, have_counts = false, have_trees = false;
-    bool full_trees = false;                 // the FTree.tree arrays are current too (a sweep may refresh only the descent table)
-    bool trees_inference = false;            // leaves of the last build: p_wt alone (INF:576)
-    bool delta_clean = false;                // the delta buffer is known to be all zero
-    bool delta_pending = false;              // a NO_APPLY sweep has left deltas that mvhdp_apply_delta has not consumed yet
-    bool last_need_full = true;              // the last sweep's kernels could reach the generic kernel (needs FTree.tree itself)
-    int64_t rows_applied = -1;               // mvhdp_apply_delta_rows progress of the current begin/end bracket (-1: no bracket open)
+    bool have_hyper = false;
+    ModelState st;                           // what the counts, trees, delta buffers and slot counts currently hold: mvhdp_state.h
     bool device_released = false;            // release_device_resources has run (mvhdp_destroy, or the exit handler)
 
     unsigned long long* d_ctl = nullptr;     // ONE block: [ST_COUNT] counters | activation key | META_WORDS64 | 8 work-queue heads (one reset launch, one read-back)
@@ -80,7 +76,6 @@ struct mvhdp_ctx {
         bool no_row_sample = false;          //   MVHDP_NO_ROW_SAMPLE: MVHDP_SL_NO_ROW_SAMPLE in every live-rows sweep
         bool no_heavy_refresh = false;       //   MVHDP_NO_HEAVY_REFRESH: live-rows sweeps without heavy_refresh_kernel beside the samplers
     } diag;
-    bool delta16_used = false;               // MvModel::delta16 holds deltas of the last sweep (until the apply pass)
     int side_priority = 2;                   // side streams A and B at high priority (a hardware-queue pool of their own)
     hipStream_t side[PLAN_N_STREAMS]{};      // side streams of the wider kernel classes (created on first use; [0] unused: the handle's stream)
     hipEvent_t ev_fork = nullptr, ev_join[PLAN_N_STREAMS]{};
@@ -92,13 +87,6 @@ struct mvhdp_ctx {
     // what the last sweep (or the recount after new assignments) left behind for the next plan
     unsigned long long last_hist[MVHDP_HIST_BINS]{};   // tokens by topic-list size class
     unsigned long long last_ent[MVHDP_ENT_BINS]{};     // entities by kernel class
-    bool nslots_valid = false;               // MvModel::nslots and the two histograms describe the current assignments
-    // Some token of view m may still carry UNASSIGNED_TOPIC (-1, PTM:63): set by set_corpus (which fills z with -1) and by set_assignments
-    // when the host's array holds one, cleared when a full sweep has visited every entity without abandoning one.  A live sweep on the
-    // 16-bit mirror needs every row's total to be constant (a LIGHT row can then never reach 65535 in a cell); a first visit of an
-    // unassigned token only adds to its row, so while this is set live sweeps stay on the 32-bit table.
-    bool unassigned[MVHDP_MAXM]{};
-    bool counts_stale = false;               // assignments were replaced (set_assignments / init_from_trees) and the counts not rebuilt since
     // overlapped segments (MVHDP_SWEEP_SEGMENT_OVERLAP, live sweeps with live_overlap): the second copy of what two segments in flight
     // must not share, allocated on first use
     struct Overlap {
@@ -108,7 +96,6 @@ struct mvhdp_ctx {
         int32_t* lists2 = nullptr;
         hipStream_t x1 = nullptr, xa = nullptr;
         hipEvent_t ev_start = nullptr;
-        bool deltas_dirty = false;           // an overlapped segmented sweep was enqueued and has not been seen to finish: delta2 / delta3 may hold leftovers
         std::vector<hipEvent_t> ev_seg;      // per segment: [3 * s] kernels done, [3 * s + 1] update done, [3 * s + 2] queue heads reset
     } ov;
     PlanRegs regs{};                         // register counts of the compiled kernels (occupancy)

@@ -302,8 +302,8 @@ int diag_ready(mvhdp_ctx* h, bool need_hyper)
 {
     for (int m = 0; m < h->mm.M; m++)
         if (!h->have_corpus[m]) FAIL(h, MVHDP_ERR_STATE, "diagnostics: set_corpus has not been called for every view");
-    if (!h->have_counts || h->counts_stale) FAIL(h, MVHDP_ERR_STATE, "diagnostics: the counts are not current (build_counts / set_counts first)");
-    if (h->delta_pending) FAIL(h, MVHDP_ERR_STATE, "diagnostics: a NO_APPLY sweep's deltas are pending (mvhdp_apply_delta first)");
+    if (!h->st.have_counts() || h->st.counts_stale()) FAIL(h, MVHDP_ERR_STATE, "diagnostics: the counts are not current (build_counts / set_counts first)");
+    if (h->st.delta_pending()) FAIL(h, MVHDP_ERR_STATE, "diagnostics: a NO_APPLY sweep's deltas are pending (mvhdp_apply_delta first)");
     if (need_hyper && !h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "diagnostics before set_hyper");
     return MVHDP_OK;
 }

@@ -812,7 +812,7 @@ extern "C" int mvhdp_set_vectors_mix(mvhdp_handle h, double lambda, const double
     CHECK_H(h);
     if (!(lambda >= 0.0 && lambda <= 1.0)) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: lambda outside [0, 1]");
     if ((exp_dot == nullptr) != (sum_exp == nullptr)) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: exp_dot and sum_exp go together (both, or both NULL)");
-    if (h->rows_applied >= 0) FAIL(h, MVHDP_ERR_STATE, "set_vectors_mix: an mvhdp_apply_delta_begin bracket is open");
+    if (h->st.bracket_open()) FAIL(h, MVHDP_ERR_STATE, "set_vectors_mix: an mvhdp_apply_delta_begin bracket is open");
     const int V0 = h->mm.V[0], K = h->mm.K;
     const size_t n = (size_t)V0 * K;
     HIPC(h, hipSetDevice(h->device));
@@ -821,7 +821,7 @@ extern "C" int mvhdp_set_vectors_mix(mvhdp_handle h, double lambda, const double
         if (h->d_mix) { hipFree(h->d_mix); h->d_mix = nullptr; }
         if (h->d_mix32) { hipFree(h->d_mix32); h->d_mix32 = nullptr; }
         h->mm.mix = nullptr; h->mm.mix32 = nullptr; h->mm.oml = 1.0; h->mix_lambda = 0.0;
-        h->have_trees = false;
+        h->st.trees_outdated();
         return MVHDP_OK;
     }
     const double* S_host = sum_exp;
@@ -865,7 +865,7 @@ extern "C" int mvhdp_set_vectors_mix(mvhdp_handle h, double lambda, const double
     if (h->d_mix32) hipFree(h->d_mix32);
     h->d_mix = d_new; h->d_mix32 = d_new32;
     h->mm.mix = d_new; h->mm.mix32 = d_new32; h->mm.oml = 1.0 - lambda; h->mix_lambda = lambda;
-    h->have_trees = false;
+    h->st.trees_outdated();
     return MVHDP_OK;
 }
 

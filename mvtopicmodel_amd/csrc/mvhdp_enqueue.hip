@@ -35,7 +35,7 @@ int activate_born(mvhdp_ctx* h, const std::vector<std::pair<int32_t, long long>>
     }
     mm.first_inactive = -1;
     for (int k = 0; k < K; k++) if (h->h_inactive[k]) { mm.first_inactive = k; break; }
-    h->have_trees = false;
+    h->st.trees_outdated();
     HIPC(h, hipMemcpy(h->d_alpha, h->h_alpha.data(), h->h_alpha.size() * sizeof(double), hipMemcpyHostToDevice));
     HIPC(h, hipMemcpy(h->d_inactive, h->h_inactive.data(), (size_t)K, hipMemcpyHostToDevice));
     return MVHDP_OK;
@@ -83,9 +83,9 @@ static int ensure_slot_counts(mvhdp_ctx* h)
     if (mm.D > 0 && !h->d_nslots) {
         HIPC(h, hipMalloc(&h->d_nslots, (size_t)mm.D * sizeof(uint16_t)));
         mm.nslots = h->d_nslots;
-        h->nslots_valid = false;
+        h->st.nslots_invalidated();
     }
-    if (h->nslots_valid) return MVHDP_OK;
+    if (h->st.nslots_valid()) return MVHDP_OK;
     unsigned long long hist[MVHDP_HIST_BINS + MVHDP_ENT_BINS] = {0};
     HIPC(h, hipMemsetAsync(h->d_ovf_meta, 0, META_BYTES, h->stream));
     HIPC(h, mvhdp_launch_slot_hist(mm, (unsigned long long*)h->d_ovf_meta + META_HIST, h->stream));
@@ -93,7 +93,7 @@ static int ensure_slot_counts(mvhdp_ctx* h)
     HIPC(h, hipStreamSynchronize(h->stream));
     std::copy(hist, hist + MVHDP_HIST_BINS, h->last_hist);
     std::copy(hist + MVHDP_HIST_BINS, hist + MVHDP_HIST_BINS + MVHDP_ENT_BINS, h->last_ent);
-    h->nslots_valid = true;
+    h->st.nslots_counted(true);
     return MVHDP_OK;
 }
 
@@ -108,9 +108,8 @@ static void fill_plan_in(mvhdp_ctx* h, uint32_t flags, bool debug, bool batch, P
     std::copy(h->last_hist, h->last_hist + MVHDP_HIST_BINS, in.tok_hist);
     std::copy(h->last_ent, h->last_ent + MVHDP_ENT_BINS, in.ent_hist);
     in.flags = flags; in.debug = debug; in.batch = batch;
-    in.trees_current = h->have_trees;
-    in.unassigned = false;
-    for (int m = 0; m < mm.M; m++) in.unassigned = in.unassigned || h->unassigned[m];
+    in.trees_current = h->st.trees_current();
+    in.unassigned = h->st.any_unassigned();
     in.first_inactive = mm.first_inactive;
     in.vectors_mix = mm.mix != nullptr && !(flags & MVHDP_SWEEP_FROZEN);      // (the inferencer's worker has lambda = 0: INF:251-252)
     in.num_cus = h->num_cus; in.max_lds = h->max_lds;
@@ -335,7 +334,7 @@ static hipError_t live_rows_prepare(mvhdp_ctx* h, const SweepPlan& p, bool from_
 static hipError_t rebuild_trees(mvhdp_ctx* h, const SweepPlan& p, hipStream_t s)
 {
     const hipError_t e = mvhdp_launch_build_trees(h->mm, false, p.need_full, s);
-    h->have_trees = true; h->full_trees = p.need_full; h->trees_inference = false;
+    h->st.trees_built(p.need_full, false);
     return e;
 }
 
@@ -344,10 +343,10 @@ static hipError_t rebuild_trees(mvhdp_ctx* h, const SweepPlan& p, hipStream_t s)
 static hipError_t trees_at_sweep_start(mvhdp_ctx* h, const SweepPlan& p, hipStream_t s)
 {
     hipError_t e = hipSuccess, e2 = hipSuccess;
-    h->last_need_full = p.need_full;
-    if (p.live_rows) { e = live_rows_prepare(h, p, false, s); h->have_trees = false; h->full_trees = false; }
+    h->st.sweep_planned(p.need_full);
+    if (p.live_rows) { e = live_rows_prepare(h, p, false, s); h->st.trees_overwritten(); }
     else if (!(p.flags & MVHDP_SWEEP_REUSE_TREES)) e = rebuild_trees(h, p, s);
-    if (p.need_full && !h->full_trees) { e2 = mvhdp_launch_build_trees(h->mm, h->trees_inference, true, s); h->full_trees = true; }
+    if (p.need_full && !h->st.full_trees()) { e2 = mvhdp_launch_build_trees(h->mm, h->st.trees_inference(), true, s); h->st.full_trees_written(); }
     return e != hipSuccess ? e : e2;
 }
 
@@ -359,9 +358,9 @@ static hipError_t live_epilogue(mvhdp_ctx* h, const SweepPlan& p, unsigned long 
     MvModel& mm = h->mm;
     const bool no_apply = (p.flags & MVHDP_SWEEP_NO_APPLY) != 0;
     hipError_t e = hipSuccess;
-    if (p.live16 && mm.D > 0) { e = mvhdp_launch_widen_mirror(mm, s); h->have_trees = false; }
+    if (p.live16 && mm.D > 0) { e = mvhdp_launch_widen_mirror(mm, s); h->st.trees_outdated(); }
     const hipError_t e2 = mvhdp_launch_live_helper(mm, no_apply ? 1 : 2, d_stats, s);
-    if (p.nseg > 1 && !(p.flags & MVHDP_SWEEP_REUSE_TREES) && (no_apply || p.overlap)) h->have_trees = false;
+    if (p.nseg > 1 && !(p.flags & MVHDP_SWEEP_REUSE_TREES) && (no_apply || p.overlap)) h->st.trees_outdated();
     return e != hipSuccess ? e : e2;
 }
 
@@ -445,12 +444,12 @@ static int enqueue_overlapped(mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_i
         B[1].counts = ov.counts2; B[1].counts16 = ov.counts16_2;
         step(hipMemcpyAsync(ov.counts2, mm.counts, cbytes, hipMemcpyDeviceToDevice, X[0]));
         step(hipMemcpyAsync(ov.counts16_2, mm.counts16, (size_t)nrows * mm.K * sizeof(uint16_t), hipMemcpyDeviceToDevice, X[0]));
-        if (!h->delta_clean) step(hipMemsetAsync(mm.delta, 0, cbytes, X[0]));
-        h->delta_clean = false;
-        if (ov.deltas_dirty) { step(hipMemsetAsync(ov.delta2, 0, cbytes, X[0])); step(hipMemsetAsync(ov.delta3, 0, cbytes, X[0])); }
-        ov.deltas_dirty = true;                                    // (cleared by mvhdp_sweep_finish / the batch's read-back when the sweep is seen to have finished)
+        if (!h->st.delta_clean()) step(hipMemsetAsync(mm.delta, 0, cbytes, X[0]));
+        h->st.delta_written(false);
+        if (h->st.deltas_dirty()) { step(hipMemsetAsync(ov.delta2, 0, cbytes, X[0])); step(hipMemsetAsync(ov.delta3, 0, cbytes, X[0])); }
+        h->st.overlap_enqueued();                                  // (overlap_finished: mvhdp_sweep_finish / the batch's read-back, when the sweep is seen to have finished)
     } else if (flags & MVHDP_SWEEP_NO_APPLY) {                     // (live, document shards: the caller wants after - before)
-        step(mvhdp_launch_live_helper(mm, 0, d_stats, X[0])); h->delta_clean = false;
+        step(mvhdp_launch_live_helper(mm, 0, d_stats, X[0])); h->st.delta_written(false);
     }
     SegCtl ctl[2] = {{h->d_ovf_meta + META_CLASS_COUNTS, h->d_doc_counter, nullptr}, {(unsigned int*)(ov.ctl2 + 8), ov.ctl2, ov.lists2}};
     step(mvhdp_launch_ctl_reset(d_stats, ST_COUNT, h->d_act_key, (unsigned long long*)h->d_ovf_meta, META_WORDS64, nullptr, nullptr, X[0]));
@@ -511,7 +510,7 @@ static int enqueue_overlapped(mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_i
         if (p.seg_apply) {
             // the copy A(nseg-1) did not write lacks the last segment's deltas
             step(mvhdp_launch_apply_sparse(B[(nseg + 1) & 1], D3[(nseg - 1) % 3], use_mirror, X[0]));
-            h->have_trees = false;
+            h->st.trees_outdated();
             // (both copies equal now; copy 0 = mm is the model, every delta buffer is zero again)
         }
     }
@@ -545,15 +544,14 @@ static int enqueue_sweep(mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_idx, u
     MvModel mk = mm;
     if (p.live) {
         mk.delta = mm.counts;
-        if (flags & MVHDP_SWEEP_NO_APPLY) { step(mvhdp_launch_live_helper(mm, 0, d_stats, s)); h->delta_clean = false; }
+        if (flags & MVHDP_SWEEP_NO_APPLY) { step(mvhdp_launch_live_helper(mm, 0, d_stats, s)); h->st.delta_written(false); }
     } else if (!p.frozen) {                                      // a frozen sweep queues nothing (WRK:587) and leaves the buffer alone
-        if (!h->delta_clean) {
+        if (!h->st.delta_clean()) {
             step(hipMemsetAsync(mm.delta, 0, (size_t)counts_len(h) * sizeof(int32_t), s));
-            if (h->delta16_used) step(hipMemsetD16Async(mm.delta16, (unsigned short)0x8000, (size_t)(mm.rowbase[M] * mm.K), s));   // (a sweep that failed before its apply pass)
-            h->delta16_used = false;
+            if (h->st.delta16_used()) step(hipMemsetD16Async(mm.delta16, (unsigned short)0x8000, (size_t)(mm.rowbase[M] * mm.K), s));   // (a sweep that failed before its apply pass)
+            h->st.delta16_rebiased();
         }
-        h->delta_clean = false;
-        if (p.delta16) h->delta16_used = true;                   // (cleared by the apply pass, which folds the 16-bit cells in and re-biases them)
+        h->st.delta_written(p.delta16);                          // (the apply pass folds the 16-bit cells in and re-biases them)
     }
     // this sweep's counters, "no activation yet", the histograms for the next plan, the class list lengths, the queue heads: one launch
     step(mvhdp_launch_ctl_reset(d_stats, ST_COUNT, h->d_act_key, (unsigned long long*)h->d_ovf_meta, META_WORDS64, nullptr, h->d_doc_counter, s));
@@ -592,13 +590,13 @@ static int enqueue_sweep(mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_idx, u
                 // leaf needs all of it), then ONE pass per row: counts += delta, delta = 0, the row's tree and 16-bit mirror
                 step(mvhdp_launch_apply_nk(mm, d_stats + ST_NEGATIVE, s));
                 step(mvhdp_launch_build_trees_rows(mm, false, p.need_full, 0, mm.rowbase[M], true, d_stats + ST_NEGATIVE, s));
-                h->have_trees = true; h->full_trees = p.need_full; h->trees_inference = false;
+                h->st.trees_built(p.need_full, false);
             } else if (p.live_rows) {                                                    // tokensPerTopic has landed: new coefficients, exact roots
                 step(live_rows_prepare(h, p, p.live16, s));
             } else if (p.live && !(flags & MVHDP_SWEEP_REUSE_TREES) && (h->live_tree_every <= 1 || seg % h->live_tree_every == 0)) {   // from the live counts
                 if (p.live16) {                                                          // (the light rows' live counts are in the mirror)
                     step(mvhdp_launch_build_trees_from_mirror(mm, p.need_full, s));
-                    h->have_trees = true; h->full_trees = p.need_full; h->trees_inference = false;
+                    h->st.trees_built(p.need_full, false);
                 } else step(rebuild_trees(h, p, s));
             }
             step(mvhdp_launch_ctl_reset(nullptr, 0, nullptr, nullptr, 0, class_counts, h->d_doc_counter, s));
@@ -621,7 +619,7 @@ static int enqueue_sweep(mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_idx, u
     }
     if (p.seg_apply && mm.D > 0) {                               // the last segment's deltas (the trees are rebuilt by whoever needs them next)
         step(mvhdp_launch_apply_delta(mm, d_stats, s));
-        h->have_trees = false;
+        h->st.trees_outdated();
     }
     if (p.live) step(live_epilogue(h, p, d_stats, s));
     step(hipEventRecord(ev_k1, s));
@@ -652,11 +650,11 @@ static void learn_from_sweep(mvhdp_ctx* h, const SweepPlan& p, const unsigned lo
     if (mm.D > 0 && p.only_seg >= 0) {
         // a single segment was swept: its histograms describe a part of the entities only -- the earlier ones stay (every plan of
         // a single-segment sweep launches whatever is reachable), only an abandoned entity asks for a recount
-        if (meta_hist[MVHDP_HIST_BINS + MVHDP_N_CLASSES] != 0) h->nslots_valid = false;
+        if (meta_hist[MVHDP_HIST_BINS + MVHDP_N_CLASSES] != 0) h->st.nslots_invalidated();
     } else if (mm.D > 0) {
         std::copy(meta_hist, meta_hist + MVHDP_HIST_BINS, h->last_hist);
         std::copy(meta_hist + MVHDP_HIST_BINS, meta_hist + MVHDP_HIST_BINS + MVHDP_ENT_BINS, h->last_ent);
-        h->nslots_valid = h->last_ent[MVHDP_N_CLASSES] == 0;        // an abandoned entity (Q11): its list is recounted before the next sweep
+        h->st.nslots_counted(h->last_ent[MVHDP_N_CLASSES] == 0);      // an abandoned entity (Q11): its list is recounted before the next sweep
     }
     if (h->dbg_env) {
         fprintf(stderr, "[mvhdp] walk threshold %.2f (base %.2f, phase %d, dir %+d, group %d); tree branch %.4f of tokens, walked on demand %.4f; per view tree share:",
@@ -706,12 +704,12 @@ static int sweep_preconditions(mvhdp_ctx* h, uint32_t flags)
         FAIL(h, MVHDP_ERR_INVALID_ARG, "sweep: SHARD_BIRTHS goes with LIVE, not with FROZEN or ONLY_SEGMENT");
     int rc = require_corpus(h); if (rc) return rc;
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "sweep before set_hyper");
-    if (!h->have_counts) FAIL(h, MVHDP_ERR_STATE, "sweep before build_counts/set_counts");
-    if ((flags & (MVHDP_SWEEP_REUSE_TREES | MVHDP_SWEEP_FROZEN)) && !h->have_trees) FAIL(h, MVHDP_ERR_STATE, "REUSE_TREES / FROZEN without trees");
-    if (h->rows_applied >= 0) FAIL(h, MVHDP_ERR_STATE, "sweep: an mvhdp_apply_delta_begin bracket is open (call mvhdp_apply_delta_end)");
-    if (h->delta_pending && !(flags & MVHDP_SWEEP_FROZEN))
+    if (!h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "sweep before build_counts/set_counts");
+    if ((flags & (MVHDP_SWEEP_REUSE_TREES | MVHDP_SWEEP_FROZEN)) && !h->st.trees_current()) FAIL(h, MVHDP_ERR_STATE, "REUSE_TREES / FROZEN without trees");
+    if (h->st.bracket_open()) FAIL(h, MVHDP_ERR_STATE, "sweep: an mvhdp_apply_delta_begin bracket is open (call mvhdp_apply_delta_end)");
+    if (h->st.delta_pending() && !(flags & MVHDP_SWEEP_FROZEN))
         FAIL(h, MVHDP_ERR_STATE, "sweep: the previous NO_APPLY sweep's deltas have not been applied (mvhdp_apply_delta)");
-    if (h->counts_stale && !(flags & MVHDP_SWEEP_FROZEN))
+    if (h->st.counts_stale() && !(flags & MVHDP_SWEEP_FROZEN))
         FAIL(h, MVHDP_ERR_STATE, "sweep: the assignments were replaced after the counts were built (call mvhdp_build_counts, mvhdp_set_counts or mvhdp_counts_written first)");
     return MVHDP_OK;
 }
@@ -775,7 +773,7 @@ int mvhdp_sweep_finish(mvhdp_ctx* h, PendingSweep& ps, mvhdp_sweep_stats* stats)
     const unsigned long long* meta = h->h_ctl + ST_COUNT + 1;
     if (hs[ST_MISCLASS] || meta[META_MISROUTED]) {
         ps.db.release();
-        h->nslots_valid = false;
+        h->st.nslots_invalidated();
         FAIL(h, MVHDP_ERR_HIP, "internal: an entity reached a sweep kernel variant that cannot hold its topic list");
     }
     if (ps.debug) {
@@ -790,7 +788,7 @@ int mvhdp_sweep_finish(mvhdp_ctx* h, PendingSweep& ps, mvhdp_sweep_stats* stats)
     mvhdp_sweep_stats st;
     stats_from_counters(hs, act, st);
     // every entity was visited and none abandoned: no token of a known type is unassigned any more (WRK:557)
-    if (!p.frozen && p.only_seg < 0 && st.aborted_docs == 0) for (int m = 0; m < mm.M; m++) h->unassigned[m] = false;
+    if (!p.frozen && p.only_seg < 0 && st.aborted_docs == 0) h->st.every_token_assigned();
     const unsigned long long negatives = hs[ST_NEGATIVE];
     // (the pinned buffer belongs to the handle: a sweep begun on it before this one returns would overwrite it -- what the
     // planner learns from is copied out first)
@@ -803,12 +801,11 @@ int mvhdp_sweep_finish(mvhdp_ctx* h, PendingSweep& ps, mvhdp_sweep_stats* stats)
     if (p.frozen) {
         // nothing was queued (WRK:587): the delta buffer is untouched
     } else if (flags & MVHDP_SWEEP_NO_APPLY) {
-        h->delta_pending = true;
+        h->st.delta_left_pending();
     } else if (p.live || p.seg_apply) {
         // the counts are already updated; what is left of the updater's work is the topic activation of the last segment
-        h->have_trees = false;
-        if (p.seg_apply) h->delta_clean = true;                      // apply_delta_kernel zeroed what it added
-        if (p.seg_apply && p.overlap) h->ov.deltas_dirty = false;
+        if (p.seg_apply) h->st.delta_applied(); else h->st.trees_outdated();   // apply_delta_kernel zeroed what it added
+        if (p.seg_apply && p.overlap) h->st.overlap_finished();
         if (ps.births) {                                             // the last segment's births (the earlier segments' were applied at their borders)
             ret = births_end(h, s, ps.oc);
             n_activations = ps.oc.n_activations;
@@ -886,13 +883,11 @@ extern "C" int mvhdp_sweep_many(mvhdp_handle h, uint32_t first_idx, int32_t n, u
         if (rc) return rc;
         if (!p.frozen && !p.live && !p.seg_apply) {
             // the updater's pass (UPD:197-218) in stream order; negative counts are counted into this sweep's counters
-            HIPC(h, mvhdp_launch_apply_delta(mm, d_st, s, h->delta16_used));
-            h->delta16_used = false;
-            h->have_trees = false; h->delta_clean = true;
-        } else if (p.live || p.seg_apply) {
-            h->have_trees = false;
-            if (p.seg_apply) h->delta_clean = true;
-        }
+            HIPC(h, mvhdp_launch_apply_delta(mm, d_st, s, h->st.delta16_used()));
+            h->st.delta16_rebiased();
+            h->st.delta_applied();
+        } else if (p.seg_apply) h->st.delta_applied();
+        else if (p.live) h->st.trees_outdated();
     }
     HIPC(h, hipEventRecord(h->ev[3], s));
     std::vector<unsigned long long> hs((size_t)n * ST_COUNT);
@@ -900,7 +895,7 @@ extern "C" int mvhdp_sweep_many(mvhdp_handle h, uint32_t first_idx, int32_t n, u
     HIPC(h, hipMemcpyAsync(hs.data(), h->d_stats_many, hs.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
     HIPC(h, hipMemcpyAsync(meta, h->d_ovf_meta, sizeof meta, hipMemcpyDeviceToHost, s));
     HIPC(h, hipStreamSynchronize(s));
-    if (p.seg_apply && p.overlap) h->ov.deltas_dirty = false;
+    if (p.seg_apply && p.overlap) h->st.overlap_finished();
     float ms_t = 0;
     hipEventElapsedTime(&ms_t, h->ev[0], h->ev[3]);
     int ret = MVHDP_OK;
@@ -914,15 +909,15 @@ extern "C" int mvhdp_sweep_many(mvhdp_handle h, uint32_t first_idx, int32_t n, u
         st.sweep_kernel_ms = ms_k; st.total_ms = ms_t / n;
         ms_sum += ms_k;
         if (stats) stats[i] = st;
-        if (hi[ST_MISCLASS]) { h->nslots_valid = false; FAIL(h, MVHDP_ERR_HIP, "internal: an entity reached a sweep kernel variant that cannot hold its topic list"); }
+        if (hi[ST_MISCLASS]) { h->st.nslots_invalidated(); FAIL(h, MVHDP_ERR_HIP, "internal: an entity reached a sweep kernel variant that cannot hold its topic list"); }
         if (hi[ST_NEGATIVE] && ret == MVHDP_OK) { h->err = "a topic count went below zero (UPD:202-215)"; ret = MVHDP_ERR_NEGATIVE_COUNT; }
     }
-    if (meta[META_MISROUTED]) { h->nslots_valid = false; FAIL(h, MVHDP_ERR_HIP, "internal: an entity could not be routed to a sweep kernel"); }
+    if (meta[META_MISROUTED]) { h->st.nslots_invalidated(); FAIL(h, MVHDP_ERR_HIP, "internal: an entity could not be routed to a sweep kernel"); }
     // the batch counts as one observation of the walk search (mean kernel time per token)
     std::vector<unsigned long long> acc(ST_COUNT, 0);
     for (int i = 0; i < n; i++) for (int k = 0; k < ST_COUNT; k++) acc[k] += hs[(size_t)i * ST_COUNT + k];
     const bool comparable = p.fast && !h->tu.walk_fixed && !(flags & (MVHDP_SWEEP_FROZEN | MVHDP_SWEEP_EXACT_CHAIN));
     learn_from_sweep(h, p, acc.data(), meta + META_HIST, ms_sum, comparable);
-    if (!p.frozen && acc[ST_ABORT] == 0) for (int m = 0; m < mm.M; m++) h->unassigned[m] = false;
+    if (!p.frozen && acc[ST_ABORT] == 0) h->st.every_token_assigned();
     return ret;
 }

@@ -543,7 +543,7 @@ static int fan_out_range(mvhdp_group_ctx* g, bool counts, int64_t e0, int64_t e1
 static int pack_prepare(mvhdp_group_ctx* g)
 {
     if (g->pack_ready || !g->pack_allowed) return MVHDP_OK;
-    for (mvhdp_ctx* h : g->members) for (int m = 0; m < h->mm.M; m++) if (h->unassigned[m]) return MVHDP_OK;   // (a first visit only adds to its row: not yet)
+    for (mvhdp_ctx* h : g->members) if (h->st.any_unassigned()) return MVHDP_OK;   // (a first visit only adds to its row: not yet)
     mvhdp_ctx* L0 = g->members[g->leaders[0]];
     const int64_t rows = L0->mm.rowbase[L0->mm.M];
     const int K = L0->mm.K;
@@ -614,7 +614,7 @@ extern "C" int mvhdp_group_build_counts(mvhdp_group g)
         mvhdp_ctx* h = g->members[i];
         local.member(i, mvhdp_build_counts(h));
         // a stale delta buffer (a failed exchange left the peers' sums in it) must not survive the recount
-        if (!h->delta_clean) { x.hip(hipSetDevice(h->device), "hipSetDevice"); x.hip(hipMemsetAsync(h->mm.delta, 0, (size_t)(len + MVHDP_TAIL_WORDS) * sizeof(int32_t), h->stream), "hipMemsetAsync"); h->delta_clean = true; h->delta_pending = false; }
+        if (!h->st.delta_clean()) { x.hip(hipSetDevice(h->device), "hipSetDevice"); x.hip(hipMemsetAsync(h->mm.delta, 0, (size_t)(len + MVHDP_TAIL_WORDS) * sizeof(int32_t), h->stream), "hipMemsetAsync"); h->st.delta_zeroed(); }
     }
     if (local.rc != MVHDP_OK)
         for (int i = 0; i < n; i++) { mvhdp_ctx* h = g->members[i]; x.hip(hipSetDevice(h->device), "hipSetDevice"); x.hip(hipMemsetAsync(h->mm.counts, 0, (size_t)len * sizeof(int32_t), h->stream), "hipMemsetAsync"); }
@@ -640,7 +640,7 @@ extern "C" int mvhdp_group_build_counts(mvhdp_group g)
     if (local.rc == MVHDP_OK && failed_ranks == 0)
         for (int i = 0; i < n; i++) local.member(i, mvhdp_counts_written(g->members[i]));
     else
-        for (int i = 0; i < n; i++) { g->members[i]->counts_stale = true; g->members[i]->have_trees = false; }
+        for (int i = 0; i < n; i++) { g->members[i]->st.counts_went_stale(); g->members[i]->st.trees_outdated(); }
     if (local.rc != MVHDP_OK) return local.rc;
     if (failed_ranks != 0)
         GFAIL(g, MVHDP_ERR_STATE, "the recount failed on " + std::to_string(failed_ranks) + " other rank(s) of the group (or the collective broke): the counts are not valid");
@@ -657,7 +657,7 @@ static void sweep_members(mvhdp_group_ctx* g, XErr& local, uint32_t sweep_idx, u
     for (int i = 0; i < n && local.rc == MVHDP_OK; i++) {
         mvhdp_ctx* h = g->members[i];
         // the trees a pipelined apply left behind are those of the counts this sweep starts from (a live sweep rebuilds per segment itself)
-        const uint32_t reuse = (h->have_trees && !(flags & MVHDP_SWEEP_LIVE)) ? MVHDP_SWEEP_REUSE_TREES : 0u;
+        const uint32_t reuse = (h->st.trees_current() && !(flags & MVHDP_SWEEP_LIVE)) ? MVHDP_SWEEP_REUSE_TREES : 0u;
         local.member(i, mvhdp_sweep_begin(h, sweep_idx, seed, flags | MVHDP_SWEEP_NO_APPLY | reuse, nullptr, nullptr, ps[i]));
     }
     for (int i = 0; i < n; i++)
@@ -681,7 +681,7 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
             mvhdp_ctx* h = g->members[i];
             hipSetDevice(h->device);
             hipMemsetAsync(h->mm.delta, 0, (size_t)len * sizeof(int32_t), h->stream);
-            h->delta_pending = false; h->counts_stale = true; h->have_trees = false; h->rows_applied = -1;
+            h->st.bracket_abandoned(); h->st.delta_discarded(false);
         }
     };
     if (local.rc != MVHDP_OK) drop_local();
@@ -798,10 +798,10 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
             local.member(i, rc2);
         } else {
             hipSetDevice(h->device); hipStreamSynchronize(h->stream);
-            if (h->rows_applied >= 0) { h->rows_applied = -1; h->have_trees = false; }     // a bracket this step opened and could not close
+            if (h->st.bracket_open()) h->st.bracket_abandoned();                            // a bracket this step opened and could not close
             // The collectives ran in place on this member's delta buffer: it now holds the OTHER ranks' sums (or half an exchange), which
             // nothing will apply.  Mark it dirty: the next sweep's enqueue and mvhdp_group_build_counts clear a dirty buffer first.
-            h->counts_stale = true; h->delta_pending = false; h->delta_clean = false;
+            h->st.delta_discarded(true);
         }
         st[i].activation_key = key; st[i].activated_topic = topic; st[i].activated_modality = view;
         st[i].activations = shard_births ? born : topic >= 0 ? 1 : 0;
@@ -812,7 +812,7 @@ static int group_step(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t seed, uin
     if (local.rc != MVHDP_OK) return local.rc;
     if (failed_ranks != 0) {
         // the other replicas applied the same (partial) sum and agree with each other; the model as a whole needs the recount
-        for (int i = 0; i < n; i++) g->members[i]->counts_stale = true;
+        for (int i = 0; i < n; i++) g->members[i]->st.counts_went_stale();
         GFAIL(g, MVHDP_ERR_STATE, "the sweep failed on " + std::to_string(failed_ranks) + " other rank(s) of the group (or the collective broke): call mvhdp_group_build_counts on every rank");
     }
     return MVHDP_OK;
@@ -864,7 +864,7 @@ static int async_land(mvhdp_group_ctx* g, int32_t* failed)
         const int grid = (int)std::min<int64_t>((len + 255) / 256, 8192);
         hipLaunchKernelGGL(add_remote_kernel, dim3(grid), dim3(256), 0, h->stream, h->mm.counts, g->xbuf[i], g->sbuf[i], len);
         x.hip(hipGetLastError(), "add_remote_kernel");
-        h->have_trees = false;
+        h->st.trees_outdated();
     }
     mvhdp_ctx* L0 = g->members[g->leaders[0]];
     x.hip(hipSetDevice(L0->device), "hipSetDevice");
@@ -881,7 +881,7 @@ static int land_exchange(mvhdp_group_ctx* g, int* local)
     int32_t failed = 0;
     const int rc = async_land(g, &failed);
     if (rc == MVHDP_OK && failed == 0) return MVHDP_OK;
-    for (mvhdp_ctx* h : g->members) h->counts_stale = true;
+    for (mvhdp_ctx* h : g->members) h->st.counts_went_stale();
     if (rc != MVHDP_OK) { *local = rc; return MVHDP_OK; }
     GFAIL(g, MVHDP_ERR_STATE, "a sweep whose deltas were still on the wire had failed on " + std::to_string(failed) + " rank(s): call mvhdp_group_build_counts on every rank");
 }
@@ -914,14 +914,14 @@ static int group_step_async(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t see
     for (int i = 0; i < n; i++) {
         mvhdp_ctx* h = g->members[i];
         x.hip(hipSetDevice(h->device), "hipSetDevice");
-        if (local.rc != MVHDP_OK) { x.hip(hipMemsetAsync(h->mm.delta, 0, bytes, h->stream), "hipMemsetAsync"); h->counts_stale = true; }
+        if (local.rc != MVHDP_OK) { x.hip(hipMemsetAsync(h->mm.delta, 0, bytes, h->stream), "hipMemsetAsync"); h->st.counts_went_stale(); }
         else x.hip(launch_add_into(h->mm.counts, h->mm.delta, len, h->stream), "add_into_kernel");
     }
     int32_t failed = 0;
     local.note(async_land(g, &failed), g->err);
     local.note(x.rc, g->err);
     if (local.rc != MVHDP_OK)                              // (a failure found after the deltas went back in: this rank still ships zeros and a raised word)
-        for (int i = 0; i < n; i++) { mvhdp_ctx* h = g->members[i]; hipSetDevice(h->device); hipMemsetAsync(h->mm.delta, 0, bytes, h->stream); h->counts_stale = true; }
+        for (int i = 0; i < n; i++) { mvhdp_ctx* h = g->members[i]; hipSetDevice(h->device); hipMemsetAsync(h->mm.delta, 0, bytes, h->stream); h->st.counts_went_stale(); }
     // 3. this sweep's deltas go on the wire (a copy: the delta buffer is the next sweep's), the collective on its own stream
     for (int i = 0; i < n; i++) {
         mvhdp_ctx* h = g->members[i];
@@ -931,7 +931,7 @@ static int group_step_async(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t see
         x.hip(hipMemsetAsync(h->mm.delta, 0, bytes, h->stream), "hipMemsetAsync");
         hipLaunchKernelGGL(set_word_kernel, dim3(1), dim3(1), 0, h->stream, g->xbuf[i] + len, (g->leader_of[i] == i && local.rc != MVHDP_OK) ? 1 : 0);
         x.hip(hipEventRecord(g->ev_swept[i], h->stream), "hipEventRecord");
-        h->delta_pending = false; h->delta_clean = true; h->have_trees = false;
+        h->st.delta_applied();
     }
     for (size_t l = 0; l < g->leaders.size(); l++) {
         const int li = g->leaders[l];
@@ -955,9 +955,9 @@ static int group_step_async(mvhdp_group_ctx* g, uint32_t sweep_idx, uint64_t see
     g->async_pending = true;
     local.note(x.rc, g->err);
     for (int i = 0; i < n; i++) { st[i].activation_key = LLONG_MAX; st[i].activated_topic = -1; st[i].activated_modality = -1; st[i].activations = 0; }
-    if (local.rc != MVHDP_OK) { for (mvhdp_ctx* h : g->members) h->counts_stale = true; return local.rc; }
+    if (local.rc != MVHDP_OK) { for (mvhdp_ctx* h : g->members) h->st.counts_went_stale(); return local.rc; }
     if (failed != 0) {
-        for (mvhdp_ctx* h : g->members) h->counts_stale = true;
+        for (mvhdp_ctx* h : g->members) h->st.counts_went_stale();
         GFAIL(g, MVHDP_ERR_STATE, "the previous sweep failed on " + std::to_string(failed) + " other rank(s) of the group: call mvhdp_group_build_counts on every rank");
     }
     return MVHDP_OK;
