@@ -350,6 +350,40 @@ int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int64_t cap, in
  * MVHDP_ERR_INVALID_ARG for n < 0, dim < 1, stripe_rows < 0 or a NULL out; MVHDP_ERR_UNSUPPORTED for dim > 65536. */
 int mvhdp_sim_probe(int32_t n, int32_t dim, int32_t stripe_rows, mvhdp_sim_stats* out);
 
+/* findTopicPhrases PTM:1921-1976, which saveTopicsandExperiment calls at PTM:1555 for the 20 most frequent phrases of every topic
+ * (PTM:1557-1586) and topicPhraseXMLReport PTM:1978-2070 for the phrase weights and candidate titles: the same-topic word runs of the
+ * view-0 tokens, counted per topic.  Only view 0 is read (tokens, z, doc_off as the handle holds them; counts are not), and an entity
+ * without view 0 is an empty span.  Per entity, from EMPTY, for every position with (feature, topic): topic == prevtopic starts the phrase
+ * [prevfeature, feature] or appends feature to the open one; otherwise an open phrase is counted under prevtopic and the state goes back
+ * to EMPTY -- the token that broke the phrase is swallowed, it is not remembered as the start of anything (PTM:1958-1966); otherwise
+ * (topic, feature) is remembered (PTM:1968-1969).  Nothing is flushed at the end of the entity: a phrase still open there is dropped.
+ * So A A B B B C counts (A: w0 w1) and (B: w3 w4), and A A B B C only the first.  The flow's sequences are plain FeatureSequences: the
+ * FeatureSequenceWithBigrams clause of PTM:1951 has no counterpart.  A phrase is its topic and its word-id sequence (the reference's key
+ * is the words joined by a blank).
+ * Per topic the phrases come by count descending; equal counts by word-id sequence in ascending lexicographic order, a proper prefix
+ * first.  THIS tie order is ours: the reference's is the iteration order of a trove hash map seen through RankedFeatureVector.  The list
+ * is cut at max_per_topic.  topic_off[k] .. topic_off[k + 1] index counts and word_off; word_off[p] .. word_off[p + 1] index words.
+ * distinct[k] = phrases[k].keys().length before the cut; occurrences[k] = the sum of all counts of topic k before the cut (countssum,
+ * PTM:2037: the weight of a phrase is count / countssum).  The output is a function of tokens and z alone: two calls give the same bytes.
+ * On the device: a walk over the entities (a wave each) that emits one record per occurrence with a 64-bit hash of (topic, length, word
+ * ids); a count by key in an open-addressing table sized so that it cannot fill -- the hash places and never decides: two occurrences
+ * are one phrase only if topic, length and every word id are equal, compared on the corpus; per topic the phrases that reach the count at
+ * the cut.  Only those cross to the host, which settles the order inside equal counts.  stats.hash_collisions counts the comparisons
+ * where the used hash bits were equal and the phrases were not (it may differ between two calls; nothing else does).
+ * Capacity as mvhdp_doc_topics_top: word_off, words and counts NULL with both caps 0 returns *n_phrases and *n_words (and topic_off /
+ * distinct / occurrences / stats, unless NULL); more phrases than cap_phrases or more words than cap_words: MVHDP_ERR_INVALID_ARG, the two
+ * sizes set, every array untouched.  word_off holds cap_phrases + 1 entries.
+ * MVHDP_ERR_STATE, every output untouched: no view-0 corpus; a view-0 z that is -1 (no assignments yet) or >= K, a view-0 token outside
+ * [0, V_0) (the reference throws at alphabet.lookupObject; as mvhdp_diagnostics). */
+typedef struct { int32_t max_per_topic;  /* < 0: every phrase (what merging shards needs); the save path uses 20 (PTM:1569) */
+                 int32_t hash_bits;      /* 0: 64.  1..63: only that many low bits of the hash are used -- for tests: forces collisions */
+               } mvhdp_phrase_args;
+typedef struct { int64_t runs /* maximal same-topic runs */, occurrences, distinct, kept, hash_collisions; } mvhdp_phrase_stats;
+int mvhdp_topic_phrases(mvhdp_handle h, const mvhdp_phrase_args* a, int64_t cap_phrases, int64_t cap_words,
+                        int64_t* topic_off /*[K+1]*/, int64_t* word_off /*[kept+1]*/, int32_t* words, int32_t* counts /*[kept]*/,
+                        int64_t* distinct /*[K]*/, int64_t* occurrences /*[K]*/,
+                        int64_t* n_phrases, int64_t* n_words, mvhdp_phrase_stats* stats /* or NULL */);
+
 /* ---- topic diagnostics: the step after training (FastQMVWVTopicModelDiagnostics, DIAG = MVTopicModel/FastQMVWVTopicModelDiagnostics.java;
  * SciTopicFlow builds it with N = 20 right after the save, whose saveExperiment / saveTopicsandExperiment call
  * calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230 from PTM:1370 / PTM:1507 and getSortedWords PTM:1792-1811 per view).

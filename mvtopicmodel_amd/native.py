@@ -12,7 +12,8 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   EmbConfigC, EmbStatsC, GroupInfoC, HyperC, MvhdpError, SimArgsC, SimStatsC, SweepStatsC, TuningC, load_library,
+                   EmbConfigC, EmbStatsC, GroupInfoC, HyperC, MvhdpError, PhraseArgsC, PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
+                   load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
 SWEEP_REUSE_TREES = 0x1
@@ -133,6 +134,62 @@ def sim_probe(n, dim, stripe_rows=0):
     if rc != 0:
         raise MvhdpError(rc, "sim_probe: bad shape" if rc == -1 else "sim_probe: dim > 65536")
     return _sim_stats(st)
+
+
+@dataclass
+class PhraseStats:
+    """mvhdp_phrase_stats: maximal same-topic runs, phrase occurrences, distinct phrases, phrases kept, and the comparisons in which the
+    used hash bits were equal and the phrases were not."""
+    runs: int = 0
+    occurrences: int = 0
+    distinct: int = 0
+    kept: int = 0
+    hash_collisions: int = 0
+
+
+@dataclass
+class TopicPhrases:
+    """findTopicPhrases PTM:1921-1976 per topic: phrases[k] = [(key, count), ...] by count descending, equal counts by word-id sequence
+    ascending (a proper prefix first), cut at max_per_topic; key = the word-id tuple, or the words joined by a blank when a vocabulary was
+    given.  distinct[k] / occurrences[k]: the topic's phrases and the sum of their counts BEFORE the cut (count / occurrences[k] is the
+    phrase weight of PTM:2037)."""
+    phrases: list
+    distinct: np.ndarray
+    occurrences: np.ndarray
+    stats: PhraseStats = None
+
+
+def _phrase_order(table, max_per_topic):
+    """[(ids, count)] in the order of include/mvhdp.h, cut"""
+    out = sorted(table, key=lambda e: (-e[1], e[0]))
+    return out if max_per_topic < 0 else out[:max_per_topic]
+
+
+def merge_topic_phrases(results, max_per_topic):
+    """The TopicPhrases of a corpus from the UNCUT ones (max_per_topic < 0, no vocabulary) of its document shards: equal keys summed, the
+    same order, the same cut.  Phrases never cross an entity, so for document shards this is exact.  No device."""
+    results = list(results)
+    K = len(results[0].phrases)
+    merged = []
+    for k in range(K):
+        acc = {}
+        for r in results:
+            if len(r.phrases) != K:
+                raise ValueError("merge_topic_phrases: the results disagree on the number of topics")
+            for ids, c in r.phrases[k]:
+                if not isinstance(ids, tuple):
+                    raise ValueError("merge_topic_phrases: results with a vocabulary cannot be merged (ask for word-id tuples)")
+                acc[ids] = acc.get(ids, 0) + int(c)
+        merged.append(acc)
+    for r in results:
+        if any(len(r.phrases[k]) != int(r.distinct[k]) for k in range(K)):
+            raise ValueError("merge_topic_phrases: a result was cut (max_per_topic must be < 0 on the shards)")
+    distinct = np.array([len(a) for a in merged], dtype=np.int64)
+    occurrences = np.sum([np.asarray(r.occurrences, dtype=np.int64) for r in results], axis=0).astype(np.int64)
+    phrases = [_phrase_order(list(a.items()), int(max_per_topic)) for a in merged]
+    st = PhraseStats(runs=sum(r.stats.runs for r in results if r.stats), occurrences=int(occurrences.sum()), distinct=int(distinct.sum()),
+                     kept=sum(len(p) for p in phrases), hash_collisions=sum(r.stats.hash_collisions for r in results if r.stats))
+    return TopicPhrases(phrases, distinct, occurrences, st)
 
 
 def round_similarity(sim):
@@ -468,6 +525,36 @@ class NativeSampler:
             self._ck(rc)
             n = cnt.value
             return i[:n].copy(), j[:n].copy(), sim[:n].copy(), _sim_stats(st)
+
+    def topic_phrases_raw(self, max_per_topic=20, hash_bits=0):
+        """mvhdp_topic_phrases as arrays: (topic_off [K+1], word_off [kept+1], words, counts [kept], distinct [K], occurrences [K], stats).
+        Two calls, sizes then arrays (the walk runs twice, as for doc_topics_top)."""
+        a = PhraseArgsC(int(max_per_topic), int(hash_bits))
+        np_, nw, st = C.c_int64(), C.c_int64(), PhraseStatsC()
+        topic_off = np.zeros(self.K + 1, dtype=np.int64)
+        distinct = np.zeros(self.K, dtype=np.int64)
+        occ = np.zeros(self.K, dtype=np.int64)
+        self._ck(self.L.mvhdp_topic_phrases(self.h, C.byref(a), 0, 0, None, None, None, None, None, None, C.byref(np_), C.byref(nw), None))
+        n, w = np_.value, nw.value
+        word_off = np.zeros(n + 1, dtype=np.int64)
+        words = np.zeros(w, dtype=np.int32)
+        counts = np.zeros(n, dtype=np.int32)
+        self._ck(self.L.mvhdp_topic_phrases(self.h, C.byref(a), n, w, _ptr(topic_off), _ptr(word_off), _ptr(words) if w else None, _ptr(counts),
+                                            _ptr(distinct), _ptr(occ), C.byref(np_), C.byref(nw), C.byref(st)))
+        return topic_off, word_off, words, counts, distinct, occ, PhraseStats(**{f: getattr(st, f) for f, _ in PhraseStatsC._fields_})
+
+    def topic_phrases(self, max_per_topic=20, vocabulary=None, hash_bits=0):
+        """findTopicPhrases PTM:1921-1976 on the device (what saveTopicsandExperiment stores, PTM:1555-1586, with max_per_topic = 20): a
+        TopicPhrases.  vocabulary: the view-0 words, to get the reference's keys (the words joined by a blank) instead of word-id tuples."""
+        topic_off, word_off, words, counts, distinct, occ, st = self.topic_phrases_raw(max_per_topic, hash_bits)
+        phrases = []
+        for k in range(self.K):
+            row = []
+            for p in range(int(topic_off[k]), int(topic_off[k + 1])):
+                ids = tuple(int(x) for x in words[word_off[p]:word_off[p + 1]])
+                row.append((ids if vocabulary is None else " ".join(str(vocabulary[i]) for i in ids), int(counts[p])))
+            phrases.append(row)
+        return TopicPhrases(phrases, distinct, occ, st)
 
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
     def top_words(self, m, n):
@@ -850,6 +937,14 @@ class NativeGroup:
         rc, d = _run_diagnostics(self.L, self.L.mvhdp_group_diagnostics, self.g, s0.K, s0.V[0], s0.M, num_top_words, vocabulary, word_length)
         self._ck(rc)
         return d
+
+    def topic_phrases(self, max_per_topic=20, vocabulary=None):
+        """NativeSampler.topic_phrases of the sharded corpus, over the LOCAL members: every member's uncut lists merged
+        (merge_topic_phrases).  A group of rank processes merges its ranks' results the same way on the host side."""
+        r = merge_topic_phrases([s.topic_phrases(-1) for s in self.members], max_per_topic)
+        if vocabulary is not None:
+            r.phrases = [[(" ".join(str(vocabulary[i]) for i in ids), c) for ids, c in row] for row in r.phrases]
+        return r
 
     def sweep(self, sweep_idx, seed, flags=0):
         """One sweep of the whole model; the list of the local members' statistics."""
