@@ -384,6 +384,60 @@ int mvhdp_topic_phrases(mvhdp_handle h, const mvhdp_phrase_args* a, int64_t cap_
                         int64_t* distinct /*[K]*/, int64_t* occurrences /*[K]*/,
                         int64_t* n_phrases, int64_t* n_words, mvhdp_phrase_stats* stats /* or NULL */);
 
+/* Held-out evaluation: the left-to-right document likelihood (Wallach, Murray, Salakhutdinov, Mimno 2009) as MALLET's
+ * MarginalProbEstimator.evaluateLeftToRight / leftToRight runs it (mallet-2.0.8 class file), with the arguments getMALLETProbEstimator
+ * passes (PTM:3470-3478) -- what replaces getMALLETProbEstimator().evaluateLeftToRight(testing, particles, resample, null).  Defined by its
+ * mathematics and this library's random streams; where it departs from MALLET's bytes is said below.
+ * The model is view m (0: the only view the reference evaluates) as the handle holds it, frozen for the call: n_wk[m], n_k[m], beta[m],
+ * alpha[m][0..K), gamma[m], alphaSum[m].  alphaSum' = gamma[m] * alphaSum[m]; alpha_k = alpha[m][k], NOT multiplied by gamma (the reference
+ * passes alpha[0] unscaled beside gamma[0] * alphaSum[0], PTM:3476, and so do we); args.alpha ([K]) with args.alpha_sum replaces both for a
+ * caller who wants them consistent.  betaSum = beta[m] * V_m, as MALLET's constructor computes it.  Inactive topics take part with whatever
+ * alpha they hold.  A vectors mix (mvhdp_set_vectors_mix) is ignored: the estimator knows nothing of it.  The held-out documents come with
+ * the call; the handle's corpus and assignments are neither needed nor touched.
+ * Arithmetic, all fp64, every operation rounded on its own (no fused multiply-add), chosen so that a visit has no divide:
+ *   rinv[k] = 1.0 / (n_k[k] + betaSum), once per call;  phi_w[k] = (n_wk[w][k] + beta) * rinv[k];  wt[k] = (alpha_k + n_dk[k]) * phi_w[k].
+ * Document d (global index doc_base + d), particle r in 0 .. particles - 1: n_dk = 0, tokensSoFar = 0; for limit = 0 .. L - 1:
+ *   1. if resample: for every position < limit whose token is in vocabulary (< V_m): take z[position] out of n_dk, form wt for that token,
+ *      draw a topic, put it back;
+ *   2. the token at limit, out of vocabulary: nothing (no probability, no tokensSoFar increment, no draw); else
+ *      p_r[limit] = total / (alphaSum' + tokensSoFar), then tokensSoFar++, z[limit] drawn from wt and added to n_dk.
+ * S[n] = sum over r ascending of p_r[n] (0 for an out-of-vocabulary position); the document's log-likelihood is the sum over n with
+ * S[n] > 0.0 (the guard of evaluateLeftToRight) of (log S[n] - log particles); the total adds the documents in ascending order.
+ * Summation order (part of the contract; tests/native/ltr_ref.c restates this paragraph).  Let T be the smallest of 1, 2, 4, 8, 16, 32 with
+ * 64 T >= K.  Lane l (0..63) owns the topics l T + j, j = 0 .. T - 1 (those >= K have weight 0 and are never drawn).  Its prefix sums are
+ * pre(l, 0) = wt[l T], pre(l, j) = pre(l, j - 1) + wt[l T + j]; its lane sum is s_l = pre(l, T - 1).  The 64 lane sums are scanned as
+ * mvhdp_wave.h's wave_incl_scan_d_dpp does: four steps s = 1, 2, 4, 8 in which every lane with (l mod 16) >= s adds the value lane l - s held
+ * before the step; then lanes 16..31 add the value of lane 15 and lanes 48..63 that of lane 47; then lanes 32..63 add the value of lane 31.
+ * total = the scanned value of lane 63; excl(l) = the scanned value of lane l - 1, 0.0 for lane 0; the running sum at topic l T + j is
+ * excl(l) + pre(l, j).  A draw: u = bits_to_unit(x0, x1) of Philox4x32-10 with key = seed (low word, high word) and counter
+ * (low 32 bits of doc_base + d,  r + (high 32 bits of doc_base + d) * 2^20,  limit,  position), position = limit for the draw at the limit;
+ * the topic is the first one in ascending order with wt > 0.0 whose running sum exceeds u * total; if there is none, the last topic with
+ * wt > 0.0 (topic 0 if every weight is 0).  The per-document sum: with the terms t_n = log S[n] - log particles of the positions that pass
+ * the guard, lane l adds t_l, t_(l + 64), .. in ascending order from 0.0, and the 64 lane values are combined by a butterfly (each lane adds
+ * the value of lane l xor 32, then 16, 8, 4, 2, 1); the device's log is within an ulp of a correctly rounded one, not equal to it.
+ * Departures from MALLET: its typeTopicCounts argument is decoded as packed (count << topicBits) | topic words, which the reference's dense
+ * int[V][K] rows are not -- we read n_wk[w][k]; MALLET walks SparseLDA buckets (smoothing, document, word), which gives the same
+ * distribution with a different map from u to topic -- we do not reproduce that map; its Randoms is unseeded -- ours is the counter above;
+ * it divides per topic -- we multiply by rinv (an ulp of difference per weight at most).
+ * doc_off[0] = 0 and doc_off[num_docs] tokens; a token >= V_m is out of vocabulary.  doc_ll [num_docs], position_sum [N] (S[n]),
+ * doc_tokens [num_docs] (in-vocabulary tokens) and stats may each be NULL.  stats.visits counts the weight vectors formed, over all
+ * particles: sum over documents and limits of (in-vocabulary positions < limit, if resample) + (1 if the limit's token is in vocabulary).
+ * Pending work on the handle's stream lands first.  The counts are taken AS THE HANDLE HOLDS THEM: unlike mvhdp_diagnostics this call
+ * does not refuse counts that have gone stale (assignments replaced since the last count) or that lack the pending deltas of a
+ * MVHDP_SWEEP_NO_APPLY sweep -- it evaluates the table as it stands, i.e. the model before that sweep; call mvhdp_apply_delta (or
+ * mvhdp_build_counts) first to evaluate the newer one.  MVHDP_ERR_STATE: no counts yet (mvhdp_build_counts, mvhdp_set_counts, or a sweep) or
+ * no hyper-parameters; MVHDP_ERR_UNSUPPORTED: K > 2048 (checked with the arguments; mvhdp_create admits no such K); MVHDP_ERR_INVALID_ARG: m out of range, particles < 1 (or > 2^20), a negative token, a doc_off that does not start
+ * at 0 or decreases, a negative doc_base; -1 for a NULL handle.  Every output is untouched on error.  The counts, the assignments, the tuning
+ * and what mvhdp_counts_written / mvhdp_trees_current would report are what they were; two calls with the same arguments return the same bytes.
+ * Cost: sum over documents of particles * L (L + 1) / 2 visits with resample, particles * L without; each visit gathers one count row. */
+typedef struct { int32_t m, particles, resample; uint64_t seed; int64_t doc_base;
+                 const double* alpha /*[K] or NULL*/; double alpha_sum; } mvhdp_heldout_args;
+typedef struct { double log_likelihood; int64_t tokens /* in vocabulary */, oov, visits; } mvhdp_heldout_stats;
+int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_args* a, int64_t num_docs,
+        const int64_t* doc_off /*[D+1]*/, const int32_t* tokens /*[N]*/,
+        double* doc_ll /*[D] or NULL*/, double* position_sum /*[N] or NULL: S[n], 0 for OOV*/,
+        int64_t* doc_tokens /*[D] or NULL*/, mvhdp_heldout_stats* stats);
+
 /* ---- topic diagnostics: the step after training (FastQMVWVTopicModelDiagnostics, DIAG = MVTopicModel/FastQMVWVTopicModelDiagnostics.java;
  * SciTopicFlow builds it with N = 20 right after the save, whose saveExperiment / saveTopicsandExperiment call
  * calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230 from PTM:1370 / PTM:1507 and getSortedWords PTM:1792-1811 per view).

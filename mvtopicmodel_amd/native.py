@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   EmbConfigC, EmbStatsC, GroupInfoC, HyperC, MvhdpError, PhraseArgsC, PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
+                   EmbConfigC, EmbStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, PhraseArgsC, PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
@@ -190,6 +190,33 @@ def merge_topic_phrases(results, max_per_topic):
     st = PhraseStats(runs=sum(r.stats.runs for r in results if r.stats), occurrences=int(occurrences.sum()), distinct=int(distinct.sum()),
                      kept=sum(len(p) for p in phrases), hash_collisions=sum(r.stats.hash_collisions for r in results if r.stats))
     return TopicPhrases(phrases, distinct, occurrences, st)
+
+
+@dataclass
+class HeldoutResult:
+    """mvhdp_heldout_left_to_right: the left-to-right estimate of log p(held-out documents | model).  doc_log_likelihood [D];
+    position_sum [N] = S[n], the particles' p(w_n | w_<n) added up (0 at an out-of-vocabulary position), or None; doc_tokens [D] and
+    tokens count the in-vocabulary tokens; visits = weight vectors formed over all particles."""
+    log_likelihood: float
+    doc_log_likelihood: np.ndarray
+    position_sum: np.ndarray
+    doc_tokens: np.ndarray
+    tokens: int = 0
+    oov: int = 0
+    visits: int = 0
+    particles: int = 0
+
+    @property
+    def perplexity(self):
+        return float(np.exp(-self.log_likelihood / self.tokens)) if self.tokens else float("nan")
+
+
+def _heldout_docs(doc_off, tokens):
+    doc_off = np.ascontiguousarray(doc_off, dtype=np.int64)
+    tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+    if doc_off.ndim != 1 or len(doc_off) < 1 or len(tokens) != int(doc_off[-1]):
+        raise ValueError("doc_off/tokens shape mismatch")
+    return doc_off, tokens
 
 
 def round_similarity(sim):
@@ -555,6 +582,27 @@ class NativeSampler:
                 row.append((ids if vocabulary is None else " ".join(str(vocabulary[i]) for i in ids), int(counts[p])))
             phrases.append(row)
         return TopicPhrases(phrases, distinct, occ, st)
+
+    def heldout_left_to_right(self, doc_off, tokens, particles=10, resample=True, seed=0, m=0, doc_base=0, alpha=None, alpha_sum=None,
+                              want_position_sums=False):
+        """getMALLETProbEstimator().evaluateLeftToRight(testing, particles, resample, null) (PTM:3470-3478) on the device, as
+        include/mvhdp.h defines it: a HeldoutResult.  The documents are passed here; a token >= V[m] is out of vocabulary.  alpha ([K])
+        with alpha_sum replaces the handle's alpha[m] and gamma[m] * alphaSum[m]."""
+        doc_off, tokens = _heldout_docs(doc_off, tokens)
+        D, N = len(doc_off) - 1, len(tokens)
+        a = HeldoutArgsC(int(m), int(particles), 1 if resample else 0, int(seed), int(doc_base), None, 0.0)
+        keep = None
+        if alpha is not None:
+            keep = np.ascontiguousarray(alpha, dtype=np.float64)
+            if keep.shape != (self.K,) or alpha_sum is None:
+                raise ValueError("alpha: K values and alpha_sum, together")
+            a.alpha, a.alpha_sum = keep.ctypes.data, float(alpha_sum)
+        doc_ll = np.zeros(D, dtype=np.float64)
+        pos = np.zeros(N, dtype=np.float64) if want_position_sums else None
+        doc_tokens = np.zeros(D, dtype=np.int64)
+        st = HeldoutStatsC()
+        self._ck(self.L.mvhdp_heldout_left_to_right(self.h, C.byref(a), D, _ptr(doc_off), _ptr(tokens), _ptr(doc_ll), _ptr(pos), _ptr(doc_tokens), C.byref(st)))
+        return HeldoutResult(st.log_likelihood, doc_ll, pos, doc_tokens, st.tokens, st.oov, st.visits, int(particles))
 
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
     def top_words(self, m, n):
@@ -945,6 +993,30 @@ class NativeGroup:
         if vocabulary is not None:
             r.phrases = [[(" ".join(str(vocabulary[i]) for i in ids), c) for ids, c in row] for row in r.phrases]
         return r
+
+    def heldout_left_to_right(self, doc_off, tokens, particles=10, resample=True, seed=0, m=0, doc_base=0, alpha=None, alpha_sum=None,
+                              want_position_sums=False):
+        """NativeSampler.heldout_left_to_right with the held-out documents split over the LOCAL members in contiguous ranges of about equal
+        sum of L^2 (the work of a document), each member told the global index of its first document.  Every member holds the whole
+        counts and documents are independent, so every per-document value is the single handle's, bit for bit; the total adds them in
+        document order on the host, as the library does."""
+        doc_off, tokens = _heldout_docs(doc_off, tokens)
+        D, n = len(doc_off) - 1, len(self.members)
+        work = np.concatenate([[0.0], np.cumsum(np.diff(doc_off).astype(np.float64) ** 2)])
+        cuts = [0] + [int(np.searchsorted(work, work[-1] * i / n, side="left")) for i in range(1, n)] + [D]
+        cuts = [min(max(c, 0), D) for c in np.maximum.accumulate(cuts)]
+        parts = []
+        for s, d0, d1 in zip(self.members, cuts[:-1], cuts[1:]):
+            t0, t1 = int(doc_off[d0]), int(doc_off[d1])
+            parts.append(s.heldout_left_to_right(doc_off[d0:d1 + 1] - t0, tokens[t0:t1], particles, resample, seed, m, int(doc_base) + d0, alpha, alpha_sum,
+                                                 want_position_sums))
+        doc_ll = np.concatenate([p.doc_log_likelihood for p in parts])
+        total = 0.0
+        for x in doc_ll:
+            total = total + float(x)
+        return HeldoutResult(total, doc_ll, np.concatenate([p.position_sum for p in parts]) if want_position_sums else None,
+                             np.concatenate([p.doc_tokens for p in parts]), sum(p.tokens for p in parts), sum(p.oov for p in parts),
+                             sum(p.visits for p in parts), int(particles))
 
     def sweep(self, sweep_idx, seed, flags=0):
         """One sweep of the whole model; the list of the local members' statistics."""
