@@ -1,8 +1,10 @@
 // mvhdp_jni.cpp — JNI shim between org.madgik.MVTopicModel.NativeSampler and the C ABI
-// of libmvhdp.so (include/mvhdp.h).  NOT part of the build (no JDK there); a host builds it with
-//   g++ -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -Iinclude
-//       mvtopicmodel_amd/java/mvhdp_jni.cpp -Lmvtopicmodel_amd/lib -lmvhdp -o libmvhdp_jni.so      (one command line)
-// The tests compile this file unmodified against a declaration-only jni.h (tests/native/jni_stub), link it against a test-side
+// of libmvhdp.so (include/mvhdp.h).  NOT part of the build (no JDK there); a host builds it, with the three shim sources beside it, with
+//   g++ -std=c++17 -shared -fPIC -I$JAVA_HOME/include -I$JAVA_HOME/include/linux -Iinclude
+//       mvtopicmodel_amd/java/mvhdp_jni.cpp mvtopicmodel_amd/java/mvhdp_sim_jni.cpp mvtopicmodel_amd/java/mvhdp_phrases_jni.cpp
+//       mvtopicmodel_amd/java/mvhdp_heldout_jni.cpp -Lmvtopicmodel_amd/lib -lmvhdp -o libmvhdp_jni.so      (one command line)
+// What the four sources share -- the handle registry, the pins, the exceptions, the array wrappers -- is mvhdp_jni_common.h.
+// The tests compile the sources unmodified against a declaration-only jni.h (tests/native/jni_stub), link them against a test-side
 // JNIEnv (tests/native/fake_jvm.cpp) and run every entry: tests/test_jni_fake_jvm.py without a device, tests/test_gpu_jni.py with one.
 //
 // Arrays cross with Get<Type>ArrayElements / Release<Type>ArrayElements, never with GetPrimitiveArrayCritical: every
@@ -11,128 +13,15 @@
 // calls may copy; the library copies once more into HBM, and the Java arrays are free to move meanwhile.  Every array
 // length is checked against the shape the handle was created with before the library sees a pointer.
 // A negative status becomes a RuntimeException carrying mvhdp_last_error().
-#include <jni.h>
-
-#include <condition_variable>
-#include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <set>
-#include <vector>
 
-#include "mvhdp.h"
+#include "mvhdp_jni_common.h"
 
-namespace {
-
-struct Shard {                       // what the jlong handle points to: the library handle plus the shape for the checks
-    mvhdp_handle h = nullptr;
-    int K = 0, M = 0;
-    int V[MVHDP_MAX_MODALITIES] = {};
-    jlong D = -1;
-    jlong N[MVHDP_MAX_MODALITIES] = {};
-    jlong embR = 0;                  // rows of the embedding matrix (V_0, + K with topics); 0: none (nEmbInit .. nEmbRelease)
-    int embC = 0, embK = 0;          //   its columns, its topic rows
-    int pins = 0;                    // JNI calls currently inside the library on this handle (guarded by g_reg_mutex)
-};
-
-// Every Shard (and group) the shim has handed to Java is listed here; a jlong that is not listed -- closed already, e.g. by a
-// finalizer racing an explicit close() -- is refused instead of dereferenced.  A call that found its object PINS it for its
-// duration: close() takes the object out of the registry at once (no new call can find it) and then waits until the calls already
-// inside the library have returned before it frees anything -- a close() racing a sweep on another thread cannot pull the handle
-// from under it.
-std::mutex g_reg_mutex;
-std::condition_variable g_reg_cv;
-std::set<void*> g_shards, g_groups;
-
-struct Group {                        // an mvhdp_group, how many members it has in this process, and the model's shape for the checks
-    mvhdp_group g = nullptr;
-    int members = 0;
-    int K = 0, M = 0;                 // of the member Shards (validate_members: every member holds the same shape)
-    std::vector<Shard*> shards;       // the members, PINNED from nGroupCreate to nGroupDestroy: nDestroy of a member (a finalizer, another thread)
-                                      // waits for its pins, so a member cannot be destroyed under a group that still names it
-    int pins = 0;
-};
-
-template <class T>
-struct Pin {
-    T* s = nullptr;
-    Pin(std::set<void*>& reg, jlong p)
-    {
-        std::lock_guard<std::mutex> lk(g_reg_mutex);
-        if (reg.count(reinterpret_cast<void*>(p))) { s = reinterpret_cast<T*>(p); s->pins++; }
-    }
-    ~Pin()
-    {
-        if (!s) return;
-        std::lock_guard<std::mutex> lk(g_reg_mutex);
-        if (--s->pins == 0) g_reg_cv.notify_all();
-    }
-    Pin(const Pin&) = delete;
-    Pin& operator=(const Pin&) = delete;
-};
-struct ShardPin : Pin<Shard> { explicit ShardPin(jlong p) : Pin<Shard>(g_shards, p) {} };
-struct GroupPin : Pin<Group> { explicit GroupPin(jlong p) : Pin<Group>(g_groups, p) {} };
-
-// close(): out of the registry under the lock, then wait for the calls that are still inside
-template <class T>
-T* unregister_and_drain(std::set<void*>& reg, jlong p)
-{
-    std::unique_lock<std::mutex> lk(g_reg_mutex);
-    auto it = reg.find(reinterpret_cast<void*>(p));
-    if (it == reg.end()) return nullptr;
-    T* s = reinterpret_cast<T*>(*it);
-    reg.erase(it);
-    g_reg_cv.wait(lk, [&] { return s->pins == 0; });
-    return s;
-}
-
-void throw_msg(JNIEnv* env, const char* cls, const char* msg)
-{
-    jclass c = env->FindClass(cls);
-    if (c) env->ThrowNew(c, msg);
-}
-
-void throw_rt(JNIEnv* env, mvhdp_handle h, int rc, const char* what)
-{
-    char msg[640];
-    snprintf(msg, sizeof msg, "%s failed (%d): %s", what, rc, mvhdp_last_error(h));
-    throw_msg(env, "java/lang/RuntimeException", msg);
-}
-
-bool bad_len(JNIEnv* env, jarray a, jlong want, const char* what)
-{
-    if (a && env->GetArrayLength(a) == want) return false;
-    char msg[256];
-    snprintf(msg, sizeof msg, "%s: array of length %lld expected, got %lld", what, (long long)want, a ? (long long)env->GetArrayLength(a) : -1LL);
-    throw_msg(env, "java/lang/IllegalArgumentException", msg);
-    return true;
-}
-
-// RAII over Get/Release<Type>ArrayElements (mode 0: copy back and free; JNI_ABORT: input only)
-// Several of them are declared side by side: once one Get has failed (OutOfMemoryError pending) the next ones take nothing -- JNI allows
-// no Get while an exception is pending -- and report failed() as well.
-struct Ints {
-    JNIEnv* env; jintArray a; jint* p; jint mode;
-    Ints(JNIEnv* e, jintArray arr, jint m) : env(e), a(arr), p(arr && !e->ExceptionCheck() ? e->GetIntArrayElements(arr, nullptr) : nullptr), mode(m) {}
-    ~Ints() { if (a && p) env->ReleaseIntArrayElements(a, p, mode); }
-    bool failed() const { return a && !p; }
-};
-struct Longs {
-    JNIEnv* env; jlongArray a; jlong* p; jint mode;
-    Longs(JNIEnv* e, jlongArray arr, jint m) : env(e), a(arr), p(arr && !e->ExceptionCheck() ? e->GetLongArrayElements(arr, nullptr) : nullptr), mode(m) {}
-    ~Longs() { if (a && p) env->ReleaseLongArrayElements(a, p, mode); }
-    bool failed() const { return a && !p; }
-};
-struct Doubles {
-    JNIEnv* env; jdoubleArray a; jdouble* p; jint mode;
-    Doubles(JNIEnv* e, jdoubleArray arr, jint m) : env(e), a(arr), p(arr && !e->ExceptionCheck() ? e->GetDoubleArrayElements(arr, nullptr) : nullptr), mode(m) {}
-    ~Doubles() { if (a && p) env->ReleaseDoubleArrayElements(a, p, mode); }
-    bool failed() const { return a && !p; }
-};
-
-static_assert(sizeof(jint) == sizeof(int32_t) && sizeof(jlong) == sizeof(int64_t) && sizeof(jdouble) == sizeof(double), "JNI primitive sizes");
-
-}  // namespace
+using mvhdp_jni::Shard; using mvhdp_jni::Group; using mvhdp_jni::ShardPin; using mvhdp_jni::GroupPin;
+using mvhdp_jni::pin; using mvhdp_jni::unpin; using mvhdp_jni::unregister_and_drain;
+using mvhdp_jni::g_reg_mutex; using mvhdp_jni::g_shards; using mvhdp_jni::g_groups;
+using mvhdp_jni::throw_msg; using mvhdp_jni::throw_rt; using mvhdp_jni::bad_len;
+using mvhdp_jni::Ints; using mvhdp_jni::Longs; using mvhdp_jni::Doubles;
 
 extern "C" {
 
@@ -169,8 +58,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDestroy(JNIEn
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetCorpus(JNIEnv* env, jclass, jlong p, jint m, jlongArray docOff, jintArray tokens)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M || !docOff || env->GetArrayLength(docOff) < 1) { throw_msg(env, "java/lang/IllegalArgumentException", "setCorpus: bad view or docOff"); return; }
     const jsize D = env->GetArrayLength(docOff) - 1;
     int rc;
@@ -190,8 +79,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetCorpus(JNI
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetAssignments(JNIEnv* env, jclass, jlong p, jint m, jintArray z)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M) { throw_msg(env, "java/lang/IllegalArgumentException", "setAssignments: bad view"); return; }
     if (s->N[m] > 0 && bad_len(env, z, s->N[m], "setAssignments")) return;
     int rc;
@@ -203,8 +92,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetAssignment
 // which entities HAVE the view (Assignments[m] != null) even when its FeatureSequence is empty: mvhdp_set_view_presence
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetViewPresence(JNIEnv* env, jclass, jlong p, jint m, jbooleanArray present)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M) { throw_msg(env, "java/lang/IllegalArgumentException", "setViewPresence: bad view"); return; }
     int rc;
     if (!present) rc = mvhdp_set_view_presence(s->h, m, nullptr);
@@ -219,8 +108,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetViewPresen
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetAssignments(JNIEnv* env, jclass, jlong p, jint m, jintArray z)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M) { throw_msg(env, "java/lang/IllegalArgumentException", "getAssignments: bad view"); return; }
     if (s->N[m] == 0) return;
     if (bad_len(env, z, s->N[m], "getAssignments")) return;
@@ -232,8 +121,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetAssignment
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetHyper(JNIEnv* env, jclass, jlong p, jobjectArray alpha, jdoubleArray alphaSum,
         jdoubleArray beta, jdoubleArray betaSum, jdoubleArray gamma, jobjectArray p_a, jobjectArray p_b, jbooleanArray inactive)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     const jsize M = s->M, K1 = s->K + 1;
     if (bad_len(env, alpha, M, "setHyper alpha") || bad_len(env, p_a, M, "setHyper p_a") || bad_len(env, p_b, M, "setHyper p_b") ||
         bad_len(env, alphaSum, M, "setHyper alphaSum") || bad_len(env, beta, M, "setHyper beta") ||
@@ -271,17 +160,17 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetHyper(JNIE
 }
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nBuildCounts(JNIEnv* env, jclass, jlong p)
-{ ShardPin pin_(p); Shard* s = pin_.s; if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+{ ShardPin pin_(env, p); Shard* s = pin_.s; if (!s) return;
   int rc = mvhdp_build_counts(s->h); if (rc) throw_rt(env, s->h, rc, "mvhdp_build_counts"); }
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nBuildTrees(JNIEnv* env, jclass, jlong p)
-{ ShardPin pin_(p); Shard* s = pin_.s; if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+{ ShardPin pin_(env, p); Shard* s = pin_.s; if (!s) return;
   int rc = mvhdp_build_trees(s->h); if (rc) throw_rt(env, s->h, rc, "mvhdp_build_trees"); }
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetCounts(JNIEnv* env, jclass, jlong p, jint m, jintArray nwk, jintArray nk)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M) { throw_msg(env, "java/lang/IllegalArgumentException", "getCounts: bad view"); return; }
     if ((nwk && bad_len(env, nwk, (jlong)s->V[m] * s->K, "getCounts typeTopicCounts")) || (nk && bad_len(env, nk, s->K, "getCounts tokensPerTopic"))) return;
     int rc;
@@ -292,8 +181,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetCounts(JNI
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetDocTopicHist(JNIEnv* env, jclass, jlong p, jint m, jintArray hist, jint histLen, jintArray lens)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M || histLen < 1) { throw_msg(env, "java/lang/IllegalArgumentException", "getDocTopicHist: bad view or length"); return; }
     if (hist && bad_len(env, hist, (jlong)s->K * histLen, "getDocTopicHist hist")) return;
     int rc;
@@ -304,8 +193,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetDocTopicHi
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetAlpha(JNIEnv* env, jclass, jlong p, jdoubleArray alphaFlat, jbooleanArray inactive)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_len(env, alphaFlat, (jlong)s->M * (s->K + 1), "getAlpha alpha") || bad_len(env, inactive, s->K, "getAlpha inactive")) return;
     std::vector<double> a(static_cast<size_t>(s->M) * (s->K + 1));
     std::vector<uint8_t> ina(static_cast<size_t>(s->K));
@@ -317,8 +206,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetAlpha(JNIE
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSweep(JNIEnv* env, jclass, jlong p, jint sweepIdx, jlong seed, jint flags, jdoubleArray pOverride, jobject out)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     // (D is -1 until setCorpus: there is no [D][M][M] to check against yet, and the library would refuse the sweep anyway)
     if (pOverride && s->D < 0) { throw_msg(env, "java/lang/IllegalStateException", "sweep pOverride: setCorpus has not been called"); return; }
     if (pOverride && bad_len(env, pOverride, s->D * static_cast<jlong>(s->M) * s->M, "sweep pOverride [D][M][M]")) return;
@@ -345,13 +234,13 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSweep(JNIEnv*
 }
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nApplyDelta(JNIEnv* env, jclass, jlong p, jint topic, jint modality)
-{ ShardPin pin_(p); Shard* s = pin_.s; if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+{ ShardPin pin_(env, p); Shard* s = pin_.s; if (!s) return;
   int rc = mvhdp_apply_delta(s->h, topic, modality); if (rc) throw_rt(env, s->h, rc, "mvhdp_apply_delta"); }
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nModelLogLikelihood(JNIEnv* env, jclass, jlong p, jdoubleArray out)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_len(env, out, s->M, "modelLogLikelihood")) return;
     double ll[MVHDP_MAX_MODALITIES];
     int rc = mvhdp_model_log_likelihood(s->h, ll);
@@ -370,8 +259,8 @@ static void stats_to_longs(const mvhdp_sweep_stats& st, jlong* o)
 // the iteration loop PTM:1146-1239 without a host round trip per iteration (mvhdp_sweep_many)
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSweepMany(JNIEnv* env, jclass, jlong p, jint firstIdx, jint n, jlong seed, jint flags, jlongArray statsFlat)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (n < 0 || (statsFlat && bad_len(env, statsFlat, (jlong)n * 8, "sweepMany stats [n][8]"))) return;
     std::vector<mvhdp_sweep_stats> st(static_cast<size_t>(n > 0 ? n : 1));
     int rc = mvhdp_sweep_many(s->h, static_cast<uint32_t>(firstIdx), n, static_cast<uint64_t>(seed), static_cast<uint32_t>(flags), st.data());
@@ -387,8 +276,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSweepMany(JNI
 // doubles = {primaryMinShare, walkTheta[8], treeBranchShare[8]}
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetTuning(JNIEnv* env, jclass, jlong p, jintArray ints, jdoubleArray doubles)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_len(env, ints, 8, "getTuning ints") || bad_len(env, doubles, 17, "getTuning doubles")) return;
     mvhdp_tuning t;
     int rc = mvhdp_get_tuning(s->h, &t);
@@ -403,8 +292,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetTuning(JNI
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetTuning(JNIEnv* env, jclass, jlong p, jintArray ints, jdoubleArray doubles)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_len(env, ints, 8, "setTuning ints") || bad_len(env, doubles, 17, "setTuning doubles")) return;
     jint iv[8]; jdouble dv[17];
     env->GetIntArrayRegion(ints, 0, 8, iv);
@@ -439,10 +328,9 @@ JNIEXPORT jlong JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupCreate(
     env->GetLongArrayRegion(handles, 0, n, hp.data());
     std::vector<mvhdp_handle> hs;
     Group* gr = new Group();
-    auto unpin_all = [&]() { std::lock_guard<std::mutex> lk(g_reg_mutex); for (Shard* s : gr->shards) if (--s->pins == 0) g_reg_cv.notify_all(); gr->shards.clear(); };
+    auto unpin_all = [&]() { for (Shard* s : gr->shards) unpin(s); gr->shards.clear(); };
     for (jsize i = 0; i < n; i++) {
-        Shard* s = nullptr;
-        { std::lock_guard<std::mutex> lk(g_reg_mutex); if (g_shards.count(reinterpret_cast<void*>(hp[i]))) { s = reinterpret_cast<Shard*>(hp[i]); s->pins++; } }
+        Shard* s = pin<Shard>(g_shards, hp[i]);
         if (!s) { unpin_all(); delete gr; throw_msg(env, "java/lang/IllegalStateException", "groupCreate: a member is closed"); return 0; }
         gr->shards.push_back(s);
         hs.push_back(s->h);
@@ -466,16 +354,14 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupUniqueId
 
 JNIEXPORT jlong JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupCreateRank(JNIEnv* env, jclass, jlong p, jbyteArray id, jint rank, jint nranks)
 {
-    Shard* s = nullptr;
-    { std::lock_guard<std::mutex> lk(g_reg_mutex); if (g_shards.count(reinterpret_cast<void*>(p))) { s = reinterpret_cast<Shard*>(p); s->pins++; } }   // (kept until nGroupDestroy)
+    Shard* s = pin<Shard>(g_shards, p);                           // (kept until nGroupDestroy)
     if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return 0; }
-    auto unpin = [&]() { std::lock_guard<std::mutex> lk(g_reg_mutex); if (--s->pins == 0) g_reg_cv.notify_all(); };
-    if (bad_len(env, id, MVHDP_UNIQUE_ID_BYTES, "groupCreateRank id")) { unpin(); return 0; }
+    if (bad_len(env, id, MVHDP_UNIQUE_ID_BYTES, "groupCreateRank id")) { unpin(s); return 0; }
     uint8_t buf[MVHDP_UNIQUE_ID_BYTES];
     env->GetByteArrayRegion(id, 0, MVHDP_UNIQUE_ID_BYTES, reinterpret_cast<jbyte*>(buf));
     Group* gr = new Group();
     int rc = mvhdp_group_create_rank(s->h, buf, rank, nranks, &gr->g);
-    if (rc != MVHDP_OK) { unpin(); delete gr; throw_group(env, nullptr, rc, "mvhdp_group_create_rank"); return 0; }
+    if (rc != MVHDP_OK) { unpin(s); delete gr; throw_group(env, nullptr, rc, "mvhdp_group_create_rank"); return 0; }
     gr->members = 1; gr->K = s->K; gr->M = s->M; gr->shards.push_back(s);
     { std::lock_guard<std::mutex> lk(g_reg_mutex); g_groups.insert(gr); }
     return reinterpret_cast<jlong>(gr);
@@ -486,14 +372,14 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupDestroy(
     Group* gr = unregister_and_drain<Group>(g_groups, p);
     if (!gr) return;
     mvhdp_group_destroy(gr->g);
-    { std::lock_guard<std::mutex> lk(g_reg_mutex); for (Shard* s : gr->shards) if (--s->pins == 0) g_reg_cv.notify_all(); }   // the members may be closed now
+    for (Shard* s : gr->shards) unpin(s);                         // the members may be closed now
     delete gr;
 }
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupBuildCounts(JNIEnv* env, jclass, jlong p)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     int rc = mvhdp_group_build_counts(gr->g);
     if (rc) throw_group(env, gr->g, rc, "mvhdp_group_build_counts");
 }
@@ -502,8 +388,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupBuildCou
 // returns the device milliseconds of the exchange (collectives + updates + tree rebuilds)
 JNIEXPORT jdouble JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupSweep(JNIEnv* env, jclass, jlong p, jint sweepIdx, jlong seed, jint flags, jlongArray statsFlat, jintArray act)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return 0.0; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return 0.0;
     if ((statsFlat && bad_len(env, statsFlat, (jlong)gr->members * 8, "groupSweep stats [members][8]")) || (act && bad_len(env, act, 3, "groupSweep act"))) return 0.0;
     std::vector<mvhdp_sweep_stats> st(static_cast<size_t>(gr->members));
     int rc = mvhdp_group_sweep(gr->g, static_cast<uint32_t>(sweepIdx), static_cast<uint64_t>(seed), static_cast<uint32_t>(flags), st.data());
@@ -522,8 +408,8 @@ JNIEXPORT jdouble JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupSweep
 // countHistogram of optimizeBeta PTM:2295-2309
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetCountHistogram(JNIEnv* env, jclass, jlong p, jint m, jintArray hist)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M || !hist || env->GetArrayLength(hist) < 1) { throw_msg(env, "java/lang/IllegalArgumentException", "getCountHistogram: bad view or array"); return; }
     int rc;
     { Ints a(env, hist, 0); if (a.failed()) return; rc = mvhdp_get_count_histogram(s->h, m, reinterpret_cast<int32_t*>(a.p), env->GetArrayLength(hist)); }
@@ -533,8 +419,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetCountHisto
 // optimizeP PTM:2706-2792: sums [M*M]
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nViewOverlapSums(JNIEnv* env, jclass, jlong p, jdoubleArray sums)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_len(env, sums, (jlong)s->M * s->M, "viewOverlapSums")) return;
     double v[MVHDP_MAX_MODALITIES * MVHDP_MAX_MODALITIES];
     int rc = mvhdp_view_overlap_sums(s->h, v);
@@ -545,8 +431,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nViewOverlapSu
 // optimizeGamma's document level PTM:2415-2433: out = {qs, qw}
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGammaDocStatistics(JNIEnv* env, jclass, jlong p, jint m, jdouble gammaM, jlong seed, jint round, jdoubleArray out)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_len(env, out, 2, "gammaDocStatistics")) return;
     double v[2];
     int rc = mvhdp_gamma_doc_statistics(s->h, m, gammaM, static_cast<uint64_t>(seed), static_cast<uint32_t>(round), &v[0], &v[1]);
@@ -558,8 +444,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGammaDocStati
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDpTableStatistics(JNIEnv* env, jclass, jlong p, jint m, jintArray hist, jint histLen, jdoubleArray conc,
                                                                                       jlong seed, jint round, jdoubleArray mk, jbyteArray active)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M || histLen < 1) { throw_msg(env, "java/lang/IllegalArgumentException", "dpTableStatistics: bad view or histLen"); return; }
     if (bad_len(env, hist, (jlong)s->K * histLen, "dpTableStatistics hist [K][histLen]") || bad_len(env, conc, s->K, "dpTableStatistics conc") ||
         bad_len(env, mk, s->K, "dpTableStatistics mk") || bad_len(env, active, s->K, "dpTableStatistics active")) return;
@@ -576,16 +462,16 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDpTableStatis
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupDrain(JNIEnv* env, jclass, jlong p)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     int rc = mvhdp_group_drain(gr->g);
     if (rc) throw_group(env, gr->g, rc, "mvhdp_group_drain");
 }
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupAbort(JNIEnv* env, jclass, jlong p)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     int rc = mvhdp_group_abort(gr->g);
     if (rc) throw_group(env, gr->g, rc, "mvhdp_group_abort");
 }
@@ -593,8 +479,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupAbort(JN
 // modelLogLikelihood PTM:3322-3452 of the sharded model: out [M]
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupModelLogLikelihood(JNIEnv* env, jclass, jlong p, jdoubleArray out)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     if (bad_len(env, out, gr->M, "groupModelLogLikelihood: one entry per view")) return;
     double ll[MVHDP_MAX_MODALITIES] = {};
     int rc = mvhdp_group_log_likelihood(gr->g, ll);
@@ -605,8 +491,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupModelLog
 // topicDocCounts / docLengthCounts over every entity of every member: hist [K*histLen]
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupGetDocTopicHist(JNIEnv* env, jclass, jlong p, jint m, jintArray hist, jint histLen, jintArray lens)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     // (the library zero-fills and sums K * histLen entries whatever it is handed: the shape is checked HERE, against the members' K and M)
     if (m < 0 || m >= gr->M || histLen < 1) { throw_msg(env, "java/lang/IllegalArgumentException", "groupGetDocTopicHist: bad view or histLen"); return; }
     if (hist && bad_len(env, hist, (jlong)gr->K * histLen, "groupGetDocTopicHist hist [K][histLen]")) return;
@@ -618,8 +504,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupGetDocTo
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupGetCountHistogram(JNIEnv* env, jclass, jlong p, jint m, jintArray hist)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     if (m < 0 || m >= gr->M || !hist || env->GetArrayLength(hist) < 1) { throw_msg(env, "java/lang/IllegalArgumentException", "groupGetCountHistogram: bad view or empty array"); return; }
     int rc;
     { Ints a(env, hist, 0); if (a.failed()) return; rc = mvhdp_group_count_histogram(gr->g, m, reinterpret_cast<int32_t*>(a.p), env->GetArrayLength(hist)); }
@@ -628,8 +514,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupGetCount
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupViewOverlapSums(JNIEnv* env, jclass, jlong p, jdoubleArray sums)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     const jsize n = gr->M * gr->M;
     if (bad_len(env, sums, n, "groupViewOverlapSums [M][M]")) return;
     double v[MVHDP_MAX_MODALITIES * MVHDP_MAX_MODALITIES] = {};
@@ -640,8 +526,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupViewOver
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupGammaDocStatistics(JNIEnv* env, jclass, jlong p, jint m, jdouble gammaM, jlong seed, jint round, jdoubleArray out)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     if (m < 0 || m >= gr->M) { throw_msg(env, "java/lang/IllegalArgumentException", "groupGammaDocStatistics: bad view"); return; }
     if (bad_len(env, out, 2, "groupGammaDocStatistics")) return;
     double v[2];
@@ -654,8 +540,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupGammaDoc
 // getSortedWords(m) PTM:1792-1811 cut at n: typesFlat / counts [K*n] (unfilled: -1 / 0), nonzero [K]
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nTopWords(JNIEnv* env, jclass, jlong p, jint m, jint n, jintArray types, jintArray counts, jintArray nonzero)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (n < 1 || n > MVHDP_DIAG_MAX_TOP_WORDS) { throw_msg(env, "java/lang/IllegalArgumentException", "topWords: n must be 1..64"); return; }
     if (bad_len(env, types, (jlong)s->K * n, "topWords types") || bad_len(env, counts, (jlong)s->K * n, "topWords counts") || bad_len(env, nonzero, s->K, "topWords nonzero")) return;
     Ints t(env, types, 0), c(env, counts, 0), z(env, nonzero, 0);
@@ -667,8 +553,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nTopWords(JNIE
 // calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230: perView [M] = discrWeightPerModality; typeWeight [V_m] or null
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDiscrWeights(JNIEnv* env, jclass, jlong p, jdoubleArray perView, jint m, jdoubleArray typeWeight)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (m < 0 || m >= s->M) { throw_msg(env, "java/lang/IllegalArgumentException", "discrWeights: bad view"); return; }
     if (bad_len(env, perView, s->M, "discrWeights perView") || (typeWeight && bad_len(env, typeWeight, s->V[m], "discrWeights typeWeight"))) return;
     Doubles pv(env, perView, 0), tw(env, typeWeight, 0);
@@ -679,6 +565,7 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDiscrWeights(
 
 // the arrays of one mvhdp_diag_out, checked against the shape: scores [13*K], wordScores [13*K*n], codoc [K*n*n], topTypes / topCounts
 // [K*n], nonzero / rank1Docs / nonzeroDocs [K], atProportions [K*7], sumCountLogCount [K], wordTypeCounts [V_0], numTokens [1], perView [M]
+namespace {                          // (file-private: a type made of the hidden namespace's cannot be more visible than they are)
 struct DiagArrays {
     Doubles scores, wordScores; Ints codoc, topTypes, topCounts, nonzero, rank1, nzDocs, props; Doubles scl; Ints wtc; Longs ntok; Doubles perView;
     Ints wl;
@@ -695,6 +582,7 @@ struct DiagArrays {
         o.sum_count_log_count = scl.p; o.word_type_counts = wtc.p; o.num_tokens = (int64_t*)ntok.p; o.discr_weight_per_view = perView.p;
     }
 };
+}  // namespace
 
 static bool bad_diag(JNIEnv* env, jint K, jint M, jint V0, jint n, jintArray wordLength, jdoubleArray scores, jdoubleArray wordScores, jintArray codoc,
                      jintArray topTypes, jintArray topCounts, jintArray nonzero, jintArray rank1, jintArray nzDocs, jintArray props, jdoubleArray scl,
@@ -718,8 +606,8 @@ static bool bad_diag(JNIEnv* env, jint K, jint M, jint V0, jint n, jintArray wor
 // FastQMVWVTopicModelDiagnostics(model, n) DIAG:53-117 on the device (getSortedWords + collectDocumentStatistics + the score rows)
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDiagnostics(JNIEnv* env, jclass, jlong p, DIAG_PARAMS)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_diag(env, s->K, s->M, s->V[0], n, wordLength, scores, wordScores, codoc, topTypes, topCounts, nonzero, rank1, nzDocs, props, scl, wtc, ntok, perView)) return;
     DIAG_ARRAYS;
     if (da.failed()) return;
@@ -732,8 +620,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nDiagnostics(J
 // the same for the sharded model (mvhdp_group_diagnostics; collective across processes)
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGroupDiagnostics(JNIEnv* env, jclass, jlong p, DIAG_PARAMS)
 {
-    GroupPin gpin_(p); Group* gr = gpin_.s;
-    if (!gr) { throw_msg(env, "java/lang/IllegalStateException", "group is closed"); return; }
+    GroupPin gpin_(env, p); Group* gr = gpin_.s;
+    if (!gr) return;
     if (gr->shards.empty()) { throw_msg(env, "java/lang/IllegalStateException", "group has no member"); return; }
     if (bad_diag(env, gr->K, gr->M, gr->shards[0]->V[0], n, wordLength, scores, wordScores, codoc, topTypes, topCounts, nonzero, rank1, nzDocs, props, scl, wtc, ntok, perView)) return;
     DIAG_ARRAYS;
@@ -758,8 +646,8 @@ static bool emb_missing(JNIEnv* env, const Shard* s)
 // numSamples, minDocLength, sigmoidCacheSize}, doubles {samplingFactor, minExp, maxExp}; weights [R*C] or null (drawn on the device)
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbInit(JNIEnv* env, jclass, jlong p, jintArray ints, jlong tableSize, jdoubleArray doubles, jdoubleArray weights, jlong seed)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_len(env, ints, 7, "embInit ints") || bad_len(env, doubles, 3, "embInit doubles")) return;
     jint iv[7]; jdouble dv[3];
     env->GetIntArrayRegion(ints, 0, 7, iv);
@@ -782,15 +670,15 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbInit(JNIEn
 
 // countWords(data, f) TWE:341-401 (cumulative, as the reference's)
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbCountWords(JNIEnv* env, jclass, jlong p)
-{ ShardPin pin_(p); Shard* s = pin_.s; if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+{ ShardPin pin_(env, p); Shard* s = pin_.s; if (!s) return;
   int rc = mvhdp_emb_count_words(s->h); if (rc) throw_rt(env, s->h, rc, "mvhdp_emb_count_words"); }
 
 // train(data, threads, numSamples, epochs) TWE:423-483: longs [7] {wordsSoFar, wordsSampled, wordsConsidered, docsSkipped, calls,
 // negativesSkipped, lastEpochCalls}, doubles [3] {residual, lastEpochResidual, kernelMs}
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbTrain(JNIEnv* env, jclass, jlong p, jint epochs, jlong seed, jint round, jint flags, jlongArray longs, jdoubleArray doubles)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (bad_len(env, longs, 7, "embTrain longs") || bad_len(env, doubles, 3, "embTrain doubles")) return;
     mvhdp_emb_stats st;
     std::memset(&st, 0, sizeof st);
@@ -805,8 +693,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbTrain(JNIE
 // getWordVectors / getTopicVectors TWE:726-745 (rows V_0.. are the topics): [R*C] each, or null
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbGetVectors(JNIEnv* env, jclass, jlong p, jdoubleArray weights, jdoubleArray negativeWeights)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (emb_missing(env, s)) return;
     const jlong n = s->embR * s->embC;
     if ((weights && bad_len(env, weights, n, "embGetVectors weights")) || (negativeWeights && bad_len(env, negativeWeights, n, "embGetVectors negativeWeights"))) return;
@@ -818,8 +706,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbGetVectors
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSetVectors(JNIEnv* env, jclass, jlong p, jdoubleArray weights, jdoubleArray negativeWeights)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (emb_missing(env, s)) return;
     const jlong n = s->embR * s->embC;
     if ((weights && bad_len(env, weights, n, "embSetVectors weights")) || (negativeWeights && bad_len(env, negativeWeights, n, "embSetVectors negativeWeights"))) return;
@@ -832,8 +720,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSetVectors
 // wordCounts [V_0], retentionProbability [V_0] (either may be null), totalWords [1]
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbWordStats(JNIEnv* env, jclass, jlong p, jlongArray counts, jdoubleArray retention, jlongArray totalWords)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (emb_missing(env, s)) return;
     if ((counts && bad_len(env, counts, s->V[0], "embWordStats counts")) || (retention && bad_len(env, retention, s->V[0], "embWordStats retention")) ||
         bad_len(env, totalWords, 1, "embWordStats totalWords")) return;
@@ -850,8 +738,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbWordStats(
 // samplingTable[first .. first + types.length)
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSamplingTable(JNIEnv* env, jclass, jlong p, jlong first, jintArray types)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (emb_missing(env, s)) return;
     if (!types) { throw_msg(env, "java/lang/IllegalArgumentException", "embSamplingTable: types is null"); return; }
     Ints t(env, types, 0);
@@ -863,8 +751,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSamplingTa
 // CalcSoftmaxTopicWordProbabilities PTM:337-367: expDotProductValues [K*V_0] or null, sumExpValues [K] (accumulated, PTM:360) or null
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSoftmax(JNIEnv* env, jclass, jlong p, jboolean resetSums, jdoubleArray expDot, jdoubleArray sumExp)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (emb_missing(env, s)) return;
     if ((expDot && bad_len(env, expDot, (jlong)s->embK * s->V[0], "embSoftmax expDot [K*V_0]")) || (sumExp && bad_len(env, sumExp, s->embK, "embSoftmax sumExp"))) return;
     Doubles e(env, expDot, 0), m(env, sumExp, 0);
@@ -876,8 +764,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbSoftmax(JN
 // findClosest TWE:485-540: query [C]; words / wordSims [n]; topics / topicSims [n] or null
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbNearest(JNIEnv* env, jclass, jlong p, jdoubleArray query, jint n, jintArray words, jdoubleArray wordSims, jintArray topics, jdoubleArray topicSims)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if (emb_missing(env, s)) return;
     if (n < 1 || n > 64) { throw_msg(env, "java/lang/IllegalArgumentException", "embNearest: n must be 1..64"); return; }
     if (bad_len(env, query, s->embC, "embNearest query") || bad_len(env, words, n, "embNearest words") || bad_len(env, wordSims, n, "embNearest wordSims") ||
@@ -890,15 +778,15 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbNearest(JN
 }
 
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nEmbRelease(JNIEnv* env, jclass, jlong p)
-{ ShardPin pin_(p); Shard* s = pin_.s; if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+{ ShardPin pin_(env, p); Shard* s = pin_.s; if (!s) return;
   int rc = mvhdp_emb_release(s->h); if (rc) { throw_rt(env, s->h, rc, "mvhdp_emb_release"); return; } s->embR = 0; s->embC = 0; s->embK = 0; }
 
 // useVectorsLambda (PTM:1199-1207): lambda = 0 switches the mix off; expDot [K*V_0] / sumExp [K] in the reference's layout, or both null:
 // the handle's own softmax table as the last embSoftmax left it
 JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetVectorsMix(JNIEnv* env, jclass, jlong p, jdouble lambda, jdoubleArray expDot, jdoubleArray sumExp)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return;
     if ((expDot == nullptr) != (sumExp == nullptr)) { throw_msg(env, "java/lang/IllegalArgumentException", "setVectorsMix: expDot and sumExp go together"); return; }
     if ((expDot && bad_len(env, expDot, (jlong)s->K * s->V[0], "setVectorsMix expDot [K*V_0]")) || (sumExp && bad_len(env, sumExp, s->K, "setVectorsMix sumExp"))) return;
     Doubles e(env, expDot, JNI_ABORT), m(env, sumExp, JNI_ABORT);
@@ -910,8 +798,8 @@ JNIEXPORT void JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nSetVectorsMix
 // returns lambda (0: off); mix [V_0*K] or null: lambda * (e / S) as the device holds it
 JNIEXPORT jdouble JNICALL Java_org_madgik_MVTopicModel_NativeSampler_nGetVectorsMix(JNIEnv* env, jclass, jlong p, jdoubleArray mix)
 {
-    ShardPin pin_(p); Shard* s = pin_.s;
-    if (!s) { throw_msg(env, "java/lang/IllegalStateException", "NativeSampler is closed"); return 0.0; }
+    ShardPin pin_(env, p); Shard* s = pin_.s;
+    if (!s) return 0.0;
     if (mix && bad_len(env, mix, (jlong)s->V[0] * s->K, "getVectorsMix mix [V_0*K]")) return 0.0;
     Doubles t(env, mix, 0);
     if (t.failed()) return 0.0;

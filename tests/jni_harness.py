@@ -1,40 +1,52 @@
-"""Runs the JNI shim (mvtopicmodel_amd/java/mvhdp_jni.cpp) without a JVM.
+"""Runs the JNI shim (the four sources mvtopicmodel_amd/java/mvhdp*_jni.cpp, one libmvhdp_jni.so) without a JVM.
 
-The shim is compiled UNMODIFIED against the declaration-only tests/native/jni_stub/jni.h and linked, in a temporary directory, with
+The sources are compiled UNMODIFIED against the declaration-only tests/native/jni_stub/jni.h and linked, in a temporary directory, with
 tests/native/fake_jvm.cpp (which defines the JNIEnv members that header declares) and with either libmvhdp.so or the CPU-side stand-in
-tests/native/fake_mvhdp.c.  `Jvm` is what a test holds: arrays and objects of the fake Java heap, `call()` for one Java_..._n* entry.
+tests/native/fake_mvhdp.c -- in either of the two forms a host may build them: the four on one command line, or one translation unit
+that includes all four.  `Jvm` is what a test holds: arrays and objects of the fake Java heap, `call()` for one Java_..._n* entry of any
+of the four classes.
 After EVERY entry `call()` reads the ledger of the fake JVM and refuses a dirty one -- on the error paths too -- and turns a pending
 exception into a Python `JavaException(cls, msg)`.  `JniSampler` / `JniGroup` transcribe the public methods of NativeSampler.java
 line by line: the same array lengths, the same flat layouts, the same way of filling SweepStats / EmbStats / Tuning / Diagnostics.
 
 Test infrastructure; nothing here is part of the product or of its build."""
 import ctypes as C
+import functools
 import os
 import re
 import subprocess
+import tempfile
 import types
 import warnings
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "mvtopicmodel_amd", "java", "mvhdp_jni.cpp")
-# MVHDP_JNI_SHIM_SOURCE: a scratch copy of the shim with one mutation applied (profiles/jni_harness.md) takes the shim's place.  Said
-# aloud on import (pytest lists the warning in its summary), so that a stray value cannot pass for a run against the repository's own file.
+JAVA_DIR = os.path.join(ROOT, "mvtopicmodel_amd", "java")
+# the Java classes and the shim source that holds the natives of each (mvhdp_jni.cpp first: SHIM)
+CLASSES = {"NativeSampler": "mvhdp_jni.cpp", "NativeSimilarity": "mvhdp_sim_jni.cpp", "NativePhrases": "mvhdp_phrases_jni.cpp", "NativeHeldout": "mvhdp_heldout_jni.cpp"}
+SHIMS = [os.path.join(JAVA_DIR, f) for f in CLASSES.values()]
+# MVHDP_JNI_SHIM_SOURCE: a scratch copy of ONE of the four sources with one mutation applied (profiles/jni_harness.md) takes the place of
+# the source of the same base name (its #include "mvhdp_jni_common.h" finds a header lying beside the copy first, the repository's
+# otherwise).  Said aloud on import (pytest lists the warning in its summary), so that a stray value cannot pass for a run against the
+# repository's own files.
 if os.environ.get("MVHDP_JNI_SHIM_SOURCE"):
-    SHIM = os.path.abspath(os.environ["MVHDP_JNI_SHIM_SOURCE"])
-    if not os.path.isfile(SHIM):
-        raise RuntimeError(f"MVHDP_JNI_SHIM_SOURCE={SHIM}: no such file")
-    warnings.warn(f"MVHDP_JNI_SHIM_SOURCE is set: the JNI tests run {SHIM}, NOT mvtopicmodel_amd/java/mvhdp_jni.cpp", RuntimeWarning)
-JAVA = os.path.join(ROOT, "mvtopicmodel_amd", "java", "org", "madgik", "MVTopicModel", "NativeSampler.java")
+    _copy = os.path.abspath(os.environ["MVHDP_JNI_SHIM_SOURCE"])
+    if not os.path.isfile(_copy) or os.path.basename(_copy) not in CLASSES.values():
+        raise RuntimeError(f"MVHDP_JNI_SHIM_SOURCE={_copy}: not a file named as one of {sorted(CLASSES.values())}")
+    SHIMS[list(CLASSES.values()).index(os.path.basename(_copy))] = _copy
+    warnings.warn(f"MVHDP_JNI_SHIM_SOURCE is set: the JNI tests run {_copy}, NOT mvtopicmodel_amd/java/{os.path.basename(_copy)}", RuntimeWarning)
+SHIM = SHIMS[0]
+COMMON = os.path.join(JAVA_DIR, "mvhdp_jni_common.h")        # what the four sources share
+JAVA = {cls: os.path.join(JAVA_DIR, "org", "madgik", "MVTopicModel", cls + ".java") for cls in CLASSES}
 NATIVE = os.path.join(ROOT, "tests", "native")
-PREFIX = "Java_org_madgik_MVTopicModel_NativeSampler_"
+PREFIX = {cls: f"Java_org_madgik_MVTopicModel_{cls}_" for cls in CLASSES}
 JNI_ABORT = 2
 
-# ---- the 51 entries: return type, then the arguments after (JNIEnv*, jclass).  J jlong, I jint, D jdouble, Z jboolean, V void;
+# ---- the 56 entries, by class: return type, then the arguments after (JNIEnv*, jclass).  J jlong, I jint, D jdouble, Z jboolean, V void;
 # [I int[], [J long[], [D double[], [Z boolean[], [B byte[], [[D double[][], L an object ----
 DIAG = ["I", "[I", "[D", "[D", "[I", "[I", "[I", "[I", "[I", "[I", "[I", "[D", "[I", "[J", "[D"]
-PROTOTYPES = {
+_BY_CLASS = {"NativeSampler": {
     "nCreate": ("J", ["I", "[I", "I", "J"]),
     "nDestroy": ("V", ["J"]),
     "nSetCorpus": ("V", ["J", "I", "[J", "[I"]),
@@ -86,7 +98,18 @@ PROTOTYPES = {
     "nEmbRelease": ("V", ["J"]),
     "nSetVectorsMix": ("V", ["J", "D", "[D", "[D"]),
     "nGetVectorsMix": ("D", ["J", "[D"]),
-}
+}, "NativeSimilarity": {
+    "nSimilarPairs": ("J", ["J", "I", "I", "I", "[D", "D", "D", "I", "J", "[I", "[I", "[D", "[J", "[D"]),
+    "nDocTopicsTop": ("J", ["J", "[D", "J", "J", "D", "I", "[J", "[I", "[D"]),
+    "nEntityTopicDistributions": ("V", ["J", "[D", "D", "I", "I", "[J", "[J", "[D"]),
+}, "NativePhrases": {
+    "nTopicPhrases": ("J", ["J", "I", "I", "[J", "[J", "[I", "[I", "[J", "[J", "[J", "[J"]),
+}, "NativeHeldout": {
+    "nLeftToRight": ("D", ["J", "I", "I", "I", "J", "J", "[D", "D", "[J", "[I", "[D", "[D", "[J", "[J"]),
+}}
+# {entry: (return code, [argument codes], Java class)}: the entry names are unique across the four classes
+PROTOTYPES = {name: (ret, args, cls) for cls, table in _BY_CLASS.items() for name, (ret, args) in table.items()}
+SIDE_ENTRIES = [name for name, (_, _, cls) in PROTOTYPES.items() if cls != "NativeSampler"]
 _CTYPE = {"J": C.c_int64, "I": C.c_int32, "D": C.c_double, "Z": C.c_uint8, "V": None}
 _CXX = {"jlong": "J", "jint": "I", "jdouble": "D", "jboolean": "Z", "void": "V", "jintArray": "[I", "jlongArray": "[J", "jdoubleArray": "[D",
         "jbooleanArray": "[Z", "jbyteArray": "[B", "jobjectArray": "[[D", "jobject": "L"}
@@ -115,27 +138,31 @@ class DirtyLedger(AssertionError):
     pass
 
 
-def shim_signatures(path=SHIM):
-    """{entry: (return code, [argument codes])} parsed from the shim's source (the DIAG_PARAMS macro expanded)."""
-    src = open(path).read()
-    macro = re.search(r"#define DIAG_PARAMS (.*?[^\\])\n", src, re.S).group(1).replace("\\\n", " ")
+def shim_signatures(paths=None):
+    """{entry: (return code, [argument codes], Java class)} parsed from the four shim sources (the DIAG_PARAMS macro expanded)."""
     out = {}
-    for ret, name, params in re.findall(r"JNIEXPORT (\w+) JNICALL " + PREFIX + r"(n\w+)\(([^)]*)\)\s*\{", src):
-        params = params.replace("DIAG_PARAMS", macro)
-        parts = [p.strip() for p in params.split(",")]
-        assert parts[0].startswith("JNIEnv*") and parts[1].split()[0] == "jclass", (name, parts[:2])
-        out[name] = (_CXX[ret], [_CXX[p.split()[0]] for p in parts[2:]])
+    for path in paths or SHIMS:
+        src = open(path).read()
+        macro = re.search(r"#define DIAG_PARAMS (.*?[^\\])\n", src, re.S)
+        macro = macro.group(1).replace("\\\n", " ") if macro else ""
+        for ret, cls, name, params in re.findall(r"JNIEXPORT (\w+) JNICALL Java_org_madgik_MVTopicModel_([A-Za-z]+)_(n\w+)\(([^)]*)\)\s*\{", src):
+            params = params.replace("DIAG_PARAMS", macro)
+            parts = [p.strip() for p in params.split(",")]
+            assert parts[0].startswith("JNIEnv*") and parts[1].split()[0] == "jclass", (name, parts[:2])
+            assert name not in out and os.path.basename(path) == CLASSES[cls], (name, cls, path)
+            out[name] = (_CXX[ret], [_CXX[p.split()[0]] for p in parts[2:]], cls)
     return out
 
 
-def java_natives(path=JAVA):
-    """{native method: (return code, [argument codes])} parsed from the `private static native` lines of the Java class."""
-    src = open(path).read()
+def java_natives():
+    """{native method: (return code, [argument codes], Java class)} parsed from the `private static native` lines of the four Java classes."""
     jt = {"long": "J", "int": "I", "double": "D", "boolean": "Z", "void": "V", "int[]": "[I", "long[]": "[J", "double[]": "[D", "boolean[]": "[Z",
           "byte[]": "[B", "double[][]": "[[D", "SweepStats": "L"}
     out = {}
-    for ret, name, params in re.findall(r"private static native ([\w\[\]]+) (n\w+)\(([^)]*)\);", src):
-        out[name] = (jt[ret], [jt[p.split()[0]] for p in params.split(",")])
+    for cls, path in JAVA.items():
+        for ret, name, params in re.findall(r"private static native ([\w\[\]]+) (n\w+)\(([^)]*)\);", open(path).read()):
+            assert name not in out, name
+            out[name] = (jt[ret], [jt[p.split()[0]] for p in params.split(",")], cls)
     return out
 
 
@@ -147,23 +174,56 @@ def build_standin(tmp):
     return out
 
 
-def build_shim(tmp, library, shim=SHIM, name="libmvhdp_jni_under_test.so"):
-    """shim + fake JVM as one shared object in `tmp`, linked against `library` (libmvhdp.so or the stand-in); returns its path."""
+_INCLUDES = ["-I", os.path.join(NATIVE, "jni_stub"), "-I", os.path.join(ROOT, "include"), "-I", JAVA_DIR]
+
+
+def build_shim(tmp, library, shims=None, name="libmvhdp_jni_under_test.so", one_tu=False):
+    """the shim sources + fake JVM as one shared object in `tmp`, linked against `library` (libmvhdp.so or the stand-in); returns its
+    path.  one_tu: the sources as one translation unit that includes them all, instead of each on the command line."""
     out = os.path.join(str(tmp), name)
     libdir, base = os.path.split(os.path.abspath(library))
     assert base.startswith("lib") and base.endswith(".so"), base
-    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-shared", "-fPIC", "-Wall", "-I", os.path.join(NATIVE, "jni_stub"),
-                           "-I", os.path.join(ROOT, "include"), shim, os.path.join(NATIVE, "fake_jvm.cpp"), "-o", out,
+    shims = list(shims or SHIMS)
+    if one_tu:
+        tu = os.path.join(str(tmp), name + ".one_tu.cpp")
+        with open(tu, "w") as f:
+            f.write("".join(f'#include "{s}"\n' for s in shims))
+        shims = [tu]
+    subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-shared", "-fPIC", "-Wall"] + _INCLUDES + shims + [os.path.join(NATIVE, "fake_jvm.cpp"), "-o", out,
                            "-Wl,-Bsymbolic", "-Wl,--no-undefined", "-L", libdir, "-l" + base[3:-3], "-Wl,-rpath," + libdir, "-pthread"])
     return out
 
 
-def shim_imports(tmp, shim=SHIM):
-    """the mvhdp_* symbols the shim's object file leaves undefined (nm -u)"""
-    obj = os.path.join(str(tmp), "shim_only.o")
-    subprocess.check_call(["g++", "-std=c++17", "-c", "-fPIC", "-I", os.path.join(NATIVE, "jni_stub"), "-I", os.path.join(ROOT, "include"), shim, "-o", obj])
-    names = subprocess.check_output(["nm", "-u", obj], text=True).split()
+def shim_imports(tmp, shims=None):
+    """the mvhdp_* symbols the shim sources' object files leave undefined (nm -u), and the JNIEnv members"""
+    names = set()
+    for i, shim in enumerate(shims or SHIMS):
+        obj = os.path.join(str(tmp), f"shim_only_{i}.o")
+        subprocess.check_call(["g++", "-std=c++17", "-c", "-fPIC"] + _INCLUDES + [shim, "-o", obj])
+        names |= set(subprocess.check_output(["nm", "-u", obj], text=True).split())
     return {n for n in names if n.startswith("mvhdp_")}, {n for n in names if n.startswith("_ZN6JNIEnv")}
+
+
+@functools.lru_cache(maxsize=None)
+def check_sources_compile_together_and_apart():
+    """What a namespace per source once stood for: each of the four sources type-checks on its own (-Wall -Werror), all four type-check
+    as one translation unit, and neither they nor the shared header contain a using-directive (a `using namespace` in one source
+    would change name lookup in the ones included after it).  Nothing is built or linked; once per process."""
+    for shim in SHIMS:
+        subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror"] + _INCLUDES + [shim])
+    with tempfile.TemporaryDirectory() as tmp:
+        tu = os.path.join(tmp, "one_tu.cpp")
+        with open(tu, "w") as f:
+            f.write("".join(f'#include "{s}"\n' for s in SHIMS))
+        subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror"] + _INCLUDES + [tu])
+    for path in SHIMS + [COMMON]:
+        assert not re.search(r"using\s+namespace", re.sub(r"//[^\n]*", "", open(path).read())), path
+    return True
+
+
+def common_header_code():
+    """mvhdp_jni_common.h without its comments"""
+    return re.sub(r"//[^\n]*", "", open(COMMON).read())
 
 
 class JArray:
@@ -246,8 +306,8 @@ class Jvm:
         assert L.fj_ledger_size() == len(LEDGER)
         self.env = L.fj_env()
         self.entries = {}
-        for name, (ret, args) in PROTOTYPES.items():
-            f = getattr(L, PREFIX + name)
+        for name, (ret, args, cls) in PROTOTYPES.items():
+            f = getattr(L, PREFIX[cls] + name)
             f.restype = _CTYPE[ret]
             f.argtypes = [vp, vp] + [_CTYPE.get(a, vp) for a in args]
             self.entries[name] = f
@@ -310,7 +370,7 @@ class Jvm:
     def call(self, name, *args):
         """One Java_..._n* entry as the JVM would call it: a fresh local frame, the entry, the frame popped; then the ledger must be
         clean (DirtyLedger if not, whatever else happened) and a pending exception is raised as JavaException."""
-        ret, codes = PROTOTYPES[name]
+        ret, codes, _ = PROTOTYPES[name]
         assert len(args) == len(codes), f"{name} takes {len(codes)} arguments"
         conv = []
         for a, code in zip(args, codes):

@@ -1,9 +1,12 @@
 /* fake_mvhdp.c -- a stand-in for libmvhdp.so on the CPU side of the JNI tests (tests/test_jni_fake_jvm.py).  A handle cannot exist
  * without a device, so the shim's lifecycle and refusal paths are run against this instead: it exports every mvhdp_* symbol the shim
  * imports, logs every call by name, and does nothing else -- except for a handful that record what they were handed (create, destroy,
- * set_corpus, get_counts, top_words, sweep, sweep_many, get_tuning, set_tuning, group_create, group_destroy, last_error).  Every other function is one line:
+ * set_corpus, get_counts, top_words, sweep, sweep_many, get_tuning, set_tuning, group_create, group_destroy, last_error) and the four
+ * post-training calls whose scalar outputs the shim reads back (similar_pairs, doc_topics_top, topic_phrases, heldout_left_to_right: on
+ * MVHDP_OK a recognisable value in each, within the capacities handed in).  Every other function is one line:
  * it returns the status fm_set_status() chose (MVHDP_ERR_UNSUPPORTED unless told otherwise) and touches none of its pointers.
- * mvhdp_sweep_many can be made to block until the test lets it go.  It is NOT a second implementation of anything. */
+ * mvhdp_sweep_many and mvhdp_heldout_left_to_right can be made to block until the test lets them go.  It is NOT a second implementation
+ * of anything. */
 #include <pthread.h>
 #include <stdlib.h>
 #include <string.h>
@@ -97,6 +100,15 @@ static void made_stats(mvhdp_sweep_stats* st, int i)
     st->activations = (int32_t)b + 14;
 }
 
+/* between begin() and end(): the call stays inside for as long as fm_block_sweeps(1) holds */
+static void gate(void)
+{
+    g_sweeps_inside++;
+    while (g_block_sweeps) pthread_cond_wait(&g_cv, &g_mu);       /* (gives g_mu up while it waits) */
+    g_sweeps_inside--;
+    g_sweeps_returned++;
+}
+
 /* ---- the ones that record ---- */
 EXPORT int mvhdp_create(const mvhdp_config* cfg, mvhdp_handle* out)
 {
@@ -138,10 +150,7 @@ EXPORT int mvhdp_sweep_many(mvhdp_handle h, uint32_t first_idx, int32_t n, uint6
     (void)h;
     int rc = begin("mvhdp_sweep_many");
     g_rec.sweep_idx = first_idx; g_rec.sweep_seed = seed; g_rec.sweep_flags = flags; g_rec.sweep_n = n;
-    g_sweeps_inside++;
-    while (g_block_sweeps) pthread_cond_wait(&g_cv, &g_mu);       /* (gives g_mu up while it waits) */
-    g_sweeps_inside--;
-    g_sweeps_returned++;
+    gate();
     end(rc);
     if (rc == MVHDP_OK) for (int i = 0; i < n; i++) made_stats(&stats[i], (int)first_idx + i);
     return rc;
@@ -175,6 +184,46 @@ EXPORT int mvhdp_top_words(mvhdp_handle h, int32_t m, int32_t n, int32_t* types,
     return end(rc);
 }
 
+/* ---- the post-training calls: the scalars the shim reads back, never more than the capacity it passed ---- */
+static int64_t at_most(int64_t cap, int64_t v) { return cap < v ? cap : v; }
+EXPORT int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int64_t cap, int32_t* i, int32_t* j, double* sim, int64_t* count, mvhdp_sim_stats* stats)
+{
+    (void)h; (void)a; (void)i; (void)j; (void)sim;
+    int rc = logged("mvhdp_similar_pairs");
+    if (rc != MVHDP_OK) return rc;
+    *count = at_most(cap, 3);
+    if (stats) { stats->pairs_screened = 101; stats->candidates = 102; stats->emitted = 103; stats->stripes = 104; stats->regrown = 105; stats->margin = 0.625; }
+    return rc;
+}
+EXPORT int mvhdp_doc_topics_top(mvhdp_handle h, const double* view_weights, int64_t d0, int64_t d1, double threshold, int32_t max, int64_t cap, int64_t* row_off,
+                                int32_t* topics, double* weights, int64_t* count)
+{
+    (void)h; (void)view_weights; (void)d0; (void)d1; (void)threshold; (void)max; (void)row_off; (void)topics; (void)weights;
+    int rc = logged("mvhdp_doc_topics_top");
+    if (rc == MVHDP_OK) *count = at_most(cap, 2);
+    return rc;
+}
+EXPORT int mvhdp_topic_phrases(mvhdp_handle h, const mvhdp_phrase_args* a, int64_t cap_phrases, int64_t cap_words, int64_t* topic_off, int64_t* word_off, int32_t* words,
+                               int32_t* counts, int64_t* distinct, int64_t* occurrences, int64_t* n_phrases, int64_t* n_words, mvhdp_phrase_stats* stats)
+{
+    (void)h; (void)a; (void)topic_off; (void)word_off; (void)words; (void)counts; (void)distinct; (void)occurrences;
+    int rc = logged("mvhdp_topic_phrases");
+    if (rc != MVHDP_OK) return rc;
+    *n_phrases = at_most(cap_phrases, 3); *n_words = at_most(cap_words, 5);
+    if (stats) { stats->runs = 201; stats->occurrences = 202; stats->distinct = 203; stats->kept = 204; stats->hash_collisions = 205; }
+    return rc;
+}
+EXPORT int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_args* a, int64_t num_docs, const int64_t* doc_off, const int32_t* tokens, double* doc_ll,
+                                       double* position_sum, int64_t* doc_tokens, mvhdp_heldout_stats* stats)
+{
+    (void)h; (void)a; (void)num_docs; (void)doc_off; (void)tokens; (void)doc_ll; (void)position_sum; (void)doc_tokens;
+    int rc = begin("mvhdp_heldout_left_to_right");
+    gate();
+    end(rc);
+    if (rc == MVHDP_OK && stats) { stats->log_likelihood = -12.5; stats->tokens = 301; stats->oov = 302; stats->visits = 303; }
+    return rc;
+}
+
 /* ---- the one-liners ---- */
 #define STUB(name, ...) EXPORT int name(__VA_ARGS__) { return logged(#name); }
 STUB(mvhdp_set_assignments, mvhdp_handle h, int32_t m, const int32_t* z)
@@ -204,6 +253,8 @@ STUB(mvhdp_emb_nearest, mvhdp_handle h, const double* query, int32_t n, int32_t*
 STUB(mvhdp_emb_release, mvhdp_handle h)
 STUB(mvhdp_set_vectors_mix, mvhdp_handle h, double lambda, const double* exp_dot, const double* sum_exp)
 STUB(mvhdp_get_vectors_mix, mvhdp_handle h, double* lambda, double* mix)
+STUB(mvhdp_entity_topic_distributions, mvhdp_handle h, const double* view_weights, double threshold, int32_t max, int32_t round_digits, int64_t n_groups,
+     const int64_t* member_off, const int64_t* members, double* out)
 STUB(mvhdp_apply_delta, mvhdp_handle h, int32_t activated_topic, int32_t activated_modality)
 STUB(mvhdp_group_unique_id, uint8_t* id)
 STUB(mvhdp_group_create_rank, mvhdp_handle member, const uint8_t* id, int32_t rank, int32_t nranks, mvhdp_group* out)

@@ -5,7 +5,6 @@ Shapes: K below, at and above the 64 lanes, ragged and several topics a lane (bo
 lengths around the 64-lane width and of 0, 1, 2 tokens; out-of-vocabulary tokens first, in the middle, last; a document beyond the LDS cap
 of z; more work items than waves."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -17,7 +16,6 @@ from tests import ltr_cases as lc
 from tests import ltr_ref as lr
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INV, STATE = -1, -2                                                          # MVHDP_ERR_INVALID_ARG, MVHDP_ERR_STATE
 KS = [5, 64, 100, 130, 1000]
 
@@ -279,45 +277,14 @@ def test_group_of_two_members_equals_one_handle(models):
             s.close()
 
 
-# ---- the Java path: the four shim sources as one library, under the test-side JNIEnv ------------------------------------------------
-PREFIX = "Java_org_madgik_MVTopicModel_NativeHeldout_"
-PROTOTYPE = ("D", ["J", "I", "I", "I", "J", "J", "[D", "D", "[J", "[I", "[D", "[D", "[J", "[J"])
+# ---- the Java path: the four shim sources as one library, under the test-side JNIEnv (tests/jni_harness.py) ---------------------------
 IAE = "java/lang/IllegalArgumentException"
 
 
 @pytest.fixture(scope="module")
 def jvm(tmp_path_factory):
     _lib.load_library()
-    tmp = tmp_path_factory.mktemp("heldout_jni")
-    java = os.path.join(ROOT, "mvtopicmodel_amd", "java")
-    four = tmp / "four_shims.cpp"
-    four.write_text(f'#include "{java}/mvhdp_jni.cpp"\n#include "{java}/mvhdp_sim_jni.cpp"\n#include "{java}/mvhdp_phrases_jni.cpp"\n#include "{java}/mvhdp_heldout_jni.cpp"\n')
-    jvm = H.Jvm(H.build_shim(tmp, _lib.LIB_PATH, shim=str(four)))
-    f = getattr(jvm.lib, PREFIX + "nLeftToRight")
-    f.restype = H._CTYPE[PROTOTYPE[0]]
-    f.argtypes = [C.c_void_p, C.c_void_p] + [H._CTYPE.get(a, C.c_void_p) for a in PROTOTYPE[1]]
-    return jvm
-
-
-def jcall(jvm, *args):
-    """the NativeHeldout entry as Jvm.call runs NativeSampler's: a fresh local frame, the entry, the ledger, the pending exception"""
-    codes = PROTOTYPE[1]
-    assert len(args) == len(codes)
-    conv = [(None if a is None else a.h) if code.startswith("[") else (float(a) if code == "D" else int(a)) for a, code in zip(args, codes)]
-    before = jvm.ledger()
-    jvm.lib.fj_begin_call()
-    r = getattr(jvm.lib, PREFIX + "nLeftToRight")(jvm.env, None, *conv)
-    jvm.lib.fj_end_call()
-    led = jvm.ledger()
-    delta = {k: (led[k] if k in ("buffers_outstanding", "locals_left", "local_arrays_left", "locals_high_water") else led[k] - before[k]) for k in H.LEDGER}
-    exc = jvm.take_exception()
-    bad = jvm.dirt(delta)
-    if bad:
-        jvm.lib.fj_ledger_reset()
-        raise H.DirtyLedger(f"nLeftToRight: the fake JVM's ledger is not clean: {bad}")
-    if exc:
-        raise H.JavaException(*exc)
-    return r
+    return H.Jvm(H.build_shim(tmp_path_factory.mktemp("heldout_jni"), _lib.LIB_PATH, one_tu=True))       # the four shim sources as one translation unit
 
 
 def test_the_java_entry_equals_the_binding(jvm):
@@ -340,22 +307,22 @@ def test_the_java_entry_equals_the_binding(jvm):
         h = j.handle
         joff, jtok = jvm.longs(off), jvm.ints(tok)
         with pytest.raises(H.JavaException) as e:                            # a library error becomes a RuntimeException with its text
-            jcall(jvm, h, 0, 3, 1, 17, 0, None, 0.0, joff, jtok, None, None, None, None)
+            jvm.call("nLeftToRight", h, 0, 3, 1, 17, 0, None, 0.0, joff, jtok, None, None, None, None)
         assert e.value.cls == "java/lang/RuntimeException" and "counts" in e.value.msg
         j.buildCounts()
         jll, jps, jdt, jst = jvm.doubles(D), jvm.doubles(N), jvm.longs(D), jvm.longs(3)
-        total = jcall(jvm, h, 0, 3, 1, 17, 0, None, 0.0, joff, jtok, jll, jps, jdt, jst)
+        total = jvm.call("nLeftToRight", h, 0, 3, 1, 17, 0, None, 0.0, joff, jtok, jll, jps, jdt, jst)
         assert total == want.log_likelihood and list(jst.get()) == [want.tokens, want.oov, want.visits]
         assert jll.get().tobytes() == want.doc_log_likelihood.tobytes() and jps.get().tobytes() == want.position_sum.tobytes()
         assert np.array_equal(jdt.get(), want.doc_tokens)
-        assert jcall(jvm, h, 0, 3, 1, 17, 0, None, 0.0, joff, jtok, None, None, None, None) == want.log_likelihood   # every output is optional
-        assert jcall(jvm, h, 0, 3, 1, 17, 0, jvm.doubles(scaled), float(scaled.sum()), joff, jtok, None, jps, None, None) == want_a.log_likelihood
+        assert jvm.call("nLeftToRight", h, 0, 3, 1, 17, 0, None, 0.0, joff, jtok, None, None, None, None) == want.log_likelihood   # every output is optional
+        assert jvm.call("nLeftToRight", h, 0, 3, 1, 17, 0, jvm.doubles(scaled), float(scaled.sum()), joff, jtok, None, jps, None, None) == want_a.log_likelihood
         assert jps.get().tobytes() == want_a.position_sum.tobytes()
 
         # a wrong array length is refused before the library is reached
         def refused(*args):
             with pytest.raises(H.JavaException) as e:
-                jcall(jvm, *args)
+                jvm.call("nLeftToRight", *args)
             assert e.value.cls == IAE, e.value
         refused(h, 0, 3, 1, 17, 0, None, 0.0, joff, jvm.ints(tok[:-1]), jll, jps, jdt, jst)      # tokens too short
         refused(h, 0, 3, 1, 17, 0, None, 0.0, joff, jvm.ints(np.append(tok, 0)), jll, jps, jdt, jst)
@@ -368,10 +335,12 @@ def test_the_java_entry_equals_the_binding(jvm):
         refused(h, 0, 3, 1, 17, 0, None, 0.0, joff, jtok, jll, jps, jvm.longs(D - 1), jst)
         refused(h, 0, 3, 1, 17, 0, None, 0.0, joff, jtok, jll, jps, jdt, jvm.longs(4))
         with pytest.raises(H.JavaException) as e:                            # particles = 0: the library's refusal
-            jcall(jvm, h, 0, 0, 1, 17, 0, None, 0.0, joff, jtok, None, None, None, None)
+            jvm.call("nLeftToRight", h, 0, 0, 1, 17, 0, None, 0.0, joff, jtok, None, None, None, None)
         assert e.value.cls == "java/lang/RuntimeException" and "particles" in e.value.msg
     finally:
         j.close()
-    with pytest.raises(H.JavaException) as e:                                # a closed sampler: its handle is 0
-        jcall(jvm, j.handle, 0, 3, 1, 17, 0, None, 0.0, jvm.longs(off), jvm.ints(tok), None, None, None, None)
-    assert j.handle == 0 and e.value.cls == "java/lang/IllegalStateException"
+    for closed in (j.handle, h):                                             # a closed sampler: its handle is 0; and the jlong it had is refused too
+        with pytest.raises(H.JavaException) as e:
+            jvm.call("nLeftToRight", closed, 0, 3, 1, 17, 0, None, 0.0, jvm.longs(off), jvm.ints(tok), None, None, None, None)
+        assert e.value.cls == "java/lang/IllegalStateException" and e.value.msg == "NativeSampler is closed"
+    assert j.handle == 0 and h != 0

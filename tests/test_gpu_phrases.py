@@ -3,7 +3,6 @@ exactly and in whole: topic_off, word_off, words, counts, distinct, occurrences 
 set_assignments does.  Shapes: document lengths at and around the 64-wide step of the walk and its multiples, documents of thousands of
 tokens, and constructed documents whose runs, phrases and chains of length-2 runs cross those steps."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -14,7 +13,6 @@ from tests import jni_harness as H
 from tests import phrases_numpy as pn
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INV, STATE = -1, -2                                                          # MVHDP_ERR_INVALID_ARG, MVHDP_ERR_STATE
 LENGTHS = [0, 1, 2, 3, 63, 64, 65, 127, 128, 129]
 
@@ -338,45 +336,14 @@ def test_merge_over_two_handles_equals_one_handle():
         assert g.topic_phrases(3, vocabulary="abcd").phrases == whole.topic_phrases(3, vocabulary="abcd").phrases
 
 
-# ---- the Java path: the three shim sources as one library, under the test-side JNIEnv -----------------------------------------------
-PREFIX = "Java_org_madgik_MVTopicModel_NativePhrases_"
-PROTOTYPE = ("J", ["J", "I", "I", "[J", "[J", "[I", "[I", "[J", "[J", "[J", "[J"])
+# ---- the Java path: the four shim sources as one library, under the test-side JNIEnv (tests/jni_harness.py) ---------------------------
 IAE = "java/lang/IllegalArgumentException"
 
 
 @pytest.fixture(scope="module")
 def jvm(tmp_path_factory):
     _lib.load_library()
-    tmp = tmp_path_factory.mktemp("phrases_jni")
-    java = os.path.join(ROOT, "mvtopicmodel_amd", "java")
-    three = tmp / "three_shims.cpp"
-    three.write_text(f'#include "{java}/mvhdp_jni.cpp"\n#include "{java}/mvhdp_sim_jni.cpp"\n#include "{java}/mvhdp_phrases_jni.cpp"\n')
-    jvm = H.Jvm(H.build_shim(tmp, _lib.LIB_PATH, shim=str(three)))
-    f = getattr(jvm.lib, PREFIX + "nTopicPhrases")
-    f.restype = H._CTYPE[PROTOTYPE[0]]
-    f.argtypes = [C.c_void_p, C.c_void_p] + [H._CTYPE.get(a, C.c_void_p) for a in PROTOTYPE[1]]
-    return jvm
-
-
-def jcall(jvm, *args):
-    """the NativePhrases entry as Jvm.call runs NativeSampler's: a fresh local frame, the entry, the ledger, the pending exception"""
-    codes = PROTOTYPE[1]
-    assert len(args) == len(codes)
-    conv = [(None if a is None else a.h) if code.startswith("[") else int(a) for a, code in zip(args, codes)]
-    before = jvm.ledger()
-    jvm.lib.fj_begin_call()
-    r = getattr(jvm.lib, PREFIX + "nTopicPhrases")(jvm.env, None, *conv)
-    jvm.lib.fj_end_call()
-    led = jvm.ledger()
-    delta = {k: (led[k] if k in ("buffers_outstanding", "locals_left", "local_arrays_left", "locals_high_water") else led[k] - before[k]) for k in H.LEDGER}
-    exc = jvm.take_exception()
-    bad = jvm.dirt(delta)
-    if bad:
-        jvm.lib.fj_ledger_reset()
-        raise H.DirtyLedger(f"nTopicPhrases: the fake JVM's ledger is not clean: {bad}")
-    if exc:
-        raise H.JavaException(*exc)
-    return r
+    return H.Jvm(H.build_shim(tmp_path_factory.mktemp("phrases_jni"), _lib.LIB_PATH, one_tu=True))       # the four shim sources as one translation unit
 
 
 def test_the_java_entry_equals_the_binding(jvm, base):
@@ -386,17 +353,17 @@ def test_the_java_entry_equals_the_binding(jvm, base):
         j.setCorpus(0, off, tok)
         h = j.handle
         with pytest.raises(H.JavaException) as e:                            # a library error becomes a RuntimeException with its text
-            jcall(jvm, h, 20, 0, None, None, None, None, None, None, jvm.longs(2), None)
+            jvm.call("nTopicPhrases", h, 20, 0, None, None, None, None, None, None, jvm.longs(2), None)
         assert e.value.cls == "java/lang/RuntimeException" and "unassigned" in e.value.msg
         j.setAssignments(0, z)
         for max_n in (20, -1):
             want = s.topic_phrases_raw(max_n)
             sizes = jvm.longs(2)
-            n = jcall(jvm, h, max_n, 0, None, None, None, None, None, None, sizes, None)
+            n = jvm.call("nTopicPhrases", h, max_n, 0, None, None, None, None, None, None, sizes, None)
             assert n == len(want[3]) and list(sizes.get()) == [len(want[3]), len(want[2])]
             nw = len(want[2])
             jto, jwo, jw, jc, jd, jo, jst = jvm.longs(K + 1), jvm.longs(n + 1), jvm.ints(nw), jvm.ints(n), jvm.longs(K), jvm.longs(K), jvm.longs(5)
-            assert jcall(jvm, h, max_n, 0, jto, jwo, jw, jc, jd, jo, sizes, jst) == n
+            assert jvm.call("nTopicPhrases", h, max_n, 0, jto, jwo, jw, jc, jd, jo, sizes, jst) == n
             assert_equal((jto.get(), jwo.get(), jw.get().astype(np.int32), jc.get().astype(np.int32), jd.get(), jo.get()), want[:6], ("java", max_n))
             st = want[6]
             assert list(jst.get()) == [st.runs, st.occurrences, st.distinct, st.kept, st.hash_collisions]
@@ -405,13 +372,13 @@ def test_the_java_entry_equals_the_binding(jvm, base):
         want = s.topic_phrases_raw(20)
         n, nw = len(want[3]), len(want[2])
         jwo, jw, jc, sizes = jvm.longs([-7] * n), jvm.ints([-7] * nw), jvm.ints([-7] * (n - 1)), jvm.longs(2)
-        assert jcall(jvm, h, 20, 0, None, jwo, jw, jc, None, None, sizes, None) == n
+        assert jvm.call("nTopicPhrases", h, 20, 0, None, jwo, jw, jc, None, None, sizes, None) == n
         assert list(sizes.get()) == [n, nw] and (jwo.get() == -7).all() and (jw.get() == -7).all() and (jc.get() == -7).all()
 
         # a wrong array length is refused before the library is reached
         def refused(*args):
             with pytest.raises(H.JavaException) as e:
-                jcall(jvm, *args)
+                jvm.call("nTopicPhrases", *args)
             assert e.value.cls == IAE, e.value
         ok = dict(to=jvm.longs(K + 1), wo=jvm.longs(n + 1), w=jvm.ints(nw), c=jvm.ints(n), d=jvm.longs(K), o=jvm.longs(K), sz=jvm.longs(2), st=jvm.longs(5))
         refused(h, 20, 0, jvm.longs(K), ok["wo"], ok["w"], ok["c"], ok["d"], ok["o"], ok["sz"], ok["st"])
@@ -426,19 +393,21 @@ def test_the_java_entry_equals_the_binding(jvm, base):
         refused(h, 20, 0, ok["to"], ok["wo"], ok["w"], ok["c"], ok["d"], ok["o"], jvm.longs(1), ok["st"])
         refused(h, 20, 0, ok["to"], ok["wo"], ok["w"], ok["c"], ok["d"], ok["o"], None, ok["st"])
         refused(h, 20, 0, ok["to"], ok["wo"], ok["w"], ok["c"], ok["d"], ok["o"], ok["sz"], jvm.longs(4))
-        assert jcall(jvm, h, 20, 0, ok["to"], ok["wo"], ok["w"], ok["c"], ok["d"], ok["o"], ok["sz"], ok["st"]) == n   # and the right lengths pass
+        assert jvm.call("nTopicPhrases", h, 20, 0, ok["to"], ok["wo"], ok["w"], ok["c"], ok["d"], ok["o"], ok["sz"], ok["st"]) == n   # and the right lengths pass
         with pytest.raises(H.JavaException) as e:                            # hash_bits outside 0..63: the library's refusal
-            jcall(jvm, h, 20, 64, None, None, None, None, None, None, jvm.longs(2), None)
+            jvm.call("nTopicPhrases", h, 20, 64, None, None, None, None, None, None, jvm.longs(2), None)
         assert e.value.cls == "java/lang/RuntimeException" and "hash_bits" in e.value.msg
     finally:
         j.close()
-    with pytest.raises(H.JavaException) as e:                                # a closed sampler: its handle is 0
-        jcall(jvm, j.handle, 20, 0, None, None, None, None, None, None, jvm.longs(2), None)
-    assert j.handle == 0 and e.value.cls == "java/lang/IllegalStateException"
+    for closed in (j.handle, h):                                             # a closed sampler: its handle is 0; and the jlong it had is refused too
+        with pytest.raises(H.JavaException) as e:
+            jvm.call("nTopicPhrases", closed, 20, 0, None, None, None, None, None, None, jvm.longs(2), None)
+        assert e.value.cls == "java/lang/IllegalStateException" and e.value.msg == "NativeSampler is closed"
+    assert j.handle == 0 and h != 0
 
 
 def jvm_bits(jvm, h, max_n, K, n, nw):
     """a second Java call with forced collisions: the same counts"""
     jc = jvm.ints(n)
-    jcall(jvm, h, max_n, 3, jvm.longs(K + 1), jvm.longs(n + 1), jvm.ints(nw), jc, None, None, jvm.longs(2), None)
+    jvm.call("nTopicPhrases", h, max_n, 3, jvm.longs(K + 1), jvm.longs(n + 1), jvm.ints(nw), jc, None, None, jvm.longs(2), None)
     return jc.get()

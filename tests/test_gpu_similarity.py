@@ -17,7 +17,6 @@ from tests import sim_numpy as sn
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 DIMS = [1, 2, 3, 33, 100, 400, 1000]
 NS = [1, 2, 31, 32, 33, 127, 128, 129, 300]
 THRESHOLDS = [0.0, 0.15, 0.3, 0.9]
@@ -280,50 +279,14 @@ def test_topic_lists_and_entity_distributions_on_the_goldens(s, name):
             assert len(sn.similar_pairs(dist, metric, thr, min_weight=0.03)[0]) > 0
 
 
-# ---- the Java path: both shim sources as one library, under the test-side JNIEnv -----------------------------------------------------
-SIM_PREFIX = "Java_org_madgik_MVTopicModel_NativeSimilarity_"
-SIM_PROTOTYPES = {
-    "nSimilarPairs": ("J", ["J", "I", "I", "I", "[D", "D", "D", "I", "J", "[I", "[I", "[D", "[J", "[D"]),
-    "nDocTopicsTop": ("J", ["J", "[D", "J", "J", "D", "I", "[J", "[I", "[D"]),
-    "nEntityTopicDistributions": ("V", ["J", "[D", "D", "I", "I", "[J", "[J", "[D"]),
-}
+# ---- the Java path: the four shim sources as one library, under the test-side JNIEnv (tests/jni_harness.py) ---------------------------
 IAE = "java/lang/IllegalArgumentException"
 
 
 @pytest.fixture(scope="module")
 def jvm(tmp_path_factory):
     _lib.load_library()
-    tmp = tmp_path_factory.mktemp("sim_jni")
-    java = os.path.join(ROOT, "mvtopicmodel_amd", "java")
-    both = tmp / "both_shims.cpp"
-    both.write_text(f'#include "{java}/mvhdp_jni.cpp"\n#include "{java}/mvhdp_sim_jni.cpp"\n')
-    jvm = H.Jvm(H.build_shim(tmp, _lib.LIB_PATH, shim=str(both)))
-    for name, (ret, args) in SIM_PROTOTYPES.items():
-        f = getattr(jvm.lib, SIM_PREFIX + name)
-        f.restype = H._CTYPE[ret]
-        f.argtypes = [C.c_void_p, C.c_void_p] + [H._CTYPE.get(a, C.c_void_p) for a in args]
-    return jvm
-
-
-def sim_call(jvm, name, *args):
-    """one NativeSimilarity entry as Jvm.call runs NativeSampler's: a fresh local frame, the entry, the ledger, the pending exception"""
-    ret, codes = SIM_PROTOTYPES[name]
-    assert len(args) == len(codes)
-    conv = [(None if a is None else a.h) if code.startswith("[") else float(a) if code == "D" else int(a) for a, code in zip(args, codes)]
-    before = jvm.ledger()
-    jvm.lib.fj_begin_call()
-    r = getattr(jvm.lib, SIM_PREFIX + name)(jvm.env, None, *conv)
-    jvm.lib.fj_end_call()
-    led = jvm.ledger()
-    delta = {k: (led[k] if k in ("buffers_outstanding", "locals_left", "local_arrays_left", "locals_high_water") else led[k] - before[k]) for k in H.LEDGER}
-    exc = jvm.take_exception()
-    bad = jvm.dirt(delta)
-    if bad:
-        jvm.lib.fj_ledger_reset()
-        raise H.DirtyLedger(f"{name}: the fake JVM's ledger is not clean: {bad}")
-    if exc:
-        raise H.JavaException(*exc)
-    return r
+    return H.Jvm(H.build_shim(tmp_path_factory.mktemp("sim_jni"), _lib.LIB_PATH, one_tu=True))       # the four shim sources as one translation unit
 
 
 def test_the_java_entries_equal_the_binding(jvm):
@@ -341,13 +304,13 @@ def test_the_java_entries_equal_the_binding(jvm):
             # nDocTopicsTop: count first, then the arrays
             off, topics, weights = smp.doc_topics_top(W3, 0.03, 3)
             joff = jvm.longs(D + 1)
-            n = sim_call(jvm, "nDocTopicsTop", h, jvm.doubles(W3), 0, D, 0.03, 3, joff, None, None)
+            n = jvm.call("nDocTopicsTop", h, jvm.doubles(W3), 0, D, 0.03, 3, joff, None, None)
             assert n == len(topics) and np.array_equal(joff.get(), off)
             jt, jw = jvm.ints(n), jvm.doubles(n)
-            assert sim_call(jvm, "nDocTopicsTop", h, jvm.doubles(W3), 0, D, 0.03, 3, None, jt, jw) == n
+            assert jvm.call("nDocTopicsTop", h, jvm.doubles(W3), 0, D, 0.03, 3, None, jt, jw) == n
             assert np.array_equal(jt.get(), topics) and jw.get().tobytes() == weights.tobytes()
             jt2, jw2 = jvm.ints([-7] * 2), jvm.doubles([-7.0] * 2)               # too small: the count, arrays untouched, no exception
-            assert sim_call(jvm, "nDocTopicsTop", h, jvm.doubles(W3), 0, D, 0.03, 3, None, jt2, jw2) == n
+            assert jvm.call("nDocTopicsTop", h, jvm.doubles(W3), 0, D, 0.03, 3, None, jt2, jw2) == n
             assert (jt2.get() == -7).all() and (jw2.get() == -7.0).all()
             # nEntityTopicDistributions
             groups = groups_of(D, None)
@@ -355,26 +318,26 @@ def test_the_java_entries_equal_the_binding(jvm):
             mem = np.concatenate([np.asarray(x, np.int64) for x in groups])
             want = smp.entity_topic_distributions(W3, 0.03, groups, -1, 5)
             jo = jvm.doubles(len(groups) * K)
-            sim_call(jvm, "nEntityTopicDistributions", h, jvm.doubles(W3), 0.03, -1, 5, jvm.longs(moff), jvm.longs(mem), jo)
+            jvm.call("nEntityTopicDistributions", h, jvm.doubles(W3), 0.03, -1, 5, jvm.longs(moff), jvm.longs(mem), jo)
             assert jo.get().tobytes() == want.tobytes()
             # nSimilarPairs on those rows
             x = want[:D + 3]
             wi, wj, wv, wst = smp.similar_pairs(x, sn.COS_FOLDED, 0.15, min_weight=0.03)
             jx = jvm.doubles(x.ravel())
             jst, jmg = jvm.longs(5), jvm.doubles(1)
-            n = sim_call(jvm, "nSimilarPairs", h, sn.COS_FOLDED, x.shape[0], K, jx, 0.03, 0.15, 0, 0, None, None, None, jst, jmg)
+            n = jvm.call("nSimilarPairs", h, sn.COS_FOLDED, x.shape[0], K, jx, 0.03, 0.15, 0, 0, None, None, None, jst, jmg)
             assert n == len(wi) > 0
             ji, jj, js = jvm.ints(n), jvm.ints(n), jvm.doubles(n)
-            assert sim_call(jvm, "nSimilarPairs", h, sn.COS_FOLDED, x.shape[0], K, jx, 0.03, 0.15, 0, 0, ji, jj, js, jst, jmg) == n
+            assert jvm.call("nSimilarPairs", h, sn.COS_FOLDED, x.shape[0], K, jx, 0.03, 0.15, 0, 0, ji, jj, js, jst, jmg) == n
             assert np.array_equal(ji.get(), wi) and np.array_equal(jj.get(), wj) and js.get().tobytes() == wv.tobytes()
             assert list(jst.get()) == [wst.pairs_screened, wst.candidates, wst.emitted, wst.stripes, wst.regrown] and jmg.get()[0] == wst.margin
             ji2 = jvm.ints([-7])
-            assert sim_call(jvm, "nSimilarPairs", h, sn.COS_FOLDED, x.shape[0], K, jx, 0.03, 0.15, 0, 0, ji2, jvm.ints(1), jvm.doubles(1), None, None) == n
+            assert jvm.call("nSimilarPairs", h, sn.COS_FOLDED, x.shape[0], K, jx, 0.03, 0.15, 0, 0, ji2, jvm.ints(1), jvm.doubles(1), None, None) == n
             assert ji2.get()[0] == -7
             # a wrong array length is refused before the library is reached (mvhdp_last_error still holds the previous call's text)
             def refused(name, *args):
                 with pytest.raises(H.JavaException) as e:
-                    sim_call(jvm, name, *args)
+                    jvm.call(name, *args)
                 assert e.value.cls == IAE, e.value
             refused("nSimilarPairs", h, sn.COS, x.shape[0], K, jvm.doubles(x.size - 1), 0.03, 0.15, 0, 0, None, None, None, None, None)
             refused("nSimilarPairs", h, sn.COS, x.shape[0], K, jvm.doubles(x.size + 1), 0.03, 0.15, 0, 0, None, None, None, None, None)
@@ -391,7 +354,15 @@ def test_the_java_entries_equal_the_binding(jvm):
             refused("nEntityTopicDistributions", h, jvm.doubles(M - 1), 0.03, -1, 5, jvm.longs(moff), jvm.longs(mem), jo)
             # a library error becomes a RuntimeException
             with pytest.raises(H.JavaException) as e:
-                sim_call(jvm, "nSimilarPairs", h, sn.COS, x.shape[0], K, jx, 0.03, -1.0, 0, 0, None, None, None, None, None)
+                jvm.call("nSimilarPairs", h, sn.COS, x.shape[0], K, jx, 0.03, -1.0, 0, 0, None, None, None, None, None)
             assert e.value.cls == "java/lang/RuntimeException" and "threshold" in e.value.msg
         finally:
             j.close()
+        for closed in (j.handle, h):                                         # a closed sampler: its handle is 0; and the jlong it had is refused too
+            for name, args in (("nSimilarPairs", (sn.COS, x.shape[0], K, jx, 0.03, 0.15, 0, 0, None, None, None, None, None)),
+                               ("nDocTopicsTop", (jvm.doubles(W3), 0, D, 0.03, 3, None, None, None)),
+                               ("nEntityTopicDistributions", (jvm.doubles(W3), 0.03, -1, 5, jvm.longs(moff), jvm.longs(mem), jo))):
+                with pytest.raises(H.JavaException) as e:
+                    jvm.call(name, closed, *args)
+                assert e.value.cls == "java/lang/IllegalStateException" and e.value.msg == "NativeSampler is closed"
+        assert j.handle == 0 and h != 0

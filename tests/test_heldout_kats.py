@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from mvtopicmodel_amd import _lib
+from tests import jni_harness as H
 from tests import ltr_cases as lc
 from tests import ltr_ref as lr
 
@@ -143,10 +144,8 @@ def test_heldout_shim_type_checks_and_matches_the_java_class(tmp_path):
     stub = os.path.join(ROOT, "tests", "native", "jni_stub")
     inc = os.path.join(ROOT, "include")
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I", stub, "-I", inc, SHIM])
-    # the four shim sources as one translation unit (how the GPU test builds them)
-    four = tmp_path / "four.cpp"
-    four.write_text('#include "mvhdp_jni.cpp"\n#include "mvhdp_sim_jni.cpp"\n#include "mvhdp_phrases_jni.cpp"\n#include "mvhdp_heldout_jni.cpp"\n')
-    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-w", "-I", stub, "-I", inc, "-I", JAVA_DIR, str(four)])
+    # the shim sources compile together (one translation unit) and apart, and none holds a using-directive
+    assert H.check_sources_compile_together_and_apart()
     code = re.sub(r"//[^\n]*", "", open(SHIM).read())
     assert "Critical" not in code                                            # no critical region: the call blocks
     cxx = {"jlong": "long", "jint": "int", "jdouble": "double", "void": "void", "jintArray": "int[]", "jlongArray": "long[]", "jdoubleArray": "double[]"}
@@ -156,7 +155,9 @@ def test_heldout_shim_type_checks_and_matches_the_java_class(tmp_path):
            for r, n, params in re.findall(r"private static native ([\w\[\]]+) (n\w+)\(([^)]*)\);", open(JAVA).read())}
     assert set(ent) == {"nLeftToRight"} and ent == nat
     called = set(re.findall(r"\b(mvhdp_[a-z_]+)\s*\(", code))
-    assert called == {"mvhdp_heldout_left_to_right", "mvhdp_last_error"}
+    assert called == {"mvhdp_heldout_left_to_right"}
+    assert 'throw_rt(env, s->h, rc, "mvhdp_heldout_left_to_right")' in code  # ... whose message throw_rt (mvhdp_jni_common.h) fetches
+    assert len(re.findall(r"\bmvhdp_last_error\(h\)", H.common_header_code())) == 1
     # every array parameter is length-checked before the library call; the token arrays against the last entry of docOff
     for m in re.finditer(r"NativeHeldout_(n\w+)\(([^)]*)\)\s*\{", code):
         body = code[m.end():code.index("\n}\n", m.end())]
@@ -167,6 +168,9 @@ def test_heldout_shim_type_checks_and_matches_the_java_class(tmp_path):
             assert re.search(r"(bad_len\(env, %s\b|GetArrayLength\(%s\))" % (a, a), before), (m.group(1), a)
         assert re.search(r"GetLongArrayRegion\(docOff, \(jsize\)D, 1, &N\)", before) and re.search(r"bad_len\(env, tokens, N,", before)
         assert re.search(r"bad_len\(env, positionSum, N,", before)
-    assert len(re.findall(r"!e->ExceptionCheck\(\) \? e->Get\w+ArrayElements", code)) == 3
-    # the helpers live in a namespace of their own
-    assert "namespace mvhdp_heldout_jni {" in code and not re.search(r"using namespace", code)
+    # the wrappers are the shared header's, and the only way this source takes an array's elements
+    common = H.common_header_code()
+    assert len(re.findall(r"!e->ExceptionCheck\(\) \? e->Get\w+ArrayElements", common)) == 3 == len(re.findall(r"Get\w+ArrayElements", common))
+    assert "ArrayElements" not in code
+    # the handle goes through the registry: pinned for the call, never cast
+    assert len(re.findall(r"ShardPin pin_\(env, handle\); Shard\* s = pin_\.s;\n    if \(!s\) return", code)) == 1 and "reinterpret_cast" not in code

@@ -1,10 +1,12 @@
-"""The JNI shim (mvtopicmodel_amd/java/mvhdp_jni.cpp), compiled unmodified and RUN without a JVM and without a device.
+"""The JNI shim (the four sources of mvtopicmodel_amd/java, all 56 entries), compiled unmodified and RUN without a JVM and without a device.
 
 tests/jni_harness.py links it with a test-side JNIEnv (tests/native/fake_jvm.cpp) and either the real libmvhdp.so -- which loads on a
 machine without a device and answers MVHDP_ERR_NO_DEVICE -- or a stand-in (tests/native/fake_mvhdp.c) that logs and records what it
 is handed.  Here: the fake's own self-tests, the prototype table against the shim's and the Java class's signatures, the refusals
 that need no handle, and against the stand-in every length check of every entry, the lifecycle races, the tuning round trip and an
-injected array failure.  The same harness drives the real library on a device in tests/test_gpu_jni.py."""
+injected array failure -- for the entries of NativeSimilarity, NativePhrases and NativeHeldout as for NativeSampler's, and in both forms
+a host may build the sources in (the four on one command line; one translation unit), since the handle registry is shared between them.
+The same harness drives the real library on a device in tests/test_gpu_jni.py."""
 import ctypes as C
 import re
 import subprocess
@@ -29,7 +31,8 @@ class StandIn:
         fm.fm_log_at.restype = C.c_char_p
         fm.fm_counter.argtypes = [C.c_char_p]
         fm.fm_group_member.restype = fm.fm_destroyed.restype = C.c_void_p
-        self.jvm = H.Jvm(H.build_shim(tmp, self.path, name="libmvhdp_jni_standin.so"))
+        self.jvm = H.Jvm(H.build_shim(tmp, self.path, name="libmvhdp_jni_standin.so"))                 # the four sources on one command line
+        self.forms = {"four_sources": self.jvm, "one_tu": H.Jvm(H.build_shim(tmp, self.path, name="libmvhdp_jni_standin_one_tu.so", one_tu=True))}
 
     def reset(self, status=0):
         self.fm.fm_reset()
@@ -185,15 +188,17 @@ def test_fake_local_references_and_injected_failures(jvm):
 # ---- the table, the Java class, the shim's source ----
 def test_prototype_table_matches_the_shim_and_the_java_class():
     sig = H.shim_signatures()
-    assert len(sig) == 51 and sig == H.PROTOTYPES
+    assert len(sig) == 56 and sig == H.PROTOTYPES
     assert H.java_natives() == H.PROTOTYPES
+    per_class = {cls: sum(1 for v in sig.values() if v[2] == cls) for cls in H.CLASSES}
+    assert per_class == {"NativeSampler": 51, "NativeSimilarity": 3, "NativePhrases": 1, "NativeHeldout": 1}
 
 
 def test_the_fields_nSweep_asks_for_are_the_fields_of_SweepStats():
     src = open(H.SHIM).read()
-    body = src[src.index(H.PREFIX + "nSweep("):src.index(H.PREFIX + "nApplyDelta(")]
+    body = src[src.index(H.PREFIX["NativeSampler"] + "nSweep("):src.index(H.PREFIX["NativeSampler"] + "nApplyDelta(")]
     asked = {(name, {"L": "J", "I": "I", "D": "D"}[kind]) for kind, name in re.findall(r"set([LID])\(\"(\w+)\"", body)}
-    java = open(H.JAVA).read()
+    java = open(H.JAVA["NativeSampler"]).read()
     cls = java[java.index("public static final class SweepStats"):]
     cls = cls[:cls.index("}")]
     declared = set()
@@ -234,7 +239,7 @@ def test_create_without_a_device_raises_the_librarys_message_and_registers_nothi
 
 def _handle_argument_calls():
     """every entry that takes a handle or a group, with nothing but that argument filled in"""
-    for name, (ret, codes) in H.PROTOTYPES.items():
+    for name, (ret, codes, _) in H.PROTOTYPES.items():
         if name in ("nCreate", "nGroupUniqueId", "nGroupCreate"):
             continue
         assert codes[0] == "J"
@@ -259,6 +264,7 @@ K, V, D, NTOK, EC, TOPN, HL = 5, [7, 4], 3, [6, 4], 3, 2, 3
 M = len(V)
 R = V[0] + K
 DOC_OFF = [[0, 2, 2, 6], [0, 1, 3, 4]]
+SN, SD, CAP, CW = 4, 3, 6, 7                                  # similarPairs: rows, columns; the capacity of the pair / phrase arrays; of the phrases' words
 
 
 class A:
@@ -329,7 +335,21 @@ GOOD = {
                     A("I", TOPN, "embNearest topics", True), A("D", TOPN, "embNearest topicSims", True)],
     "nSetVectorsMix": ["h", 0.5, A("D", K * V[0], "setVectorsMix expDot [K*V_0]", "pair"), A("D", K, "setVectorsMix sumExp", "pair")],
     "nGetVectorsMix": ["h", A("D", V[0] * K, "getVectorsMix mix [V_0*K]", True)],
+    # NativeSimilarity, NativePhrases, NativeHeldout (the capacity arrays -- i, topics, counts, words -- go with any length)
+    "nSimilarPairs": ["h", 1, SN, SD, A("D", SN * SD, "similarPairs xFlat"), 0.03, 0.15, 0, 0, A("I", CAP, None), A("I", CAP, "similarPairs j"),
+                      A("D", CAP, "similarPairs sim"), A("J", 5, "similarPairs statsOut", True), A("D", 1, "similarPairs marginOut", True)],
+    "nDocTopicsTop": ["h", A("D", M, "docTopicsTop viewWeights"), 0, D, 0.03, 3, A("J", D + 1, "docTopicsTop rowOff", True), A("I", CAP, None),
+                      A("D", CAP, "docTopicsTop weights")],
+    "nEntityTopicDistributions": ["h", A("D", M, "entityTopicDistributions viewWeights"), 0.03, -1, 5, A("J", 3, None, values=[0, 2, 3]),
+                                  A("J", 3, None, values=[0, 1, 2]), A("D", 2 * K, "entityTopicDistributions out")],
+    "nTopicPhrases": ["h", 20, 0, A("J", K + 1, "topicPhrases topicOff", True), A("J", CAP + 1, "topicPhrases wordOff"), A("I", CW, None, True), A("I", CAP, None),
+                      A("J", K, "topicPhrases distinct", True), A("J", K, "topicPhrases occurrences", True), A("J", 2, "topicPhrases sizesOut"),
+                      A("J", 5, "topicPhrases statsOut", True)],
+    "nLeftToRight": ["h", 0, 3, 1, 17, 0, A("D", K, "heldout alpha", True), 0.0, A("J", D + 1, None, values=[0, 2, 2, 5]), A("I", 5, "heldout tokens"),
+                     A("D", D, "heldout docLl", True), A("D", 5, "heldout positionSum", True), A("J", D, "heldout docTokens", True),
+                     A("J", 3, "heldout statsOut", True)],
 }
+assert set(H.SIDE_ENTRIES) <= set(GOOD)
 NO_ARRAYS = {"h": ["nBuildCounts", "nBuildTrees", "nEmbCountWords"], "g": ["nGroupBuildCounts", "nGroupDrain", "nGroupAbort"]}
 
 
@@ -408,7 +428,7 @@ def test_every_length_check_of_every_entry(standin, model):
                 before = standin.fm.fm_log_len()
                 model.jvm.call(name, *model.args(name, (i, None)))
                 assert standin.fm.fm_log_len() > before, (name, i)
-    assert checked >= 150, checked
+    assert checked >= 190, checked
     # the rows of the double[][] arguments of setHyper: alpha[m] holds K + 1 entries, p_a[m] / p_b[m] hold M
     for i, want, label in ((1, K + 1, "setHyper alpha[m]"), (6, M, "setHyper p_a[m]"), (7, M, "setHyper p_b[m]")):
         for n in (want - 1, want + 1, None):
@@ -454,7 +474,7 @@ def test_scalar_arguments_out_of_range_are_refused_before_the_library(standin, m
            ("nGetDocTopicHist", 1, -1), ("nGetDocTopicHist", 3, 0), ("nGetCountHistogram", 1, M), ("nDpTableStatistics", 1, M), ("nDpTableStatistics", 3, 0),
            ("nGroupGetDocTopicHist", 1, M), ("nGroupGetDocTopicHist", 3, 0), ("nGroupGetCountHistogram", 1, -1), ("nGroupGammaDocStatistics", 1, M),
            ("nTopWords", 2, 0), ("nTopWords", 2, 65), ("nDiscrWeights", 2, M), ("nDiagnostics", 1, 0), ("nDiagnostics", 1, 65), ("nGroupDiagnostics", 1, 65),
-           ("nEmbNearest", 2, 0), ("nEmbNearest", 2, 65)]
+           ("nEmbNearest", 2, 0), ("nEmbNearest", 2, 65), ("nSimilarPairs", 2, -1), ("nSimilarPairs", 3, 0), ("nDocTopicsTop", 2, -1), ("nDocTopicsTop", 3, D + 1)]
     for name, i, v in bad:
         args = model.args(name)
         args[i] = v
@@ -494,6 +514,16 @@ def test_outputs_come_back_and_scalars_keep_their_order(standin, model):
     assert (nwk[0, 0], nk[0]) == (41, 43)                     # what the library wrote into the buffers reaches the Java arrays
     model.s.topWords(1, TOPN, K)
     assert (standin.counter("top_m"), standin.counter("top_n")) == (1, TOPN)
+    # the scalars the entries of the three other classes read back from the library
+    args = model.args("nSimilarPairs")
+    assert model.jvm.call("nSimilarPairs", *args) == 3
+    assert list(args[-2].get()) == [101, 102, 103, 104, 105] and args[-1].get()[0] == 0.625
+    assert model.jvm.call("nDocTopicsTop", *model.args("nDocTopicsTop")) == 2
+    args = model.args("nTopicPhrases")
+    assert model.jvm.call("nTopicPhrases", *args) == 3
+    assert list(args[-2].get()) == [3, 5] and list(args[-1].get()) == [201, 202, 203, 204, 205]
+    args = model.args("nLeftToRight")
+    assert model.jvm.call("nLeftToRight", *args) == -12.5 and list(args[-1].get()) == [301, 302, 303]
 
 
 def test_a_library_error_becomes_a_runtime_exception_with_its_message(standin, model):
@@ -601,6 +631,11 @@ def test_destroy_twice_destroys_once(standin, jvm):
     jvm.call("nDestroy", h)
     assert standin.counter("destroys") == 1
     raises(ISE, jvm.call, "nBuildCounts", h)
+    before = standin.fm.fm_log_len()
+    for name, rest in _handle_argument_calls():               # the jlong of a sampler closed a moment ago: refused by the side entries as well
+        if name in H.SIDE_ENTRIES:
+            raises(ISE, jvm.call, name, h, *rest, contains="NativeSampler is closed")
+    assert standin.fm.fm_log_len() == before
     g = JniGroup(jvm, [JniSampler(jvm, K, V)])
     gh = g.g
     jvm.call("nGroupDestroy", gh); jvm.call("nGroupDestroy", gh)
@@ -662,30 +697,86 @@ def closed_sampler(jvm):
     return s
 
 
-def test_destroy_waits_for_a_sweep_that_is_inside_the_library(standin, jvm):
-    standin.reset(0)
-    s = JniSampler(jvm, K, V)
+def _destroy_waits_for(standin, jvm, s, call, library_name):
+    """nDestroy on another thread while call() is held inside the library: it returns only once the call has; returns the call's result"""
     standin.fm.fm_block_sweeps(1)
-    sweeping, sbox = _in_thread(s.sweepMany, 0, 2, 1, 0)
+    inside, sbox = _in_thread(call)
     for _ in range(300):
         if standin.fm.fm_sweeps_inside() == 1:
             break
         time.sleep(0.01)
     if standin.fm.fm_sweeps_inside() != 1:
         standin.fm.fm_block_sweeps(0)
-        sweeping.join(30)
-        raise AssertionError(f"nSweepMany did not reach the library: {sbox}")
+        inside.join(30)
+        raise AssertionError(f"{library_name} was not reached: {sbox}")
     closing, cbox = _in_thread(jvm.call, "nDestroy", s.handle)
     try:
         time.sleep(0.3)
         assert closing.is_alive() and standin.counter("destroys") == 0
     finally:
         standin.fm.fm_block_sweeps(0)
-        sweeping.join(30); closing.join(30)
-    assert not sweeping.is_alive() and not closing.is_alive() and "error" not in sbox and "error" not in cbox
+        inside.join(30); closing.join(30)
+    assert not inside.is_alive() and not closing.is_alive() and "error" not in sbox and "error" not in cbox
     log = standin.log()
-    assert standin.fm.fm_sweeps_returned() == 1 and log.index("mvhdp_sweep_many") < log.index("mvhdp_destroy")
-    assert [st.tokens for st in sbox["value"]] == [1001, 2001]
+    assert standin.fm.fm_sweeps_returned() == 1 and log.index(library_name) < log.index("mvhdp_destroy")
+    return sbox["value"]
+
+
+def test_destroy_waits_for_a_sweep_that_is_inside_the_library(standin, jvm):
+    standin.reset(0)
+    s = JniSampler(jvm, K, V)
+    sts = _destroy_waits_for(standin, jvm, s, lambda: s.sweepMany(0, 2, 1, 0), "mvhdp_sweep_many")
+    assert [st.tokens for st in sts] == [1001, 2001]
+
+
+def test_destroy_waits_for_a_held_out_call_that_is_inside_the_library(standin, jvm):
+    """the entries outside mvhdp_jni.cpp pin the handle too: mvhdp_heldout_left_to_right, the longest call the shim makes"""
+    standin.reset(0)
+    s = JniSampler(jvm, K, V)
+    stats = jvm.longs(3)
+    args = [s.handle, 0, 3, 1, 17, 0, None, 0.0, jvm.longs([0, 2, 2, 5]), jvm.ints(np.ones(5)), None, None, None, stats]
+    assert _destroy_waits_for(standin, jvm, s, lambda: jvm.call("nLeftToRight", *args), "mvhdp_heldout_left_to_right") == -12.5
+    assert list(stats.get()) == [301, 302, 303]
+    raises(ISE, jvm.call, "nLeftToRight", *args, contains="NativeSampler is closed")
+
+
+@pytest.mark.parametrize("form", ["four_sources", "one_tu"])
+def test_each_build_form_has_one_registry_for_all_four_sources(standin, jvm, form):
+    """The four sources on one command line, and one translation unit that includes them: in either, an entry outside mvhdp_jni.cpp
+    finds the handle nCreate (inside it) registered, refuses one that was never issued or is closed, and nothing of the shared header
+    is exported -- a registry per source would refuse every handle, an exported one could be interposed."""
+    j = standin.forms[form]
+    standin.reset(0)
+    j.lib.fj_ledger_reset(); j.lib.fj_exception_clear()
+    for bogus in (0, 0x5a5a5a5a5a58, -8):
+        for name, rest in _handle_argument_calls():
+            if name not in ("nDestroy", "nGroupDestroy"):
+                e = raises(ISE, j.call, name, bogus, *rest)
+                assert e.msg in ("NativeSampler is closed", "group is closed"), (name, e.msg)
+    assert standin.log() == []
+    s = JniSampler(j, K, V)
+    s.setCorpus(0, DOC_OFF[0], np.arange(NTOK[0]) % V[0])
+    h, stats = s.handle, j.longs(5)
+    good = {"nSimilarPairs": [h, 1, SN, SD, j.doubles(SN * SD), 0.03, 0.15, 0, 0, j.ints(CAP), j.ints(CAP), j.doubles(CAP), stats, None],
+            "nDocTopicsTop": [h, j.doubles(M), 0, D, 0.03, 3, None, j.ints(CAP), j.doubles(CAP)],
+            "nEntityTopicDistributions": [h, j.doubles(M), 0.03, -1, 5, j.longs([0, 1]), j.longs([0]), j.doubles(K)],
+            "nTopicPhrases": [h, 20, 0, None, None, None, None, None, None, j.longs(2), None],
+            "nLeftToRight": [h, 0, 3, 1, 17, 0, None, 0.0, j.longs([0, 2]), j.ints([1, 2]), None, None, None, None]}
+    assert sorted(good) == sorted(H.SIDE_ENTRIES)
+    want = {"nSimilarPairs": 3, "nDocTopicsTop": 2, "nEntityTopicDistributions": None, "nTopicPhrases": 0, "nLeftToRight": -12.5}
+    for name, args in good.items():
+        assert j.call(name, *args) == want[name], name
+    assert list(stats.get()) == [101, 102, 103, 104, 105]
+    assert standin.log()[-5:] == ["mvhdp_similar_pairs", "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_topic_phrases",
+                                  "mvhdp_heldout_left_to_right"]
+    s.close()
+    for name, args in good.items():
+        raises(ISE, j.call, name, *args, contains="NativeSampler is closed")
+    exported = subprocess.check_output(["nm", "-D", "--defined-only", j.path], text=True).split("\n")
+    names = [line.split()[-1] for line in exported if line.strip()]
+    assert sum(n.startswith("Java_") for n in names) == 56
+    leaked = [n for n in names if "mvhdp_jni" in n or re.search(r"g_reg|g_shards|g_groups|throw_|bad_len|Pin|4Ints|5Longs|7Doubles", n)]
+    assert not leaked, leaked
 
 
 def test_a_failing_get_elements_leaves_the_library_uncalled_and_nothing_held(standin, model):
@@ -705,7 +796,7 @@ def test_a_failing_get_elements_leaves_the_library_uncalled_and_nothing_held(sta
 
 
 def test_every_entry_is_executed(standin, model):
-    """all 51, each through to the library and back (the stand-in answers MVHDP_OK)"""
+    """all 56, each through to the library and back (the stand-in answers MVHDP_OK)"""
     jvm = model.jvm
     jvm.log.clear()
     before = standin.fm.fm_log_len()
@@ -721,7 +812,7 @@ def test_every_entry_is_executed(standin, model):
     g2 = JniGroup(jvm, [s2])                                  # nGroupCreate
     g3 = JniGroup.ofRank(jvm, model.s, np.zeros(128), 0, 1)   # nGroupCreateRank
     g3.close(); g2.close(); s2.close()                        # nGroupDestroy, nDestroy
-    assert sorted(set(jvm.log)) == sorted(H.shim_signatures())
+    assert sorted(set(jvm.log)) == sorted(H.shim_signatures()) and len(set(jvm.log)) == 56
     called = set(standin.log()[before:])
     imports, _ = H.shim_imports(model.tmp)
     assert called == imports - {"mvhdp_last_error", "mvhdp_group_last_error"}      # every mvhdp_* the shim imports but the two messages

@@ -11,6 +11,7 @@ import pytest
 
 from mvtopicmodel_amd import _lib
 from mvtopicmodel_amd import native
+from tests import jni_harness as H
 from tests import phrases_numpy as pn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -131,10 +132,8 @@ def test_phrases_shim_type_checks_and_matches_the_java_class(tmp_path):
     stub = os.path.join(ROOT, "tests", "native", "jni_stub")
     inc = os.path.join(ROOT, "include")
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I", stub, "-I", inc, SHIM])
-    # the three shim sources as one translation unit (how the GPU test builds them)
-    three = tmp_path / "three.cpp"
-    three.write_text('#include "mvhdp_jni.cpp"\n#include "mvhdp_sim_jni.cpp"\n#include "mvhdp_phrases_jni.cpp"\n')
-    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-w", "-I", stub, "-I", inc, "-I", JAVA_DIR, str(three)])
+    # the shim sources compile together (one translation unit) and apart, and none holds a using-directive
+    assert H.check_sources_compile_together_and_apart()
     code = re.sub(r"//[^\n]*", "", open(SHIM).read())
     assert "Critical" not in code                                            # no critical region: the call blocks
     cxx = {"jlong": "long", "jint": "int", "void": "void", "jintArray": "int[]", "jlongArray": "long[]"}
@@ -144,7 +143,9 @@ def test_phrases_shim_type_checks_and_matches_the_java_class(tmp_path):
            for r, n, params in re.findall(r"private static native ([\w\[\]]+) (n\w+)\(([^)]*)\);", open(JAVA).read())}
     assert set(ent) == {"nTopicPhrases"} and ent == nat
     called = set(re.findall(r"\b(mvhdp_[a-z_]+)\s*\(", code))
-    assert called == {"mvhdp_topic_phrases", "mvhdp_last_error"}
+    assert called == {"mvhdp_topic_phrases"}
+    assert 'throw_rt(env, s->h, rc, "mvhdp_topic_phrases")' in code          # ... whose message throw_rt (mvhdp_jni_common.h) fetches
+    assert len(re.findall(r"\bmvhdp_last_error\(h\)", H.common_header_code())) == 1
     # every array parameter is length-checked before the library call
     for m in re.finditer(r"NativePhrases_(n\w+)\(([^)]*)\)\s*\{", code):
         body = code[m.end():code.index("\n}\n", m.end())]
@@ -154,6 +155,9 @@ def test_phrases_shim_type_checks_and_matches_the_java_class(tmp_path):
         for a in arrays:
             assert re.search(r"(bad_len\(env, %s\b|GetArrayLength\(%s\))" % (a, a), before), (m.group(1), a)
         assert before.count("ExceptionCheck") == 0                          # (the RAII wrappers do it: one ExceptionCheck in front of every Get)
-    assert len(re.findall(r"!e->ExceptionCheck\(\) \? e->Get\w+ArrayElements", code)) == 2
-    # the helpers live in a namespace of their own
-    assert "namespace mvhdp_phrases_jni {" in code and not re.search(r"using namespace", code)
+    # the wrappers are the shared header's, and the only way this source takes an array's elements
+    common = H.common_header_code()
+    assert len(re.findall(r"!e->ExceptionCheck\(\) \? e->Get\w+ArrayElements", common)) == 3 == len(re.findall(r"Get\w+ArrayElements", common))
+    assert "ArrayElements" not in code
+    # the handle goes through the registry: pinned for the call, never cast
+    assert len(re.findall(r"ShardPin pin_\(env, handle\); Shard\* s = pin_\.s;\n    if \(!s\) return", code)) == 1 and "reinterpret_cast" not in code

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from oracle import doc_topics as dto
+from tests import jni_harness as H
 from tests import sim_numpy as sn
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -195,10 +196,8 @@ def test_sim_shim_type_checks_and_matches_the_java_class(tmp_path):
     stub = os.path.join(ROOT, "tests", "native", "jni_stub")
     inc = os.path.join(ROOT, "include")
     subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-Wall", "-Werror", "-I", stub, "-I", inc, SHIM])
-    # both shim sources as one translation unit (how the GPU test builds them)
-    both = tmp_path / "both.cpp"
-    both.write_text('#include "mvhdp_jni.cpp"\n#include "mvhdp_sim_jni.cpp"\n')
-    subprocess.check_call(["g++", "-std=c++17", "-fsyntax-only", "-w", "-I", stub, "-I", inc, "-I", os.path.dirname(SHIM), str(both)])
+    # the shim sources compile together (one translation unit) and apart, and none holds a using-directive
+    assert H.check_sources_compile_together_and_apart()
     src = open(SHIM).read()
     code = re.sub(r"//[^\n]*", "", src)
     assert "Critical" not in code                                            # no critical region: every call blocks
@@ -209,7 +208,10 @@ def test_sim_shim_type_checks_and_matches_the_java_class(tmp_path):
     assert set(ent) == {"nSimilarPairs", "nDocTopicsTop", "nEntityTopicDistributions"} and ent == nat
     # every entry reaches its library function; the shim calls nothing else of the library but mvhdp_last_error
     called = set(re.findall(r"\b(mvhdp_[a-z_]+)\s*\(", code))
-    assert called == {"mvhdp_similar_pairs", "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_last_error"}
+    assert called == {"mvhdp_similar_pairs", "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions"}
+    for fn in called:                                                        # ... whose message throw_rt (mvhdp_jni_common.h) fetches
+        assert re.search(r'throw_rt\(env, s->h, rc, "%s"\)' % fn, code), fn
+    assert len(re.findall(r"\bmvhdp_last_error\(h\)", H.common_header_code())) == 1
     # every array parameter of every entry is length-checked before the library call
     for m in re.finditer(r"NativeSimilarity_(n\w+)\(([^)]*)\)\s*\{", code):
         body = code[m.end():code.index("\n}\n", m.end())]
@@ -217,4 +219,9 @@ def test_sim_shim_type_checks_and_matches_the_java_class(tmp_path):
         for a in re.findall(r"j(?:int|long|double)Array (\w+)", m.group(2)):
             assert re.search(r"(bad_len\(env, %s\b|GetArrayLength\(%s\))" % (a, a), before), (m.group(1), a)
         assert before.count("ExceptionCheck") == 0                          # (the RAII wrappers do it: one ExceptionCheck in front of every Get)
-    assert len(re.findall(r"!e->ExceptionCheck\(\) \? e->Get\w+ArrayElements", code)) == 3
+    # the wrappers are the shared header's, and the only way this source takes an array's elements
+    common = H.common_header_code()
+    assert len(re.findall(r"!e->ExceptionCheck\(\) \? e->Get\w+ArrayElements", common)) == 3 == len(re.findall(r"Get\w+ArrayElements", common))
+    assert "ArrayElements" not in code
+    # the handle goes through the registry: pinned for the call, never cast
+    assert len(re.findall(r"ShardPin pin_\(env, handle\); Shard\* s = pin_\.s;\n    if \(!s\) return", code)) == 3 and "reinterpret_cast" not in code
