@@ -438,6 +438,43 @@ int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_args* a, int
         double* doc_ll /*[D] or NULL*/, double* position_sum /*[N] or NULL: S[n], 0 for OOV*/,
         int64_t* doc_tokens /*[D] or NULL*/, mvhdp_heldout_stats* stats);
 
+/* Cross-view prediction: the types of view m ranked per entity by the model's own expectation, score(d, w) = sum_k theta_d[k] * phi[w][k].
+ * The reference has no counterpart (its flow ends at the similarity SQL): THIS definition is ours; tests/native/xview_ref.c restates it.
+ * theta_d[k]: the bits of mvhdp_doc_topic_proportions(h, view_weights, d, d + 1), its missing-view carry-over included.  A caller who
+ *   predicts view m from the other views passes view_weights[m] = 0.  The weights must be finite, none negative, their sum > 0 (else
+ *   MVHDP_ERR_INVALID_ARG).  args.theta, a host array [d1 - d0][K], replaces the proportions (view_weights may then be NULL); every entry
+ *   must be finite and >= 0 (else MVHDP_ERR_INVALID_ARG).
+ * phi[w][k] = ((double)n_wk[m][w][k] + beta[m]) / ((double)n_k[m][k] + betaSum[m]): one correctly rounded fp64 division; exactly 0.0 for a
+ *   topic in inActiveTopicIndex (PTM:2670-2671).  A vectors mix (mvhdp_set_vectors_mix) is NOT applied.
+ * score(d, w): s = +0.0; for k = 0 .. K - 1 ascending: s = fma(theta_d[k], phi[w][k], s) -- a fused fp64 multiply-add per topic, one chain,
+ *   no partial sums, no reassociation.
+ * Order of the view's types for an entity: score descending, equal scores by ascending type id.  (The comparison is that of the 64-bit
+ *   pattern made monotone -- sign bit set for a non-negative score, every bit flipped for a negative one -- which is the numeric order of
+ *   any two scores; with the arguments admitted above every score is finite and >= +0.0.)
+ * Excluded set of d (only with exclude_present != 0): the types < V_m that occur in d's view-m span of the handle's corpus.  They are never
+ *   listed and never counted in a rank.
+ * mvhdp_predict_items: per entity of [d0, d1) the first min(n, V_m - |excluded|) types in that order with their scores; counts[d - d0] says
+ *   how many; unused slots hold item -1 and score 0.0.  n >= 1; n > V_m is allowed.  On the device the list is placed by counting, for each
+ *   listed type, the listed types in front of it: n is meant to be small (the cost per entity grows with n^2 / 64).
+ * mvhdp_score_items: for pair i, score[i] = score(entity[i], item[i]), the same bits, and rank[i] = the number of types w' != item[i] of
+ *   view m that are not excluded for entity[i] and precede item[i] in the order (0-based).  The queried item is scored and ranked even
+ *   when it is itself excluded.  Pairs may come in any order and repeat; only entities that have pairs are computed.  Log-score, recall@N
+ *   and reciprocal rank are the host's to derive.
+ * Preconditions: as mvhdp_doc_topic_proportions (every view's corpus, the hyper-parameters), and counts that are current: no counts yet,
+ *   stale counts, or the pending deltas of a MVHDP_SWEEP_NO_APPLY sweep return MVHDP_ERR_STATE, as mvhdp_diagnostics does.
+ * MVHDP_ERR_INVALID_ARG, every output untouched: m out of range, a bad entity range, a NULL output, n < 1, a pair whose entity is outside
+ *   [d0, d1) or whose item is outside [0, V_m), bad weights or theta.  d0 == d1 or n_pairs == 0: MVHDP_OK, nothing written.
+ * No model state changes.  Integers and exact fp64 values decide every comparison: two calls give the same bits.
+ * On the device: phi formed once per call as fp64 [V_m][K] (in stripes of types beyond 256 MiB); a tiled fp64 kernel computes a block of
+ * scores [entities][V_m] (at most 256 MiB at a time; the D x V_m matrix never exists whole); one wave per entity selects behind it. */
+typedef struct { int32_t m; int32_t exclude_present; const double* view_weights /*[M] or NULL with theta*/;
+                 const double* theta /*[d1-d0][K] host, or NULL*/; } mvhdp_predict_args;
+int mvhdp_predict_items(mvhdp_handle h, const mvhdp_predict_args* a, int64_t d0, int64_t d1, int32_t n,
+                        int32_t* items /*[d1-d0][n]*/, double* scores /*[d1-d0][n]*/, int32_t* counts /*[d1-d0]*/);
+int mvhdp_score_items(mvhdp_handle h, const mvhdp_predict_args* a, int64_t d0, int64_t d1, int64_t n_pairs,
+                      const int64_t* entity /*[n_pairs], in [d0,d1), any order, repeats allowed*/, const int32_t* item /*[n_pairs], in [0,V_m)*/,
+                      double* score /*[n_pairs]*/, int32_t* rank /*[n_pairs]*/);
+
 /* ---- topic diagnostics: the step after training (FastQMVWVTopicModelDiagnostics, DIAG = MVTopicModel/FastQMVWVTopicModelDiagnostics.java;
  * SciTopicFlow builds it with N = 20 right after the save, whose saveExperiment / saveTopicsandExperiment call
  * calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230 from PTM:1370 / PTM:1507 and getSortedWords PTM:1792-1811 per view).
@@ -561,7 +598,7 @@ int mvhdp_emb_release(mvhdp_handle h);
  *     p_wt = lambda * (expDotProductValues[k][w] / sumExpValues[k]) + (1 - lambda) * ((n_wk + beta_0) / (n_k + betaSum_0))
  * in the document term of every view-0 token and in every leaf of a view-0 word tree (0 for an inactive topic, as ever).  Views m > 0,
  * modelLogLikelihood, the diagnostics, mvhdp_build_inference_trees, mvhdp_init_assignments_from_trees and MVHDP_SWEEP_FROZEN do not use it
- * (the inferencer's worker has lambda = 0, INF:251-252).
+ * (the inferencer's worker has lambda = 0, INF:251-252).  Nor do mvhdp_predict_items / mvhdp_score_items: their phi is the count term alone.
  * lambda == 0: mix off (the state after mvhdp_create: the kernels launched are those of a handle that never set one).  0 < lambda <= 1: on.
  * Anything else, NaN included: MVHDP_ERR_INVALID_ARG.  lambda is confined to [0, 1] because the samplers' certified prefix scan and their
  * fp32 screening rest on every term of the document sum being non-negative.

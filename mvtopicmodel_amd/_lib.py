@@ -16,7 +16,7 @@ ABI_SYMBOLS = [
     "mvhdp_get_counts", "mvhdp_set_counts", "mvhdp_get_tree", "mvhdp_get_doc_topic_hist",
     "mvhdp_get_count_histogram", "mvhdp_view_overlap_sums", "mvhdp_model_log_likelihood", "mvhdp_doc_topic_proportions",
     "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
-    "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right",
+    "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_predict_items", "mvhdp_score_items",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
@@ -165,6 +165,10 @@ class HeldoutStatsC(C.Structure):
     _fields_ = [("log_likelihood", C.c_double), ("tokens", C.c_int64), ("oov", C.c_int64), ("visits", C.c_int64)]
 
 
+class PredictArgsC(C.Structure):
+    _fields_ = [("m", C.c_int32), ("exclude_present", C.c_int32), ("view_weights", C.c_void_p), ("theta", C.c_void_p)]
+
+
 _lib = None
 _preloaded = []            # keeps the handles of the runtime libraries loaded on the library's behalf alive
 
@@ -279,6 +283,8 @@ def load_library():
     L.mvhdp_sim_probe.argtypes = [i32, i32, i32, C.POINTER(SimStatsC)]
     L.mvhdp_topic_phrases.argtypes = [vp, C.POINTER(PhraseArgsC), i64, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(PhraseStatsC)]
     L.mvhdp_heldout_left_to_right.argtypes = [vp, C.POINTER(HeldoutArgsC), i64, vp, vp, vp, vp, vp, C.POINTER(HeldoutStatsC)]
+    L.mvhdp_predict_items.argtypes = [vp, C.POINTER(PredictArgsC), i64, i64, i32, vp, vp, vp]
+    L.mvhdp_score_items.argtypes = [vp, C.POINTER(PredictArgsC), i64, i64, i64, vp, vp, vp, vp]
     L.mvhdp_gamma_doc_statistics.argtypes = [vp, i32, C.c_double, u64, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mvhdp_dp_table_statistics.argtypes = [vp, i32, vp, i32, vp, u64, u32, vp, vp]
     L.mvhdp_antoniak_draws.argtypes = [vp, i32, vp, vp, u64, u32, vp]

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   EmbConfigC, EmbStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, PhraseArgsC, PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
+                   EmbConfigC, EmbStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
@@ -209,6 +209,29 @@ class HeldoutResult:
     @property
     def perplexity(self):
         return float(np.exp(-self.log_likelihood / self.tokens)) if self.tokens else float("nan")
+
+
+@dataclass
+class ItemScores:
+    """mvhdp_score_items: per queried (entity, item) pair the model's score and the item's 0-based rank among the view's types that are
+    not excluded for the entity (include/mvhdp.h).  The summaries are the host's arithmetic on those two arrays."""
+    score: np.ndarray
+    rank: np.ndarray
+
+    def mean_log_score(self):
+        """mean over the pairs of log score (-inf if a score is 0; nan without pairs)"""
+        if len(self.score) == 0:
+            return float("nan")
+        with np.errstate(divide="ignore"):
+            return float(np.mean(np.log(self.score)))
+
+    def recall_at(self, n):
+        """the share of the pairs whose item is among the entity's first n"""
+        return float(np.mean(self.rank < int(n))) if len(self.rank) else float("nan")
+
+    def mrr(self):
+        """mean reciprocal rank, 1 / (rank + 1)"""
+        return float(np.mean(1.0 / (self.rank.astype(np.float64) + 1.0))) if len(self.rank) else float("nan")
 
 
 def _heldout_docs(doc_off, tokens):
@@ -603,6 +626,54 @@ class NativeSampler:
         st = HeldoutStatsC()
         self._ck(self.L.mvhdp_heldout_left_to_right(self.h, C.byref(a), D, _ptr(doc_off), _ptr(tokens), _ptr(doc_ll), _ptr(pos), _ptr(doc_tokens), C.byref(st)))
         return HeldoutResult(st.log_likelihood, doc_ll, pos, doc_tokens, st.tokens, st.oov, st.visits, int(particles))
+
+    # -- cross-view prediction (include/mvhdp.h mvhdp_predict_items / mvhdp_score_items) --
+    def _predict_args(self, m, view_weights, d0, d1, exclude_present, theta):
+        d0 = int(d0)
+        d1 = self.D if d1 is None else int(d1)
+        a = PredictArgsC(int(m), 1 if exclude_present else 0, None, None)
+        keep = []
+        if view_weights is not None:
+            w = np.ascontiguousarray(view_weights, dtype=np.float64)
+            if w.shape != (self.M,):
+                raise ValueError("view_weights must be [M]")
+            keep.append(w)
+            a.view_weights = w.ctypes.data
+        if theta is not None:
+            t = np.ascontiguousarray(theta, dtype=np.float64)
+            if t.shape != (max(d1 - d0, 0), self.K):
+                raise ValueError("theta must be [d1 - d0][K]")
+            keep.append(t)
+            a.theta = t.ctypes.data
+        return a, keep, d0, d1
+
+    def predict_items(self, m, view_weights, n, d0=0, d1=None, exclude_present=True, theta=None):
+        """The first n types of view m per entity of [d0, d1) by score(d, w) = sum_k theta_d[k] phi_m[w][k], score descending, equal
+        scores by type id: (items [d1-d0][n] (-1 unfilled), scores [d1-d0][n], counts [d1-d0]).  theta_d is
+        doc_topic_proportions(view_weights) -- pass view_weights[m] = 0 to predict the view from the others -- or the rows of theta.
+        exclude_present: the types the entity already holds in view m are not listed."""
+        a, keep, d0, d1 = self._predict_args(m, view_weights, d0, d1, exclude_present, theta)
+        n = int(n)
+        rows = max(d1 - d0, 0)
+        items = np.full((rows, max(n, 0)), -1, dtype=np.int32)
+        scores = np.zeros((rows, max(n, 0)), dtype=np.float64)
+        counts = np.zeros(rows, dtype=np.int32)
+        self._ck(self.L.mvhdp_predict_items(self.h, C.byref(a), d0, d1, n, _ptr(items), _ptr(scores), _ptr(counts)))
+        return items, scores, counts
+
+    def score_items(self, m, view_weights, entities, items, d0=0, d1=None, exclude_present=True, theta=None):
+        """Score and rank given (entity, item) pairs of view m -- the held-back items of a held-out evaluation: an ItemScores.  Entities
+        are ids of this handle inside [d0, d1), in any order, repeats allowed; rank counts the types that are not excluded for the
+        entity and come before the item (the item itself is ranked even if the entity holds it)."""
+        a, keep, d0, d1 = self._predict_args(m, view_weights, d0, d1, exclude_present, theta)
+        ent = np.ascontiguousarray(entities, dtype=np.int64)
+        it = np.ascontiguousarray(items, dtype=np.int32)
+        if ent.ndim != 1 or ent.shape != it.shape:
+            raise ValueError("entities and items: two arrays of one length")
+        score = np.zeros(len(ent), dtype=np.float64)
+        rank = np.zeros(len(ent), dtype=np.int32)
+        self._ck(self.L.mvhdp_score_items(self.h, C.byref(a), d0, d1, len(ent), _ptr(ent), _ptr(it), _ptr(score), _ptr(rank)))
+        return ItemScores(score, rank)
 
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
     def top_words(self, m, n):
@@ -1017,6 +1088,54 @@ class NativeGroup:
         return HeldoutResult(total, doc_ll, np.concatenate([p.position_sum for p in parts]) if want_position_sums else None,
                              np.concatenate([p.doc_tokens for p in parts]), sum(p.tokens for p in parts), sum(p.oov for p in parts),
                              sum(p.visits for p in parts), int(particles))
+
+    def _member_ranges(self, d0, d1):
+        """the LOCAL members' entities as one sequence, member after member: (member, first global id, local d0, local d1) of every
+        member that holds a part of [d0, d1)"""
+        bases = np.concatenate([[0], np.cumsum([s.D for s in self.members])]).astype(np.int64)
+        d1 = int(bases[-1]) if d1 is None else int(d1)
+        d0 = int(d0)
+        if d0 < 0 or d1 > int(bases[-1]) or d0 > d1:
+            raise ValueError("bad entity range")
+        out = []
+        for s, b, e in zip(self.members, bases[:-1], bases[1:]):
+            lo, hi = max(d0, int(b)), min(d1, int(e))
+            if lo < hi:
+                out.append((s, int(b), lo - int(b), hi - int(b)))
+        return out, d0, d1
+
+    def predict_items(self, m, view_weights, n, d0=0, d1=None, exclude_present=True, theta=None):
+        """NativeSampler.predict_items over the LOCAL members: the counts are replicated and the entities partitioned, so every member
+        answers for its own entities and the rows are concatenated in entity order (entity ids count through the members in their
+        order); per entity the values are a single handle's, bit for bit.  (As with doc_topic_proportions on a shard, the carry-over of
+        a missing view does not reach across a member's first entity.)"""
+        parts, d0, d1 = self._member_ranges(d0, d1)
+        th = None if theta is None else np.ascontiguousarray(theta, dtype=np.float64)
+        got = [s.predict_items(m, view_weights, n, lo, hi, exclude_present, None if th is None else th[b + lo - d0:b + hi - d0]) for s, b, lo, hi in parts]
+        if not got:
+            return np.full((0, int(n)), -1, dtype=np.int32), np.zeros((0, int(n))), np.zeros(0, dtype=np.int32)
+        return tuple(np.concatenate([g[i] for g in got]) for i in range(3))
+
+    def score_items(self, m, view_weights, entities, items, d0=0, d1=None, exclude_present=True, theta=None):
+        """NativeSampler.score_items over the LOCAL members: every pair goes to the member that holds its entity; the results come back
+        in the order of the pairs."""
+        parts, d0, d1 = self._member_ranges(d0, d1)
+        ent = np.ascontiguousarray(entities, dtype=np.int64)
+        it = np.ascontiguousarray(items, dtype=np.int32)
+        if ent.ndim != 1 or ent.shape != it.shape:
+            raise ValueError("entities and items: two arrays of one length")
+        if len(ent) and (ent.min() < d0 or ent.max() >= d1):
+            raise ValueError("an entity outside [d0, d1)")
+        th = None if theta is None else np.ascontiguousarray(theta, dtype=np.float64)
+        score = np.zeros(len(ent), dtype=np.float64)
+        rank = np.zeros(len(ent), dtype=np.int32)
+        for s, b, lo, hi in parts:
+            at = np.flatnonzero((ent >= b + lo) & (ent < b + hi))
+            if len(at) == 0:
+                continue
+            r = s.score_items(m, view_weights, ent[at] - b, it[at], lo, hi, exclude_present, None if th is None else th[b + lo - d0:b + hi - d0])
+            score[at], rank[at] = r.score, r.rank
+        return ItemScores(score, rank)
 
     def sweep(self, sweep_idx, seed, flags=0):
         """One sweep of the whole model; the list of the local members' statistics."""
