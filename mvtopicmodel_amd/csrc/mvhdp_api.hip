@@ -544,16 +544,12 @@ extern "C" int mvhdp_get_doc_topic_hist(mvhdp_handle h, int32_t m, int32_t* hist
         FAIL(h, MVHDP_ERR_INVALID_ARG, "get_doc_topic_hist: bad argument");
     int rc = require_corpus(h); if (rc) return rc;
     HIPC(h, hipSetDevice(h->device));
-    int32_t *d_hist = nullptr, *d_len = nullptr;
-    hipError_t e = hipSuccess;
-    if (hist) e = hipMalloc(&d_hist, (size_t)mm.K * hist_len * sizeof(int32_t));
-    if (e == hipSuccess && doc_len_counts) e = hipMalloc(&d_len, (size_t)len_len * sizeof(int32_t));
-    if (e == hipSuccess) e = mvhdp_launch_doc_topic_hist(mm, m, d_hist, hist_len, d_len, len_len, h->stream);
-    if (e == hipSuccess && hist) e = hipMemcpy(hist, d_hist, (size_t)mm.K * hist_len * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && doc_len_counts) e = hipMemcpy(doc_len_counts, d_len, (size_t)len_len * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (d_hist) hipFree(d_hist);
-    if (d_len) hipFree(d_len);
-    HIPC(h, e);
+    DevArray<int32_t> d_hist, d_len;
+    if (hist) HIPC(h, d_hist.alloc((size_t)mm.K * hist_len));
+    if (doc_len_counts) HIPC(h, d_len.alloc((size_t)len_len));
+    HIPC(h, mvhdp_launch_doc_topic_hist(mm, m, d_hist, hist_len, d_len, len_len, h->stream));   // (waits for the stream)
+    if (hist) HIPC(h, hipMemcpy(hist, d_hist, d_hist.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    if (doc_len_counts) HIPC(h, hipMemcpy(doc_len_counts, d_len, d_len.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
     return MVHDP_OK;
 }
 
@@ -890,13 +886,11 @@ extern "C" int mvhdp_get_count_histogram(mvhdp_handle h, int32_t m, int32_t* his
     if (m < 0 || m >= mm.M || !hist || len < 1) FAIL(h, MVHDP_ERR_INVALID_ARG, "get_count_histogram: bad argument");
     if (!h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "get_count_histogram before build_counts/set_counts");
     HIPC(h, hipSetDevice(h->device));
-    int32_t* d = nullptr;
-    HIPC(h, hipMalloc(&d, (size_t)len * sizeof(int32_t)));
-    hipError_t e = mvhdp_launch_count_hist(mm, m, d, len, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hist, d, (size_t)len * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d);
-    HIPC(h, e);
+    DevArray<int32_t> d;
+    HIPC(h, d.alloc((size_t)len));
+    HIPC(h, mvhdp_launch_count_hist(mm, m, d, len, h->stream));
+    HIPC(h, d.download(hist, (size_t)len, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
     return MVHDP_OK;
 }
 
@@ -910,15 +904,13 @@ int mvhdp_view_overlap_accumulate(mvhdp_ctx* h, double* acc)
     const int M = mm.M;
     if (mm.D == 0) return MVHDP_OK;
     HIPC(h, hipSetDevice(h->device));
-    double* d = nullptr;
+    DevArray<double> d;
     const size_t n = (size_t)M * M * mm.D;
-    HIPC(h, hipMalloc(&d, n * sizeof(double)));
+    HIPC(h, d.alloc(n));
     std::vector<double> host(n);
-    hipError_t e = mvhdp_launch_view_overlap(mm, d, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(host.data(), d, n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d);
-    HIPC(h, e);
+    HIPC(h, mvhdp_launch_view_overlap(mm, d, h->stream));
+    HIPC(h, d.download(host.data(), n, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < M * M; i++) {                     // PTM:2789-2792: sequential, entity order
         double a = acc[i];
         const double* col = host.data() + (size_t)i * mm.D;
@@ -953,8 +945,10 @@ int mvhdp_doc_topic_prepare(mvhdp_ctx* h, DocTopicCarry& carry)
                 if (has) last = d;                             // (a present view without tokens is refreshed to zeros, PTM:2873-2886)
                 src[(size_t)d] = last;
             }
-            HIPC(h, hipMalloc(&h->d_carry[m], (size_t)mm.D * sizeof(int64_t)));
-            HIPC(h, hipMemcpy(h->d_carry[m], src.data(), (size_t)mm.D * sizeof(int64_t), hipMemcpyHostToDevice));
+            DevArray<int64_t> d_src;                           // the handle's only once it is filled
+            HIPC(h, d_src.alloc(src.size()));
+            HIPC(h, hipMemcpy(d_src, src.data(), src.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+            h->d_carry[m] = d_src.release();
         }
         carry.src[m] = h->d_carry[m];
     }
@@ -971,17 +965,14 @@ extern "C" int mvhdp_doc_topic_proportions(mvhdp_handle h, const double* view_we
     if (d1 == d0) return MVHDP_OK;
     DocTopicCarry carry{};
     rc = mvhdp_doc_topic_prepare(h, carry); if (rc) return rc;
-    double *d_w = nullptr, *d_out = nullptr;
+    DevArray<double> d_w, d_out;
     const size_t n = (size_t)(d1 - d0) * mm.K;
-    hipError_t e = hipMalloc(&d_w, (size_t)mm.M * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_out, n * sizeof(double));
-    if (e == hipSuccess) e = hipMemcpyAsync(d_w, view_weights, (size_t)mm.M * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = mvhdp_launch_doc_topic_prop(mm, carry, d_w, d0, d1, d_out, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out, d_out, n * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (d_w) hipFree(d_w);
-    if (d_out) hipFree(d_out);
-    HIPC(h, e);
+    HIPC(h, d_w.alloc((size_t)mm.M));
+    HIPC(h, d_out.alloc(n));
+    HIPC(h, d_w.upload(view_weights, (size_t)mm.M, h->stream));
+    HIPC(h, mvhdp_launch_doc_topic_prop(mm, carry, d_w, d0, d1, d_out, h->stream));
+    HIPC(h, d_out.download(out, n, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
     return MVHDP_OK;
 }
 
@@ -995,14 +986,12 @@ extern "C" int mvhdp_gamma_doc_statistics(mvhdp_handle h, int32_t m, double gamm
     if (mm.D == 0) return MVHDP_OK;
     HIPC(h, hipSetDevice(h->device));
     const int NB = 1024;                                   // fixed: the summation order is part of the result
-    double* d_part = nullptr;
+    DevArray<double> d_part;
     std::vector<double> part(2 * NB);
-    hipError_t e = hipMalloc(&d_part, 2 * NB * sizeof(double));
-    if (e == hipSuccess) e = mvhdp_launch_gamma_doc_stats(mm, m, gamma_m, (uint32_t)seed, (uint32_t)(seed >> 32), round, d_part, NB, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(part.data(), d_part, 2 * NB * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (d_part) hipFree(d_part);
-    HIPC(h, e);
+    HIPC(h, d_part.alloc(2 * NB));
+    HIPC(h, mvhdp_launch_gamma_doc_stats(mm, m, gamma_m, (uint32_t)seed, (uint32_t)(seed >> 32), round, d_part, NB, h->stream));
+    HIPC(h, d_part.download(part.data(), 2 * NB, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
     double a = 0, b = 0;
     for (int i = 0; i < NB; i++) { a += part[2 * i]; b += part[2 * i + 1]; }
     *qs = a; *qw = b;
@@ -1021,21 +1010,18 @@ extern "C" int mvhdp_dp_table_statistics(mvhdp_handle h, int32_t m, const int32_
     if (m < 0 || m >= mm.M || !hist || hist_len < 1 || !conc || !mk || !active) FAIL(h, MVHDP_ERR_INVALID_ARG, "dp_table_statistics: bad argument");
     HIPC(h, hipSetDevice(h->device));
     const size_t hb = (size_t)K * hist_len * sizeof(int32_t);
-    void* d = nullptr;
-    hipError_t e = hipMalloc(&d, hb + (size_t)K * (2 * sizeof(double) + 8));
-    if (e != hipSuccess) HIPC(h, e);
-    int32_t* d_hist = (int32_t*)d;
-    double* d_conc = (double*)((char*)d + ((hb + 7) & ~(size_t)7));
+    DevArray<char> d;                                      // one block: hist [K][hist_len], padded to 8 bytes | conc [K] | mk [K] | active [K]
+    HIPC(h, d.alloc(hb + (size_t)K * (2 * sizeof(double) + 8)));
+    int32_t* d_hist = (int32_t*)d.get();
+    double* d_conc = (double*)(d.get() + ((hb + 7) & ~(size_t)7));
     double* d_mk = d_conc + K;
     uint8_t* d_act = (uint8_t*)(d_mk + K);
-    e = hipMemcpyAsync(d_hist, hist, hb, hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_conc, conc, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = mvhdp_launch_dp_tables(d_hist, hist_len, K, m, d_conc, (uint32_t)seed, (uint32_t)(seed >> 32), round, d_mk, d_act, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(mk, d_mk, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(active, d_act, (size_t)K, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d);
-    HIPC(h, e);
+    HIPC(h, hipMemcpyAsync(d_hist, hist, hb, hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(d_conc, conc, (size_t)K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, mvhdp_launch_dp_tables(d_hist, hist_len, K, m, d_conc, (uint32_t)seed, (uint32_t)(seed >> 32), round, d_mk, d_act, h->stream));
+    HIPC(h, hipMemcpyAsync(mk, d_mk, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipMemcpyAsync(active, d_act, (size_t)K, hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
     return MVHDP_OK;
 }
 
@@ -1046,17 +1032,14 @@ extern "C" int mvhdp_antoniak_draws(mvhdp_handle h, int32_t n, const int32_t* it
     if (n < 0 || (n > 0 && (!items || !conc || !tables))) FAIL(h, MVHDP_ERR_INVALID_ARG, "antoniak_draws: bad argument");
     if (n == 0) return MVHDP_OK;
     HIPC(h, hipSetDevice(h->device));
-    void* d = nullptr;
-    hipError_t e = hipMalloc(&d, (size_t)n * (sizeof(double) + 2 * sizeof(int32_t)));
-    if (e != hipSuccess) HIPC(h, e);
-    double* d_conc = (double*)d; int32_t* d_items = (int32_t*)(d_conc + n); int32_t* d_tab = d_items + n;
-    e = hipMemcpyAsync(d_conc, conc, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(d_items, items, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = mvhdp_launch_antoniak_draws(n, d_items, d_conc, (uint32_t)seed, (uint32_t)(seed >> 32), round, d_tab, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(tables, d_tab, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d);
-    HIPC(h, e);
+    DevArray<char> d;                                      // one block: conc [n] | items [n] | tables [n]
+    HIPC(h, d.alloc((size_t)n * (sizeof(double) + 2 * sizeof(int32_t))));
+    double* d_conc = (double*)d.get(); int32_t* d_items = (int32_t*)(d_conc + n); int32_t* d_tab = d_items + n;
+    HIPC(h, hipMemcpyAsync(d_conc, conc, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, hipMemcpyAsync(d_items, items, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, mvhdp_launch_antoniak_draws(n, d_items, d_conc, (uint32_t)seed, (uint32_t)(seed >> 32), round, d_tab, h->stream));
+    HIPC(h, hipMemcpyAsync(tables, d_tab, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
     return MVHDP_OK;
 }
 
@@ -1072,14 +1055,12 @@ int mvhdp_ll_doc_accumulate(mvhdp_ctx* h, int m, double* ll, int64_t* cnt)
     if (m < 0 || m >= mm.M) FAIL(h, MVHDP_ERR_INVALID_ARG, "model_log_likelihood: bad view");
     if (mm.D == 0) return MVHDP_OK;
     HIPC(h, hipSetDevice(h->device));
-    double* d_doc = nullptr;
-    HIPC(h, hipMalloc(&d_doc, (size_t)mm.D * sizeof(double)));
+    DevArray<double> d_doc;
+    HIPC(h, d_doc.alloc((size_t)mm.D));
     std::vector<double> hdoc((size_t)mm.D);
-    hipError_t e = mvhdp_launch_loglik_doc(mm, m, d_doc, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hdoc.data(), d_doc, (size_t)mm.D * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    hipFree(d_doc);
-    HIPC(h, e);
+    HIPC(h, mvhdp_launch_loglik_doc(mm, m, d_doc, h->stream));
+    HIPC(h, d_doc.download(hdoc.data(), (size_t)mm.D, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
     double a = *ll;
     int64_t c = *cnt;
     for (int64_t d = 0; d < mm.D; d++) {
@@ -1100,21 +1081,18 @@ int mvhdp_ll_model_finish(mvhdp_ctx* h, int m, double ll, int64_t modalityCnt, d
     if (std::isnan(ll) || std::isinf(ll)) { *out = 0; return MVHDP_OK; }                           // PTM:3375-3383
     HIPC(h, hipSetDevice(h->device));
     const int NP = 1024;
-    double* d_part = nullptr;
-    unsigned long long* d_nz = nullptr;
-    hipError_t e = hipMalloc(&d_part, NP * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc(&d_nz, sizeof(unsigned long long));
+    DevArray<double> d_part;
+    DevArray<unsigned long long> d_nz;
+    HIPC(h, d_part.alloc(NP));
+    HIPC(h, d_nz.alloc(1));
     std::vector<double> hpart(NP);
     std::vector<int32_t> nk((size_t)K);
     unsigned long long nz = 0;
-    if (e == hipSuccess) e = mvhdp_launch_loglik_topic(mm, m, d_part, NP, d_nz, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(hpart.data(), d_part, NP * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(&nz, d_nz, sizeof nz, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(nk.data(), mm.counts + mm.rowbase[M] * K + (int64_t)m * K, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-    if (d_part) hipFree(d_part);
-    if (d_nz) hipFree(d_nz);
-    HIPC(h, e);
+    HIPC(h, mvhdp_launch_loglik_topic(mm, m, d_part, NP, d_nz, h->stream));
+    HIPC(h, d_part.download(hpart.data(), NP, h->stream));
+    HIPC(h, d_nz.download(&nz, 1, h->stream));
+    HIPC(h, hipMemcpyAsync(nk.data(), mm.counts + mm.rowbase[M] * K + (int64_t)m * K, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, hipStreamSynchronize(h->stream));
     for (int i = 0; i < NP; i++) ll += hpart[i];                                                    // PTM:3389-3415
     if (std::isnan(ll) || std::isinf(ll)) ll = 0;
     const double bv = mm.beta[m] * mm.V[m];

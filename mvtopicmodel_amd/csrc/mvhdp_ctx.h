@@ -5,6 +5,7 @@
 #include "../../include/mvhdp.h"
 #include "mvhdp_plan.h"
 #include "mvhdp_state.h"
+#include "mvhdp_scratch.h"
 
 #include <algorithm>
 #include <functional>
@@ -118,6 +119,7 @@ bool mvhdp_is_live(mvhdp_ctx* h);
                         if ((h)->device_released) return MVHDP_ERR_STATE; /* the process is exiting */ } while (0)
 #define HIPC(h, call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { \
     (h)->err = std::string(#call) + ": " + hipGetErrorString(e_); return MVHDP_ERR_HIP; } } while (0)
+#define LAUNCH(h, ...) do { hipLaunchKernelGGL(__VA_ARGS__); HIPC(h, hipGetLastError()); } while (0)   // in a host function that returns int
 #define FAIL(h, code, msg) do { (h)->err = (msg); return (code); } while (0)
 
 enum { MVHDP_HEAVY_CAP = 8192 };             // heavy rows a live sweep keeps trees for (each holds 65535 tokens or more: beyond any corpus that fits a GPU)

@@ -292,12 +292,6 @@ __global__ __launch_bounds__(256) void diag_columns_kernel(const int32_t* __rest
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------
-struct DevBuf {                                       // hipFree on every path out
-    std::vector<void*> p;
-    template <class T> hipError_t get(T** out, size_t n) { void* q = nullptr; hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)); if (e == hipSuccess) p.push_back(q); *out = (T*)q; return e; }
-    ~DevBuf() { for (void* q : p) hipFree(q); }
-};
-
 int diag_ready(mvhdp_ctx* h, bool need_hyper)
 {
     for (int m = 0; m < h->mm.M; m++)
@@ -308,14 +302,14 @@ int diag_ready(mvhdp_ctx* h, bool need_hyper)
     return MVHDP_OK;
 }
 
-// the transposed n_wk of view m in a fresh device buffer (owned by bufs)
-hipError_t transpose_view(mvhdp_ctx* h, int m, DevBuf& bufs, int32_t** nkw)
+// the transposed n_wk of view m in a fresh device buffer
+hipError_t transpose_view(mvhdp_ctx* h, int m, DevArray<int32_t>& nkw)
 {
     const MvModel& mm = h->mm;
-    hipError_t e = bufs.get(nkw, (size_t)mm.V[m] * mm.K);
+    hipError_t e = nkw.alloc((size_t)mm.V[m] * mm.K);
     if (e != hipSuccess || mm.V[m] == 0) return e;
     dim3 grid((mm.V[m] + 63) / 64, (mm.K + 63) / 64);
-    hipLaunchKernelGGL(diag_transpose_kernel, grid, dim3(256), 0, h->stream, mm.counts + mm.rowbase[m] * mm.K, mm.V[m], mm.K, *nkw);
+    hipLaunchKernelGGL(diag_transpose_kernel, grid, dim3(256), 0, h->stream, mm.counts + mm.rowbase[m] * mm.K, mm.V[m], mm.K, nkw.get());
     return hipGetLastError();
 }
 
@@ -330,33 +324,31 @@ hipError_t launch_topn(mvhdp_ctx* h, const int32_t* nkw, int m, int n, int32_t* 
 int discr_weights_device(mvhdp_ctx* h, double* per_view, int want, double* tw_dev, int64_t* rowsum_dev)
 {
     const MvModel& mm = h->mm;
-    DevBuf b;
-    double *d_tw = nullptr, *d_ps = nullptr;
-    int64_t* d_rs = nullptr;
-    long long* d_pc = nullptr;
+    DevArray<double> d_tw, d_ps;
+    DevArray<int64_t> d_rs;
+    DevArray<long long> d_pc;
     int64_t vmax = 0;
     for (int m = 0; m < mm.M; m++) vmax = std::max<int64_t>(vmax, mm.V[m]);
-    HIPC(h, b.get(&d_tw, (size_t)vmax));
-    HIPC(h, b.get(&d_rs, (size_t)vmax));
-    HIPC(h, b.get(&d_ps, (size_t)mm.M * ROWS_BLOCKS));
-    HIPC(h, b.get(&d_pc, (size_t)mm.M * ROWS_BLOCKS));
+    HIPC(h, d_tw.alloc((size_t)vmax));
+    HIPC(h, d_rs.alloc((size_t)vmax));
+    HIPC(h, d_ps.alloc((size_t)mm.M * ROWS_BLOCKS));
+    HIPC(h, d_pc.alloc((size_t)mm.M * ROWS_BLOCKS));
     for (int m = 0; m < mm.M; m++) {
         const bool mine = m == want && tw_dev;
-        double* twm = mine ? tw_dev : d_tw;
-        int64_t* rsm = mine && rowsum_dev ? rowsum_dev : d_rs;
+        double* twm = mine ? tw_dev : d_tw.get();
+        int64_t* rsm = mine && rowsum_dev ? rowsum_dev : d_rs.get();
         if (mm.V[m] > 0)
-            hipLaunchKernelGGL(diag_rows_kernel, dim3(ROWS_BLOCKS), dim3(256), 0, h->stream, mm.counts + mm.rowbase[m] * mm.K, mm.V[m], mm.K,
-                               twm, rsm, d_ps + (size_t)m * ROWS_BLOCKS, d_pc + (size_t)m * ROWS_BLOCKS);
-        else {
+            LAUNCH(h, diag_rows_kernel, dim3(ROWS_BLOCKS), dim3(256), 0, h->stream, mm.counts + mm.rowbase[m] * mm.K, mm.V[m], mm.K,
+                   twm, rsm, d_ps + (size_t)m * ROWS_BLOCKS, d_pc + (size_t)m * ROWS_BLOCKS);
+        else {                                                                 // a part of each array: the byte counts by hand
             HIPC(h, hipMemsetAsync(d_ps + (size_t)m * ROWS_BLOCKS, 0, ROWS_BLOCKS * sizeof(double), h->stream));
             HIPC(h, hipMemsetAsync(d_pc + (size_t)m * ROWS_BLOCKS, 0, ROWS_BLOCKS * sizeof(long long), h->stream));
         }
-        HIPC(h, hipGetLastError());
     }
     std::vector<double> ps((size_t)mm.M * ROWS_BLOCKS);
     std::vector<long long> pc((size_t)mm.M * ROWS_BLOCKS);
-    HIPC(h, hipMemcpyAsync(ps.data(), d_ps, ps.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipMemcpyAsync(pc.data(), d_pc, pc.size() * sizeof(long long), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, d_ps.download(ps.data(), ps.size(), h->stream));
+    HIPC(h, d_pc.download(pc.data(), pc.size(), h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     double skewSum = 0;                                                    // PTM:2190-2191
     long long nonZeroSkewCnt = 1;
@@ -378,13 +370,12 @@ int mvhdp_diag_model(mvhdp_ctx* h, int N, DiagModel& dm)
     MvModel& mm = h->mm;
     const int K = mm.K, V0 = mm.V[0];
     HIPC(h, hipSetDevice(h->device));
-    DevBuf b;
-    int32_t *nkw = nullptr, *d_types = nullptr, *d_counts = nullptr, *d_nz = nullptr;
-    double* d_tw = nullptr;
-    int64_t* d_rs = nullptr;
-    HIPC(h, transpose_view(h, 0, b, &nkw));
-    HIPC(h, b.get(&d_types, (size_t)K * N)); HIPC(h, b.get(&d_counts, (size_t)K * N)); HIPC(h, b.get(&d_nz, (size_t)K));
-    HIPC(h, b.get(&d_tw, (size_t)V0)); HIPC(h, b.get(&d_rs, (size_t)V0));
+    DevArray<int32_t> nkw, d_types, d_counts, d_nz;
+    DevArray<double> d_tw;
+    DevArray<int64_t> d_rs;
+    HIPC(h, transpose_view(h, 0, nkw));
+    HIPC(h, d_types.alloc((size_t)K * N)); HIPC(h, d_counts.alloc((size_t)K * N)); HIPC(h, d_nz.alloc((size_t)K));
+    HIPC(h, d_tw.alloc((size_t)V0)); HIPC(h, d_rs.alloc((size_t)V0));
     HIPC(h, launch_topn(h, nkw, 0, N, d_types, d_counts, d_nz));
     dm.N = N;
     dm.per_view.assign((size_t)mm.M, 0.0);
@@ -392,11 +383,11 @@ int mvhdp_diag_model(mvhdp_ctx* h, int N, DiagModel& dm)
     dm.types.resize((size_t)K * N); dm.counts.resize((size_t)K * N); dm.nonzero.resize((size_t)K);
     dm.word_type_counts.resize((size_t)V0); dm.type_weight.resize((size_t)V0);
     dm.nk.resize((size_t)K);
-    HIPC(h, hipMemcpyAsync(dm.types.data(), d_types, dm.types.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipMemcpyAsync(dm.counts.data(), d_counts, dm.counts.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipMemcpyAsync(dm.nonzero.data(), d_nz, dm.nonzero.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipMemcpyAsync(dm.word_type_counts.data(), d_rs, (size_t)V0 * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipMemcpyAsync(dm.type_weight.data(), d_tw, (size_t)V0 * 8, hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, d_types.download(dm.types.data(), dm.types.size(), h->stream));
+    HIPC(h, d_counts.download(dm.counts.data(), dm.counts.size(), h->stream));
+    HIPC(h, d_nz.download(dm.nonzero.data(), dm.nonzero.size(), h->stream));
+    HIPC(h, d_rs.download(dm.word_type_counts.data(), (size_t)V0, h->stream));
+    HIPC(h, d_tw.download(dm.type_weight.data(), (size_t)V0, h->stream));
     HIPC(h, hipMemcpyAsync(dm.nk.data(), mm.counts + mm.rowbase[mm.M] * K, (size_t)K * 4, hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     return MVHDP_OK;
@@ -430,23 +421,22 @@ int mvhdp_diag_docs(mvhdp_ctx* h, const DiagModel& dm, DiagAcc& acc)
     const int64_t blocks = (mm.D + wpb - 1) / wpb;
     const int grid = (int)std::min<int64_t>(blocks, DOC_WAVES / wpb);
     const int G = grid * wpb;
-    DevBuf b;
-    int32_t *d_tlt = nullptr, *d_tln = nullptr, *d_ctr = nullptr, *d_codoc = nullptr, *d_err = nullptr;
-    int8_t *d_tlp = nullptr, *d_pos0 = nullptr;
-    double *d_part = nullptr, *d_scl = nullptr;
-    unsigned long long* d_tok = nullptr;
-    HIPC(h, b.get(&d_tlt, tl_types.size())); HIPC(h, b.get(&d_tln, tl_n.size())); HIPC(h, b.get(&d_tlp, tl_pos.size())); HIPC(h, b.get(&d_pos0, pos0.size()));
-    HIPC(h, b.get(&d_ctr, (size_t)K * NCTR)); HIPC(h, b.get(&d_codoc, (size_t)K * N * N)); HIPC(h, b.get(&d_err, 1));
-    HIPC(h, b.get(&d_part, (size_t)G * K)); HIPC(h, b.get(&d_scl, (size_t)K)); HIPC(h, b.get(&d_tok, 1));
+    DevArray<int32_t> d_tlt, d_tln, d_ctr, d_codoc, d_err;
+    DevArray<int8_t> d_tlp, d_pos0;
+    DevArray<double> d_part, d_scl;
+    DevArray<unsigned long long> d_tok;
+    HIPC(h, d_tlt.alloc(tl_types.size())); HIPC(h, d_tln.alloc(tl_n.size())); HIPC(h, d_tlp.alloc(tl_pos.size())); HIPC(h, d_pos0.alloc(pos0.size()));
+    HIPC(h, d_ctr.alloc((size_t)K * NCTR)); HIPC(h, d_codoc.alloc((size_t)K * N * N)); HIPC(h, d_err.alloc(1));
+    HIPC(h, d_part.alloc((size_t)G * K)); HIPC(h, d_scl.alloc((size_t)K)); HIPC(h, d_tok.alloc(1));
     const hipStream_t s = h->stream;
-    HIPC(h, hipMemcpyAsync(d_tlt, tl_types.data(), tl_types.size() * 4, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(d_tln, tl_n.data(), tl_n.size() * 4, hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(d_tlp, tl_pos.data(), tl_pos.size(), hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemcpyAsync(d_pos0, pos0.data(), pos0.size(), hipMemcpyHostToDevice, s));
-    HIPC(h, hipMemsetAsync(d_ctr, 0, (size_t)K * NCTR * 4, s));
-    HIPC(h, hipMemsetAsync(d_codoc, 0, (size_t)K * N * N * 4, s));
-    HIPC(h, hipMemsetAsync(d_err, 0, 4, s));
-    HIPC(h, hipMemsetAsync(d_tok, 0, 8, s));
+    HIPC(h, d_tlt.upload(tl_types.data(), tl_types.size(), s));
+    HIPC(h, d_tln.upload(tl_n.data(), tl_n.size(), s));
+    HIPC(h, d_tlp.upload(tl_pos.data(), tl_pos.size(), s));
+    HIPC(h, d_pos0.upload(pos0.data(), pos0.size(), s));
+    HIPC(h, d_ctr.fill(0, s));
+    HIPC(h, d_codoc.fill(0, s));
+    HIPC(h, d_err.fill(0, s));
+    HIPC(h, d_tok.fill(0, s));
     DiagDocArgs a{};
     a.doc_off = mm.doc_off[0]; a.tok = mm.tok[0]; a.z = mm.z[0];
     a.D = mm.D; a.K = K; a.V = mm.V[0]; a.N = N;
@@ -455,19 +445,17 @@ int mvhdp_diag_docs(mvhdp_ctx* h, const DiagModel& dm, DiagAcc& acc)
     a.g_ctr = d_ctr; a.codoc = d_codoc; a.partial = d_part; a.tokens = d_tok; a.err = d_err;
     a.wpb = wpb; a.lds_ctr = lds_ctr ? 1 : 0;
     HIPC(h, hipFuncSetAttribute((const void*)diag_doc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(diag_doc_kernel, dim3(grid), dim3(64 * wpb), lds, s, a);
-    HIPC(h, hipGetLastError());
-    hipLaunchKernelGGL(diag_sum_partials, dim3((K + 255) / 256), dim3(256), 0, s, d_part, G, K, d_scl);
-    HIPC(h, hipGetLastError());
+    LAUNCH(h, diag_doc_kernel, dim3(grid), dim3(64 * wpb), lds, s, a);
+    LAUNCH(h, diag_sum_partials, dim3((K + 255) / 256), dim3(256), 0, s, d_part, G, K, d_scl);
     std::vector<int32_t> ctr((size_t)K * NCTR), codoc((size_t)K * N * N);
     std::vector<double> scl((size_t)K);
     int32_t err = 0;
     unsigned long long ntok = 0;
-    HIPC(h, hipMemcpyAsync(ctr.data(), d_ctr, ctr.size() * 4, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(codoc.data(), d_codoc, codoc.size() * 4, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(scl.data(), d_scl, scl.size() * 8, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, s));
-    HIPC(h, hipMemcpyAsync(&ntok, d_tok, 8, hipMemcpyDeviceToHost, s));
+    HIPC(h, d_ctr.download(ctr.data(), ctr.size(), s));
+    HIPC(h, d_codoc.download(codoc.data(), codoc.size(), s));
+    HIPC(h, d_scl.download(scl.data(), scl.size(), s));
+    HIPC(h, d_err.download(&err, 1, s));
+    HIPC(h, d_tok.download(&ntok, 1, s));
     HIPC(h, hipStreamSynchronize(s));
     if (err) FAIL(h, MVHDP_ERR_STATE, "diagnostics: a view-0 token is unassigned or out of vocabulary (collectDocumentStatistics would throw, DIAG:171-173)");
     for (int k = 0; k < K; k++) {
@@ -493,18 +481,16 @@ int mvhdp_diag_finish(mvhdp_ctx* h, const DiagModel& dm, const DiagAcc& acc, con
     HIPC(h, hipSetDevice(h->device));
     std::vector<double> col((size_t)K * NCOL);
     {
-        DevBuf b;
-        int32_t *nkw = nullptr, *d_nk = nullptr;
-        int64_t* d_wtc = nullptr;
-        double *d_tw = nullptr, *d_col = nullptr;
-        HIPC(h, transpose_view(h, 0, b, &nkw));
-        HIPC(h, b.get(&d_nk, (size_t)K)); HIPC(h, b.get(&d_wtc, (size_t)V0)); HIPC(h, b.get(&d_tw, (size_t)V0)); HIPC(h, b.get(&d_col, col.size()));
-        HIPC(h, hipMemcpyAsync(d_nk, dm.nk.data(), (size_t)K * 4, hipMemcpyHostToDevice, h->stream));
-        HIPC(h, hipMemcpyAsync(d_wtc, dm.word_type_counts.data(), (size_t)V0 * 8, hipMemcpyHostToDevice, h->stream));
-        HIPC(h, hipMemcpyAsync(d_tw, dm.type_weight.data(), (size_t)V0 * 8, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(diag_columns_kernel, dim3(K), dim3(256), 0, h->stream, nkw, V0, d_nk, d_wtc, (double)acc.num_tokens, d_tw, d_col);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(col.data(), d_col, col.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        DevArray<int32_t> nkw, d_nk;
+        DevArray<int64_t> d_wtc;
+        DevArray<double> d_tw, d_col;
+        HIPC(h, transpose_view(h, 0, nkw));
+        HIPC(h, d_nk.alloc((size_t)K)); HIPC(h, d_wtc.alloc((size_t)V0)); HIPC(h, d_tw.alloc((size_t)V0)); HIPC(h, d_col.alloc(col.size()));
+        HIPC(h, d_nk.upload(dm.nk.data(), (size_t)K, h->stream));
+        HIPC(h, d_wtc.upload(dm.word_type_counts.data(), (size_t)V0, h->stream));
+        HIPC(h, d_tw.upload(dm.type_weight.data(), (size_t)V0, h->stream));
+        LAUNCH(h, diag_columns_kernel, dim3(K), dim3(256), 0, h->stream, nkw, V0, d_nk, d_wtc, (double)acc.num_tokens, d_tw, d_col);
+        HIPC(h, d_col.download(col.data(), col.size(), h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     const double nan = std::numeric_limits<double>::quiet_NaN();
@@ -619,15 +605,14 @@ extern "C" int mvhdp_top_words(mvhdp_handle h, int32_t m, int32_t n, int32_t* ty
     int rc = diag_ready(h, false); if (rc) return rc;
     HIPC(h, hipSetDevice(h->device));
     const int K = mm.K;
-    DevBuf b;
-    int32_t *nkw = nullptr, *d_t = nullptr, *d_c = nullptr, *d_nz = nullptr;
-    HIPC(h, transpose_view(h, m, b, &nkw));
-    HIPC(h, b.get(&d_t, (size_t)K * n)); HIPC(h, b.get(&d_c, (size_t)K * n)); HIPC(h, b.get(&d_nz, (size_t)K));
+    DevArray<int32_t> nkw, d_t, d_c, d_nz;
+    HIPC(h, transpose_view(h, m, nkw));
+    HIPC(h, d_t.alloc((size_t)K * n)); HIPC(h, d_c.alloc((size_t)K * n)); HIPC(h, d_nz.alloc((size_t)K));
     HIPC(h, launch_topn(h, nkw, m, n, d_t, d_c, d_nz));
     std::vector<int32_t> t((size_t)K * n), c((size_t)K * n), z((size_t)K);
-    HIPC(h, hipMemcpyAsync(t.data(), d_t, t.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipMemcpyAsync(c.data(), d_c, c.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPC(h, hipMemcpyAsync(z.data(), d_nz, z.size() * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, d_t.download(t.data(), t.size(), h->stream));
+    HIPC(h, d_c.download(c.data(), c.size(), h->stream));
+    HIPC(h, d_nz.download(z.data(), z.size(), h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     std::copy(t.begin(), t.end(), types); std::copy(c.begin(), c.end(), counts); std::copy(z.begin(), z.end(), nonzero);
     return MVHDP_OK;
@@ -641,13 +626,12 @@ extern "C" int mvhdp_discr_weights(mvhdp_handle h, double* per_view, int32_t m, 
     if (m < 0 || m >= mm.M) FAIL(h, MVHDP_ERR_INVALID_ARG, "discr_weights: bad view");
     int rc = diag_ready(h, false); if (rc) return rc;
     HIPC(h, hipSetDevice(h->device));
-    DevBuf b;
-    double* d_tw = nullptr;
-    if (type_weight) HIPC(h, b.get(&d_tw, (size_t)mm.V[m]));
+    DevArray<double> d_tw;
+    if (type_weight) HIPC(h, d_tw.alloc((size_t)mm.V[m]));
     std::vector<double> pv((size_t)mm.M), tw(type_weight ? (size_t)mm.V[m] : 0);
     rc = discr_weights_device(h, pv.data(), m, d_tw, nullptr); if (rc) return rc;
     if (type_weight && mm.V[m] > 0) {
-        HIPC(h, hipMemcpyAsync(tw.data(), d_tw, tw.size() * 8, hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, d_tw.download(tw.data(), tw.size(), h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
         std::copy(tw.begin(), tw.end(), type_weight);
     }

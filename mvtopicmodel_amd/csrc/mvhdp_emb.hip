@@ -365,12 +365,6 @@ __global__ __launch_bounds__(256) void emb_cos_kernel(const double* __restrict__
 
 int grid_for(int64_t n) { return (int)std::max<int64_t>(1, std::min<int64_t>((n + 255) / 256, 8192)); }
 
-struct EmbBuf {                                       // hipFree on every path out
-    std::vector<void*> p;
-    template <class T> hipError_t get(T** out, size_t n) { void* q = nullptr; hipError_t e = hipMalloc(&q, std::max<size_t>(n, 1) * sizeof(T)); if (e == hipSuccess) p.push_back(q); *out = (T*)q; return e; }
-    ~EmbBuf() { for (void* q : p) hipFree(q); }
-};
-
 }  // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -443,8 +437,7 @@ static int emb_init_state(mvhdp_ctx* h, const mvhdp_emb_config& c, const double*
         HIPC(h, hipMemcpy(e->w, weights, nb, hipMemcpyHostToDevice));
         HIPC(h, hipMemset(e->neg, 0, nb));
     } else {
-        hipLaunchKernelGGL(emb_init_kernel, dim3(grid_for(e->R * C)), dim3(256), 0, h->stream, e->w, e->neg, e->R, C, (uint32_t)seed, (uint32_t)(seed >> 32));
-        HIPC(h, hipGetLastError());
+        LAUNCH(h, emb_init_kernel, dim3(grid_for(e->R * C)), dim3(256), 0, h->stream, e->w, e->neg, e->R, C, (uint32_t)seed, (uint32_t)(seed >> 32));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     return MVHDP_OK;
@@ -484,16 +477,14 @@ extern "C" int mvhdp_emb_count_words(mvhdp_handle h)
     std::vector<unsigned long long> cnt((size_t)V0, 0);
     int32_t err = 0;
     {
-        EmbBuf b;
-        unsigned long long* d_cnt = nullptr;
-        int32_t* d_err = nullptr;
-        HIPC(h, b.get(&d_cnt, (size_t)V0)); HIPC(h, b.get(&d_err, 1));
-        HIPC(h, hipMemsetAsync(d_cnt, 0, (size_t)V0 * 8, h->stream));
-        HIPC(h, hipMemsetAsync(d_err, 0, 4, h->stream));
-        hipLaunchKernelGGL(emb_count_kernel, dim3(grid_for(N0)), dim3(256), 0, h->stream, h->mm.tok[0], N0, V0, d_cnt, d_err);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(cnt.data(), d_cnt, (size_t)V0 * 8, hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, h->stream));
+        DevArray<unsigned long long> d_cnt;
+        DevArray<int32_t> d_err;
+        HIPC(h, d_cnt.alloc((size_t)V0)); HIPC(h, d_err.alloc(1));
+        HIPC(h, d_cnt.fill(0, h->stream));
+        HIPC(h, d_err.fill(0, h->stream));
+        LAUNCH(h, emb_count_kernel, dim3(grid_for(N0)), dim3(256), 0, h->stream, h->mm.tok[0], N0, V0, d_cnt, d_err);
+        HIPC(h, d_cnt.download(cnt.data(), (size_t)V0, h->stream));
+        HIPC(h, d_err.download(&err, 1, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     if (err) FAIL(h, MVHDP_ERR_INVALID_ARG, "emb_count_words: a view-0 token is outside [0, V_0)");
@@ -521,14 +512,12 @@ extern "C" int mvhdp_emb_count_words(mvhdp_handle h)
     e->have_table = false;                                                               // (the table and retention are rewritten below)
     HIPC(h, hipMemcpyAsync(e->d_retention, retention.data(), (size_t)V0 * 8, hipMemcpyHostToDevice, h->stream));
     {
-        EmbBuf b;
-        double* d_dist = nullptr;
-        int32_t* d_sorted = nullptr;
-        HIPC(h, b.get(&d_dist, (size_t)V0)); HIPC(h, b.get(&d_sorted, (size_t)V0));
-        HIPC(h, hipMemcpyAsync(d_dist, dist.data(), (size_t)V0 * 8, hipMemcpyHostToDevice, h->stream));
-        HIPC(h, hipMemcpyAsync(d_sorted, sorted.data(), (size_t)V0 * 4, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(emb_table_kernel, dim3(grid_for(size)), dim3(256), 0, h->stream, d_dist, d_sorted, V0, dist[V0 - 1], size, e->table);
-        HIPC(h, hipGetLastError());
+        DevArray<double> d_dist;
+        DevArray<int32_t> d_sorted;
+        HIPC(h, d_dist.alloc((size_t)V0)); HIPC(h, d_sorted.alloc((size_t)V0));
+        HIPC(h, d_dist.upload(dist.data(), (size_t)V0, h->stream));
+        HIPC(h, d_sorted.upload(sorted.data(), (size_t)V0, h->stream));
+        LAUNCH(h, emb_table_kernel, dim3(grid_for(size)), dim3(256), 0, h->stream, d_dist, d_sorted, V0, dist[V0 - 1], size, e->table);
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     e->counts.swap(counts);
@@ -553,16 +542,13 @@ extern "C" int mvhdp_emb_train(mvhdp_handle h, int32_t epochs, uint64_t seed, ui
     HIPC(h, hipSetDevice(h->device));
     const hipStream_t st = h->stream;
     {   // every token and topic in range first: a refused call leaves the vectors as they were
-        EmbBuf b;
-        int32_t* d_err = nullptr;
+        DevArray<int32_t> d_err;
         int32_t err = 0;
-        HIPC(h, b.get(&d_err, 1));
-        HIPC(h, hipMemsetAsync(d_err, 0, 4, st));
-        if (N0 > 0) {
-            hipLaunchKernelGGL(emb_check_kernel, dim3(grid_for(N0)), dim3(256), 0, st, mm.tok[0], topics ? (const int32_t*)mm.z[0] : nullptr, N0, e->V0, mm.K, d_err);
-            HIPC(h, hipGetLastError());
-        }
-        HIPC(h, hipMemcpyAsync(&err, d_err, 4, hipMemcpyDeviceToHost, st));
+        HIPC(h, d_err.alloc(1));
+        HIPC(h, d_err.fill(0, st));
+        if (N0 > 0)
+            LAUNCH(h, emb_check_kernel, dim3(grid_for(N0)), dim3(256), 0, st, mm.tok[0], topics ? (const int32_t*)mm.z[0] : nullptr, N0, e->V0, mm.K, d_err);
+        HIPC(h, d_err.download(&err, 1, st));
         HIPC(h, hipStreamSynchronize(st));
         if (err & 1) FAIL(h, MVHDP_ERR_INVALID_ARG, "emb_train: a view-0 token is outside [0, V_0)");
         if (err & 2) FAIL(h, MVHDP_ERR_INVALID_ARG, "emb_train: a view-0 topic is unassigned or outside [0, K)");
@@ -620,9 +606,8 @@ extern "C" int mvhdp_emb_train(mvhdp_handle h, int32_t epochs, uint64_t seed, ui
         a.epoch = ep;
         HIPC(h, hipMemsetAsync(e->ctl, 0, sizeof(unsigned long long), st));
         HIPC(h, hipEventRecord(h->ev[0], st));
-        if (serial) hipLaunchKernelGGL(emb_train_kernel<false>, dim3(grid), dim3(block), lds, st, a);
-        else hipLaunchKernelGGL(emb_train_kernel<true>, dim3(grid), dim3(block), lds, st, a);
-        HIPC(h, hipGetLastError());
+        if (serial) LAUNCH(h, emb_train_kernel<false>, dim3(grid), dim3(block), lds, st, a);
+        else LAUNCH(h, emb_train_kernel<true>, dim3(grid), dim3(block), lds, st, a);
         HIPC(h, hipEventRecord(h->ev[1], st));
         HIPC(h, hipMemcpyAsync(part.data(), e->res_part, (size_t)waves * 8, hipMemcpyDeviceToHost, st));
         HIPC(h, hipMemcpyAsync(ctr, e->ctl + 1, sizeof(ctr), hipMemcpyDeviceToHost, st));
@@ -710,20 +695,15 @@ extern "C" int mvhdp_emb_softmax(mvhdp_handle h, int32_t reset_sums, double* exp
     if (!e->expdot) HIPC(h, hipMalloc(&e->expdot, (size_t)V0 * K * sizeof(double)));
     std::vector<double> sums((size_t)K);
     {
-        EmbBuf b;
-        double* d_sums = nullptr;
-        HIPC(h, b.get(&d_sums, (size_t)K));
-        hipLaunchKernelGGL(emb_dot_kernel, dim3(grid_for((int64_t)V0 * K)), dim3(256), 0, st, e->w, V0, K, C, e->expdot);
-        HIPC(h, hipGetLastError());
-        hipLaunchKernelGGL(emb_exp_kernel, dim3(K), dim3(256), 0, st, e->expdot, V0, K, d_sums);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(sums.data(), d_sums, (size_t)K * 8, hipMemcpyDeviceToHost, st));
+        DevArray<double> d_sums, d_t;
+        HIPC(h, d_sums.alloc((size_t)K));
+        LAUNCH(h, emb_dot_kernel, dim3(grid_for((int64_t)V0 * K)), dim3(256), 0, st, e->w, V0, K, C, e->expdot);
+        LAUNCH(h, emb_exp_kernel, dim3(K), dim3(256), 0, st, e->expdot, V0, K, d_sums);
+        HIPC(h, d_sums.download(sums.data(), (size_t)K, st));
         if (exp_dot) {
-            double* d_t = nullptr;
-            HIPC(h, b.get(&d_t, (size_t)V0 * K));
-            hipLaunchKernelGGL(emb_transpose_kernel, dim3((V0 + 31) / 32, (K + 31) / 32), dim3(256), 0, st, e->expdot, V0, K, d_t);
-            HIPC(h, hipGetLastError());
-            HIPC(h, hipMemcpyAsync(exp_dot, d_t, (size_t)V0 * K * 8, hipMemcpyDeviceToHost, st));
+            HIPC(h, d_t.alloc((size_t)V0 * K));
+            LAUNCH(h, emb_transpose_kernel, dim3((V0 + 31) / 32, (K + 31) / 32), dim3(256), 0, st, e->expdot, V0, K, d_t);
+            HIPC(h, d_t.download(exp_dot, (size_t)V0 * K, st));
         }
         HIPC(h, hipStreamSynchronize(st));
     }
@@ -744,13 +724,11 @@ extern "C" int mvhdp_emb_nearest(mvhdp_handle h, const double* query, int32_t n,
     HIPC(h, hipSetDevice(h->device));
     std::vector<double> sim((size_t)e->R);
     {
-        EmbBuf b;
-        double *d_q = nullptr, *d_s = nullptr;
-        HIPC(h, b.get(&d_q, (size_t)C)); HIPC(h, b.get(&d_s, (size_t)e->R));
-        HIPC(h, hipMemcpyAsync(d_q, query, (size_t)C * 8, hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(emb_cos_kernel, dim3(grid_for(e->R)), dim3(256), 0, h->stream, e->w, e->R, C, d_q, d_s);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(sim.data(), d_s, (size_t)e->R * 8, hipMemcpyDeviceToHost, h->stream));
+        DevArray<double> d_q, d_s;
+        HIPC(h, d_q.alloc((size_t)C)); HIPC(h, d_s.alloc((size_t)e->R));
+        HIPC(h, d_q.upload(query, (size_t)C, h->stream));
+        LAUNCH(h, emb_cos_kernel, dim3(grid_for(e->R)), dim3(256), 0, h->stream, e->w, e->R, C, d_q, d_s);
+        HIPC(h, d_s.download(sim.data(), (size_t)e->R, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     // IDSorter order (weight descending, equal weights by descending id), cut at n: a partial sort of V_0 + K values on the host
@@ -835,36 +813,31 @@ extern "C" int mvhdp_set_vectors_mix(mvhdp_handle h, double lambda, const double
     }
     for (int k = 0; k < K; k++) if (!(S_host[k] > 0.0) || !std::isfinite(S_host[k])) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: a sum_exp entry is not a positive finite number");
     // everything checked: from here on the new table replaces the old one
-    EmbBuf b;
-    double *d_S = nullptr, *d_e = nullptr, *d_new = nullptr;
-    HIPC(h, b.get(&d_S, (size_t)K));
-    if (exp_dot) HIPC(h, b.get(&d_e, n));
-    HIPC(h, hipMalloc(&d_new, n * sizeof(double)));
-    float* d_new32 = nullptr;
-    { hipError_t e32 = hipMalloc(&d_new32, n * sizeof(float) + 16); if (e32 != hipSuccess) { hipFree(d_new); HIPC(h, e32); } }
-    const hipStream_t st = h->stream;
-    unsigned int* d_bad = nullptr;
+    DevArray<double> d_S, d_e, d_new;
+    DevArray<float> d_new32;
+    DevArray<unsigned int> d_bad;
     unsigned int h_bad = 0;
-    { hipError_t eb = b.get(&d_bad, (size_t)1); if (eb != hipSuccess) { hipFree(d_new); hipFree(d_new32); HIPC(h, eb); } }
-    hipError_t er = hipMemsetAsync(d_bad, 0, sizeof(unsigned int), st);
-    if (er == hipSuccess) er = hipMemcpyAsync(d_S, S_host, (size_t)K * 8, hipMemcpyHostToDevice, st);
-    if (er == hipSuccess && exp_dot) er = hipMemcpyAsync(d_e, exp_dot, n * 8, hipMemcpyHostToDevice, st);
-    if (er == hipSuccess) {
-        if (exp_dot) hipLaunchKernelGGL(mix_from_kv_kernel, dim3(grid_for((int64_t)n)), dim3(256), 0, st, d_e, d_S, lambda, V0, K, d_new, d_new32, d_bad);
-        else         hipLaunchKernelGGL(mix_from_vk_kernel, dim3(grid_for((int64_t)n)), dim3(256), 0, st, h->emb->expdot, d_S, lambda, V0, K, d_new, d_new32, d_bad);
-        er = hipGetLastError();
-    }
-    if (er == hipSuccess) er = hipMemcpyAsync(&h_bad, d_bad, sizeof(unsigned int), hipMemcpyDeviceToHost, st);
-    if (er == hipSuccess) er = hipStreamSynchronize(st);
-    if (er != hipSuccess) { hipFree(d_new); hipFree(d_new32); HIPC(h, er); }
-    if (h_bad) {                                               // the mix in force stays as it is
-        hipFree(d_new); hipFree(d_new32);
-        FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: lambda * (exp_dot / sum_exp) is not finite (or beyond fp32's range) for some cell");
-    }
+    HIPC(h, d_S.alloc((size_t)K));
+    if (exp_dot) HIPC(h, d_e.alloc(n));
+    HIPC(h, d_new.alloc(n));
+    HIPC(h, d_new32.alloc(n + 4));                             // 16 bytes of slack behind the fp32 table
+    HIPC(h, d_bad.alloc(1));
+    const hipStream_t st = h->stream;
+    HIPC(h, d_bad.fill(0, st));
+    HIPC(h, d_S.upload(S_host, (size_t)K, st));
+    if (exp_dot) {
+        HIPC(h, d_e.upload(exp_dot, n, st));
+        LAUNCH(h, mix_from_kv_kernel, dim3(grid_for((int64_t)n)), dim3(256), 0, st, d_e, d_S, lambda, V0, K, d_new, d_new32, d_bad);
+    } else
+        LAUNCH(h, mix_from_vk_kernel, dim3(grid_for((int64_t)n)), dim3(256), 0, st, h->emb->expdot, d_S, lambda, V0, K, d_new, d_new32, d_bad);
+    HIPC(h, d_bad.download(&h_bad, 1, st));
+    HIPC(h, hipStreamSynchronize(st));
+    // the mix in force stays as it is
+    if (h_bad) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_vectors_mix: lambda * (exp_dot / sum_exp) is not finite (or beyond fp32's range) for some cell");
     if (h->d_mix) hipFree(h->d_mix);
     if (h->d_mix32) hipFree(h->d_mix32);
-    h->d_mix = d_new; h->d_mix32 = d_new32;
-    h->mm.mix = d_new; h->mm.mix32 = d_new32; h->mm.oml = 1.0 - lambda; h->mix_lambda = lambda;
+    h->d_mix = d_new.release(); h->d_mix32 = d_new32.release();
+    h->mm.mix = h->d_mix; h->mm.mix32 = h->d_mix32; h->mm.oml = 1.0 - lambda; h->mix_lambda = lambda;
     h->st.trees_outdated();
     return MVHDP_OK;
 }

@@ -218,12 +218,6 @@ __global__ __launch_bounds__(256) void heldout_reduce_kernel(const double* __res
     }
 }
 
-struct DevBuf {                                                // hipFree on scope exit
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { if (p) { hipFree(p); p = nullptr; } return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 template <int T>
 hipError_t launch_ltr(const HeldoutArgs& ka, bool vec, unsigned blocks, hipStream_t s)
@@ -278,10 +272,11 @@ extern "C" int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_a
         tab[at] = alpha[k];
         tab[(size_t)64 * T + at] = 1.0 / ((double)nk[(size_t)k] + beta_sum);
     }
-    DevBuf d_tab, d_head;
-    HIPC(h, d_tab.alloc(tab.size() * sizeof(double)));
-    HIPC(h, d_head.alloc(sizeof(u64)));
-    HIPC(h, hipMemcpyAsync(d_tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    DevArray<double> d_tab;
+    DevArray<u64> d_head;
+    HIPC(h, d_tab.alloc(tab.size()));
+    HIPC(h, d_head.alloc(1));
+    HIPC(h, d_tab.upload(tab.data(), tab.size(), h->stream));
 
     // ---- what the host can count ----
     mvhdp_heldout_stats st{};
@@ -315,23 +310,26 @@ extern "C" int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_a
             for (int64_t d = 0; d < Dc; d++) { c_order[(size_t)d] = (int32_t)d; longest = std::max(longest, c_off[(size_t)d + 1] - c_off[(size_t)d]); }
             std::stable_sort(c_order.begin(), c_order.end(), [&](int32_t l, int32_t r) {
                 return c_off[(size_t)l + 1] - c_off[(size_t)l] > c_off[(size_t)r + 1] - c_off[(size_t)r]; });
-            DevBuf d_off, d_tok, d_order, d_zs, d_P, d_S, d_ll;
-            HIPC(h, d_off.alloc((size_t)(Dc + 1) * sizeof(int64_t)));
-            HIPC(h, d_tok.alloc((size_t)Nc * sizeof(int32_t)));
-            HIPC(h, d_order.alloc((size_t)Dc * sizeof(int32_t)));
-            HIPC(h, d_P.alloc((size_t)R * Nc * sizeof(double)));
-            HIPC(h, d_S.alloc((size_t)Nc * sizeof(double)));
-            HIPC(h, d_ll.alloc((size_t)Dc * sizeof(double)));
-            if (longest > HELDOUT_ZCAP) HIPC(h, d_zs.alloc((size_t)R * Nc * sizeof(uint16_t)));
-            HIPC(h, hipMemcpyAsync(d_off.p, c_off.data(), (size_t)(Dc + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-            HIPC(h, hipMemcpyAsync(d_tok.p, tokens + t0, (size_t)Nc * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            HIPC(h, hipMemcpyAsync(d_order.p, c_order.data(), (size_t)Dc * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
-            HIPC(h, hipMemsetAsync(d_head.p, 0, sizeof(u64), h->stream));
+            DevArray<int64_t> d_off;
+            DevArray<int32_t> d_tok, d_order;
+            DevArray<uint16_t> d_zs;
+            DevArray<double> d_P, d_S, d_ll;
+            HIPC(h, d_off.alloc((size_t)Dc + 1));
+            HIPC(h, d_tok.alloc((size_t)Nc));
+            HIPC(h, d_order.alloc((size_t)Dc));
+            HIPC(h, d_P.alloc((size_t)R * Nc));
+            HIPC(h, d_S.alloc((size_t)Nc));
+            HIPC(h, d_ll.alloc((size_t)Dc));
+            if (longest > HELDOUT_ZCAP) HIPC(h, d_zs.alloc((size_t)R * Nc));
+            HIPC(h, d_off.upload(c_off.data(), (size_t)Dc + 1, h->stream));
+            HIPC(h, d_tok.upload(tokens + t0, (size_t)Nc, h->stream));
+            HIPC(h, d_order.upload(c_order.data(), (size_t)Dc, h->stream));
+            HIPC(h, d_head.fill(0, h->stream));
             HeldoutArgs ka{};
             ka.rows = mm.counts + mm.rowbase[m] * K;
-            ka.tab = d_tab.as<double>();
-            ka.doc_off = d_off.as<int64_t>(); ka.tok = d_tok.as<int32_t>(); ka.order = d_order.as<int32_t>();
-            ka.zs = d_zs.as<uint16_t>(); ka.P = d_P.as<double>(); ka.head = d_head.as<u64>();
+            ka.tab = d_tab;
+            ka.doc_off = d_off; ka.tok = d_tok; ka.order = d_order;
+            ka.zs = d_zs; ka.P = d_P; ka.head = d_head;
             ka.n_items = Dc * R; ka.Nc = Nc; ka.doc_global0 = a->doc_base + d0;
             ka.K = K; ka.V = V; ka.R = R; ka.resample = resample ? 1 : 0;
             ka.beta = beta; ka.alpha_sum = alpha_sum;
@@ -348,11 +346,9 @@ extern "C" int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_a
             }
             HIPC(h, e);
             const unsigned rblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((Dc + 3) / 4, (int64_t)h->num_cus * 8));
-            hipLaunchKernelGGL(heldout_reduce_kernel, dim3(rblocks), dim3(256), 0, h->stream, d_P.as<double>(), d_off.as<int64_t>(), d_tok.as<int32_t>(), Dc, Nc, V, R,
-                               std::log((double)R), d_S.as<double>(), d_ll.as<double>());
-            HIPC(h, hipGetLastError());
-            HIPC(h, hipMemcpyAsync(h_S.data() + t0, d_S.p, (size_t)Nc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-            HIPC(h, hipMemcpyAsync(h_ll.data() + d0, d_ll.p, (size_t)Dc * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            LAUNCH(h, heldout_reduce_kernel, dim3(rblocks), dim3(256), 0, h->stream, d_P, d_off, d_tok, Dc, Nc, V, R, std::log((double)R), d_S, d_ll);
+            HIPC(h, d_S.download(h_S.data() + t0, (size_t)Nc, h->stream));
+            HIPC(h, d_ll.download(h_ll.data() + d0, (size_t)Dc, h->stream));
             HIPC(h, hipStreamSynchronize(h->stream));
         }
         d0 = d1;

@@ -14,6 +14,7 @@
 // reference's order with one rounding per operation (Java never fuses a*b+c).
 #include "mvhdp_device.h"
 #include "mvhdp_slim.h"
+#include "mvhdp_scratch.h"
 #include "../../include/mvhdp.h"
 
 #include "mvhdp_wave.h"
@@ -1337,10 +1338,10 @@ __global__ void hist_bucket0_kernel(int32_t* hist, int32_t hist_len, int K, cons
 hipError_t mvhdp_launch_doc_topic_hist(const MvModel& mm, int m, int32_t* hist, int32_t hist_len,
                                        int32_t* doc_len_counts, int32_t len_len, hipStream_t s)
 {
-    int32_t* dwv = nullptr;                                  // [1 + K]: entities with the view, entities holding topic k
-    hipError_t e = hipMalloc(&dwv, (size_t)(1 + mm.K) * sizeof(int32_t));
+    DevArray<int32_t> dwv;                                   // [1 + K]: entities with the view, entities holding topic k
+    hipError_t e = dwv.alloc((size_t)(1 + mm.K));
     if (e != hipSuccess) return e;
-    e = hipMemsetAsync(dwv, 0, (size_t)(1 + mm.K) * sizeof(int32_t), s);
+    e = dwv.fill(0, s);
     if (e == hipSuccess && hist) e = hipMemsetAsync(hist, 0, (size_t)mm.K * hist_len * sizeof(int32_t), s);
     if (e == hipSuccess && doc_len_counts) e = hipMemsetAsync(doc_len_counts, 0, (size_t)len_len * sizeof(int32_t), s);
     if (e == hipSuccess) {
@@ -1357,15 +1358,14 @@ hipError_t mvhdp_launch_doc_topic_hist(const MvModel& mm, int m, int32_t* hist, 
         int64_t blocks = (mm.D + wpb - 1) / wpb;
         int grid = (int)(blocks < 1024 ? (blocks < 1 ? 1 : blocks) : 1024);
         if (e == hipSuccess) hipLaunchKernelGGL(doc_topic_hist_kernel, dim3(grid), dim3(64 * wpb), lds, s,
-                                                mm, m, hist, hist_len, doc_len_counts, len_len, dwv, CL);
+                                                mm, m, hist, hist_len, doc_len_counts, len_len, dwv.get(), CL);
         if (e == hipSuccess) e = hipGetLastError();
         if (e == hipSuccess && hist) {
-            hipLaunchKernelGGL(hist_bucket0_kernel, dim3((mm.K + 63) / 64), dim3(64), 0, s, hist, hist_len, mm.K, dwv);
+            hipLaunchKernelGGL(hist_bucket0_kernel, dim3((mm.K + 63) / 64), dim3(64), 0, s, hist, hist_len, mm.K, dwv.get());
             e = hipGetLastError();
         }
     }
-    const hipError_t es = hipStreamSynchronize(s);           // a kernel fault surfaces here, not on a later call
-    hipFree(dwv);
+    const hipError_t es = hipStreamSynchronize(s);           // a kernel fault surfaces here, not on a later call; dwv is freed behind it
     return e != hipSuccess ? e : es;
 }
 

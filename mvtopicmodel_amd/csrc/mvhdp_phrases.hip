@@ -249,13 +249,6 @@ __global__ __launch_bounds__(256) void phrase_words_kernel(const int32_t* __rest
     for (int64_t i = 0; i < len; i++) words[o + i] = tok[s + i];
 }
 
-struct DevBuf {                                                // hipFree on scope exit
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { if (p) { hipFree(p); p = nullptr; } return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return (T*)p; }
-};
-
 unsigned blocks_for(u64 n) { return (unsigned)((n + 255) / 256); }
 
 } // namespace
@@ -280,20 +273,19 @@ extern "C" int mvhdp_topic_phrases(mvhdp_handle h, const mvhdp_phrase_args* a, i
     mvhdp_phrase_stats st{};
 
     // ---- the walk, twice: sizes and validation, then the records ----
-    DevBuf ctl, rec, wave_room;
-    HIPC(h, ctl.alloc(PH_WORDS * sizeof(u64)));
-    HIPC(h, hipMemsetAsync(ctl.p, 0, PH_WORDS * sizeof(u64), h->stream));
+    DevArray<u64> ctl, wave_room;
+    DevArray<PhraseRec> rec;
+    HIPC(h, ctl.alloc(PH_WORDS));
+    HIPC(h, ctl.fill(0, h->stream));
     const unsigned walk_blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((D + 3) / 4, (int64_t)h->num_cus * 8));
     const size_t walk_waves = (size_t)walk_blocks * (256 / WV);
     std::vector<u64> room(walk_waves + 1, 0);                  // per wave of the walk's grid: its occurrences, then where its records start
     u64 hc[PH_WORDS] = {};
-    HIPC(h, wave_room.alloc(walk_waves * sizeof(u64)));
+    HIPC(h, wave_room.alloc(walk_waves));
     if (D > 0) {
-        hipLaunchKernelGGL(phrase_walk_kernel<false>, dim3(walk_blocks), dim3(256), 0, h->stream, mm.doc_off[0], tok, mm.z[0], D, K, mm.V[0], ctl.as<u64>(), wave_room.as<u64>(),
-                           (PhraseRec*)nullptr, (u64)0);
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(hc, ctl.p, sizeof hc, hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipMemcpyAsync(room.data(), wave_room.p, walk_waves * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+        LAUNCH(h, phrase_walk_kernel<false>, dim3(walk_blocks), dim3(256), 0, h->stream, mm.doc_off[0], tok, mm.z[0], D, K, mm.V[0], ctl, wave_room, (PhraseRec*)nullptr, (u64)0);
+        HIPC(h, ctl.download(hc, PH_WORDS, h->stream));
+        HIPC(h, wave_room.download(room.data(), walk_waves, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     if (hc[PH_BAD]) FAIL(h, MVHDP_ERR_STATE, "topic_phrases: a view-0 token is unassigned (set_assignments), or its topic or its type is out of range");
@@ -306,28 +298,26 @@ extern "C" int mvhdp_topic_phrases(mvhdp_handle h, const mvhdp_phrase_args* a, i
     std::vector<int32_t> c_len, c_cnt, c_words;
     std::vector<int64_t> c_woff(1, 0);
     if (n_occ > 0) {
-        HIPC(h, rec.alloc((size_t)n_occ * sizeof(PhraseRec)));
-        HIPC(h, hipMemsetAsync(rec.p, 0, (size_t)n_occ * sizeof(PhraseRec), h->stream));
-        HIPC(h, hipMemcpyAsync(wave_room.p, room.data(), walk_waves * sizeof(u64), hipMemcpyHostToDevice, h->stream));
-        hipLaunchKernelGGL(phrase_walk_kernel<true>, dim3(walk_blocks), dim3(256), 0, h->stream, mm.doc_off[0], tok, mm.z[0], D, K, mm.V[0], ctl.as<u64>(), wave_room.as<u64>(),
-                           rec.as<PhraseRec>(), n_occ);
-        HIPC(h, hipGetLastError());
+        HIPC(h, rec.alloc((size_t)n_occ));
+        HIPC(h, rec.fill(0, h->stream));
+        HIPC(h, wave_room.upload(room.data(), walk_waves, h->stream));
+        LAUNCH(h, phrase_walk_kernel<true>, dim3(walk_blocks), dim3(256), 0, h->stream, mm.doc_off[0], tok, mm.z[0], D, K, mm.V[0], ctl, wave_room, rec, n_occ);
 
         // ---- the count by key ----
         u64 cap = 64;
         while (cap < 2 * n_occ) cap <<= 1;
-        DevBuf slot_rec, slot_cnt, d_distinct, d_seg, cursor, ent_rec, ent_cnt, d_cut, d_reach, d_occ;
-        HIPC(h, slot_rec.alloc((size_t)cap * sizeof(u64)));
-        HIPC(h, slot_cnt.alloc((size_t)cap * sizeof(uint32_t)));
-        HIPC(h, d_distinct.alloc((size_t)K * sizeof(u64)));
-        HIPC(h, hipMemsetAsync(slot_rec.p, 0xff, (size_t)cap * sizeof(u64), h->stream));
-        HIPC(h, hipMemsetAsync(slot_cnt.p, 0, (size_t)cap * sizeof(uint32_t), h->stream));
-        HIPC(h, hipMemsetAsync(d_distinct.p, 0, (size_t)K * sizeof(u64), h->stream));
-        hipLaunchKernelGGL(phrase_insert_kernel, dim3(blocks_for(n_occ)), dim3(256), 0, h->stream, rec.as<PhraseRec>(), n_occ, tok, hash_mask,
-                           slot_rec.as<u64>(), slot_cnt.as<uint32_t>(), cap - 1, d_distinct.as<u64>(), ctl.as<u64>());
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(h_distinct.data(), d_distinct.p, (size_t)K * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipMemcpyAsync(hc, ctl.p, sizeof hc, hipMemcpyDeviceToHost, h->stream));
+        DevArray<u64> slot_rec, d_distinct, cursor, ent_rec;
+        DevArray<uint32_t> slot_cnt, ent_cnt, d_cut;
+        DevArray<int64_t> d_seg, d_reach, d_occ;
+        HIPC(h, slot_rec.alloc((size_t)cap));
+        HIPC(h, slot_cnt.alloc((size_t)cap));
+        HIPC(h, d_distinct.alloc((size_t)K));
+        HIPC(h, slot_rec.fill(0xff, h->stream));
+        HIPC(h, slot_cnt.fill(0, h->stream));
+        HIPC(h, d_distinct.fill(0, h->stream));
+        LAUNCH(h, phrase_insert_kernel, dim3(blocks_for(n_occ)), dim3(256), 0, h->stream, rec, n_occ, tok, hash_mask, slot_rec, slot_cnt, cap - 1, d_distinct, ctl);
+        HIPC(h, d_distinct.download((u64*)h_distinct.data(), (size_t)K, h->stream));   // counts: the same bits either way
+        HIPC(h, ctl.download(hc, PH_WORDS, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
         st.hash_collisions = (int64_t)hc[PH_COLLISIONS];
         for (int k = 0; k < K; k++) seg_off[(size_t)k + 1] = seg_off[(size_t)k] + h_distinct[(size_t)k];
@@ -335,52 +325,46 @@ extern "C" int mvhdp_topic_phrases(mvhdp_handle h, const mvhdp_phrase_args* a, i
         st.distinct = n_distinct;
 
         // ---- per topic: the cut, and who reaches it ----
-        HIPC(h, d_seg.alloc((size_t)(K + 1) * sizeof(int64_t)));
-        HIPC(h, cursor.alloc((size_t)K * sizeof(u64)));
-        HIPC(h, ent_rec.alloc((size_t)n_distinct * sizeof(u64)));
-        HIPC(h, ent_cnt.alloc((size_t)n_distinct * sizeof(uint32_t)));
-        HIPC(h, d_cut.alloc((size_t)K * sizeof(uint32_t)));
-        HIPC(h, d_reach.alloc((size_t)K * sizeof(int64_t)));
-        HIPC(h, d_occ.alloc((size_t)K * sizeof(int64_t)));
-        HIPC(h, hipMemcpyAsync(d_seg.p, seg_off.data(), (size_t)(K + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-        HIPC(h, hipMemsetAsync(cursor.p, 0, (size_t)K * sizeof(u64), h->stream));
-        hipLaunchKernelGGL(phrase_scatter_kernel, dim3(blocks_for(cap)), dim3(256), 0, h->stream, rec.as<PhraseRec>(), slot_rec.as<u64>(), slot_cnt.as<uint32_t>(), cap,
-                           d_seg.as<int64_t>(), cursor.as<u64>(), ent_rec.as<u64>(), ent_cnt.as<uint32_t>());
-        HIPC(h, hipGetLastError());
-        hipLaunchKernelGGL(phrase_select_kernel, dim3((unsigned)K), dim3(256), 0, h->stream, d_seg.as<int64_t>(), ent_cnt.as<uint32_t>(), a->max_per_topic,
-                           d_cut.as<uint32_t>(), d_reach.as<int64_t>(), d_occ.as<int64_t>());
-        HIPC(h, hipGetLastError());
-        HIPC(h, hipMemcpyAsync(h_reach.data(), d_reach.p, (size_t)K * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipMemcpyAsync(h_occ.data(), d_occ.p, (size_t)K * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, d_seg.alloc((size_t)K + 1));
+        HIPC(h, cursor.alloc((size_t)K));
+        HIPC(h, ent_rec.alloc((size_t)n_distinct));
+        HIPC(h, ent_cnt.alloc((size_t)n_distinct));
+        HIPC(h, d_cut.alloc((size_t)K));
+        HIPC(h, d_reach.alloc((size_t)K));
+        HIPC(h, d_occ.alloc((size_t)K));
+        HIPC(h, d_seg.upload(seg_off.data(), (size_t)K + 1, h->stream));
+        HIPC(h, cursor.fill(0, h->stream));
+        LAUNCH(h, phrase_scatter_kernel, dim3(blocks_for(cap)), dim3(256), 0, h->stream, rec, slot_rec, slot_cnt, cap, d_seg, cursor, ent_rec, ent_cnt);
+        LAUNCH(h, phrase_select_kernel, dim3((unsigned)K), dim3(256), 0, h->stream, d_seg, ent_cnt, a->max_per_topic, d_cut, d_reach, d_occ);
+        HIPC(h, d_reach.download(h_reach.data(), (size_t)K, h->stream));
+        HIPC(h, d_occ.download(h_occ.data(), (size_t)K, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
         for (int k = 0; k < K; k++) cand_off[(size_t)k + 1] = cand_off[(size_t)k] + h_reach[(size_t)k];
         const int64_t n_cand = cand_off[(size_t)K];
 
         // ---- what crosses: the kept phrases and the count ties at the cut ----
         if (n_cand > 0) {
-            DevBuf d_coff, c_start, d_len, d_cnt, d_woff, d_words;
-            HIPC(h, d_coff.alloc((size_t)(K + 1) * sizeof(int64_t)));
-            HIPC(h, c_start.alloc((size_t)n_cand * sizeof(int64_t)));
-            HIPC(h, d_len.alloc((size_t)n_cand * sizeof(int32_t)));
-            HIPC(h, d_cnt.alloc((size_t)n_cand * sizeof(int32_t)));
-            HIPC(h, hipMemcpyAsync(d_coff.p, cand_off.data(), (size_t)(K + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-            hipLaunchKernelGGL(phrase_pack_kernel, dim3((unsigned)K), dim3(256), 0, h->stream, rec.as<PhraseRec>(), d_seg.as<int64_t>(), ent_rec.as<u64>(), ent_cnt.as<uint32_t>(),
-                               d_cut.as<uint32_t>(), d_coff.as<int64_t>(), c_start.as<int64_t>(), d_len.as<int32_t>(), d_cnt.as<int32_t>());
-            HIPC(h, hipGetLastError());
+            DevArray<int64_t> d_coff, c_start, d_woff;
+            DevArray<int32_t> d_len, d_cnt, d_words;
+            HIPC(h, d_coff.alloc((size_t)K + 1));
+            HIPC(h, c_start.alloc((size_t)n_cand));
+            HIPC(h, d_len.alloc((size_t)n_cand));
+            HIPC(h, d_cnt.alloc((size_t)n_cand));
+            HIPC(h, d_coff.upload(cand_off.data(), (size_t)K + 1, h->stream));
+            LAUNCH(h, phrase_pack_kernel, dim3((unsigned)K), dim3(256), 0, h->stream, rec, d_seg, ent_rec, ent_cnt, d_cut, d_coff, c_start, d_len, d_cnt);
             c_len.resize((size_t)n_cand); c_cnt.resize((size_t)n_cand);
-            HIPC(h, hipMemcpyAsync(c_len.data(), d_len.p, (size_t)n_cand * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-            HIPC(h, hipMemcpyAsync(c_cnt.data(), d_cnt.p, (size_t)n_cand * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPC(h, d_len.download(c_len.data(), (size_t)n_cand, h->stream));
+            HIPC(h, d_cnt.download(c_cnt.data(), (size_t)n_cand, h->stream));
             HIPC(h, hipStreamSynchronize(h->stream));
             c_woff.resize((size_t)n_cand + 1);
             for (int64_t c = 0; c < n_cand; c++) c_woff[(size_t)c + 1] = c_woff[(size_t)c] + c_len[(size_t)c];
             const int64_t nw = c_woff[(size_t)n_cand];
-            HIPC(h, d_woff.alloc((size_t)(n_cand + 1) * sizeof(int64_t)));
-            HIPC(h, d_words.alloc((size_t)nw * sizeof(int32_t)));
-            HIPC(h, hipMemcpyAsync(d_woff.p, c_woff.data(), (size_t)(n_cand + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-            hipLaunchKernelGGL(phrase_words_kernel, dim3(blocks_for((u64)n_cand)), dim3(256), 0, h->stream, tok, c_start.as<int64_t>(), d_woff.as<int64_t>(), n_cand, d_words.as<int32_t>());
-            HIPC(h, hipGetLastError());
+            HIPC(h, d_woff.alloc((size_t)n_cand + 1));
+            HIPC(h, d_words.alloc((size_t)nw));
+            HIPC(h, d_woff.upload(c_woff.data(), (size_t)n_cand + 1, h->stream));
+            LAUNCH(h, phrase_words_kernel, dim3(blocks_for((u64)n_cand)), dim3(256), 0, h->stream, tok, c_start, d_woff, n_cand, d_words);
             c_words.resize((size_t)nw);
-            HIPC(h, hipMemcpyAsync(c_words.data(), d_words.p, (size_t)nw * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+            HIPC(h, d_words.download(c_words.data(), (size_t)nw, h->stream));
             HIPC(h, hipStreamSynchronize(h->stream));
         }
     }

@@ -357,18 +357,11 @@ __global__ __launch_bounds__(64) void group_sum_kernel(const int64_t* __restrict
     }
 }
 
-struct DevBuf {                                                // hipFree on scope exit
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { if (p) { hipFree(p); p = nullptr; } return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return (T*)p; }
-};
-
 struct KeySim { u64 key; double sim; };
 
 // The lists of entities [d0, d1) as CSR arrays on the device.  Two passes over chunks of entities (counts, then entries) so that the
 // dense [D][K] matrix never exists; a range that fits one chunk keeps its proportions between the passes.
-struct TopCsr { DevBuf off, topics, weights; std::vector<int64_t> h_off; int64_t total = 0; bool over_cap = false; };
+struct TopCsr { DevArray<int64_t> off; DevArray<int32_t> topics; DevArray<double> weights; std::vector<int64_t> h_off; int64_t total = 0; bool over_cap = false; };
 
 int build_top_csr(mvhdp_ctx* h, const double* view_weights, int64_t d0, int64_t d1, double threshold, int maxn, int by_topic, int64_t cap /* < 0: none */, TopCsr& csr)
 {
@@ -381,35 +374,33 @@ int build_top_csr(mvhdp_ctx* h, const double* view_weights, int64_t d0, int64_t 
     csr.total = 0;
     if (nd == 0) return MVHDP_OK;
     const int64_t chunk = std::max<int64_t>(1, std::min<int64_t>(nd, ((int64_t)256 << 20) / ((int64_t)K * 8)));
-    DevBuf w, prop, cnt;
-    HIPC(h, w.alloc((size_t)mm.M * sizeof(double)));
-    HIPC(h, prop.alloc((size_t)chunk * K * sizeof(double)));
-    HIPC(h, cnt.alloc((size_t)nd * sizeof(int32_t)));
-    HIPC(h, hipMemcpyAsync(w.p, view_weights, (size_t)mm.M * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    DevArray<double> w, prop;
+    DevArray<int32_t> cnt;
+    HIPC(h, w.alloc((size_t)mm.M));
+    HIPC(h, prop.alloc((size_t)chunk * K));
+    HIPC(h, cnt.alloc((size_t)nd));
+    HIPC(h, w.upload(view_weights, (size_t)mm.M, h->stream));
     auto grid = [](int64_t n) { return dim3((unsigned)(n < 16384 ? n : 16384)); };
     for (int64_t c0 = d0; c0 < d1; c0 += chunk) {
         const int64_t c1 = std::min(c0 + chunk, d1);
-        HIPC(h, mvhdp_launch_doc_topic_prop(mm, carry, w.as<double>(), c0, c1, prop.as<double>(), h->stream));
-        hipLaunchKernelGGL(top_count_kernel, grid(c1 - c0), dim3(WV), 0, h->stream, prop.as<double>(), c1 - c0, K, threshold, maxn, cnt.as<int32_t>() + (c0 - d0));
-        HIPC(h, hipGetLastError());
+        HIPC(h, mvhdp_launch_doc_topic_prop(mm, carry, w, c0, c1, prop, h->stream));
+        LAUNCH(h, top_count_kernel, grid(c1 - c0), dim3(WV), 0, h->stream, prop, c1 - c0, K, threshold, maxn, cnt + (c0 - d0));
     }
     std::vector<int32_t> h_cnt((size_t)nd);
-    HIPC(h, hipMemcpyAsync(h_cnt.data(), cnt.p, (size_t)nd * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
+    HIPC(h, cnt.download(h_cnt.data(), (size_t)nd, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     for (int64_t d = 0; d < nd; d++) csr.h_off[(size_t)d + 1] = csr.h_off[(size_t)d] + h_cnt[(size_t)d];
     csr.total = csr.h_off[(size_t)nd];
     if (cap >= 0 && csr.total > cap) { csr.over_cap = true; return MVHDP_OK; }
-    HIPC(h, csr.off.alloc((size_t)(nd + 1) * sizeof(int64_t)));
-    HIPC(h, csr.topics.alloc((size_t)csr.total * sizeof(int32_t)));
-    HIPC(h, csr.weights.alloc((size_t)csr.total * sizeof(double)));
-    HIPC(h, hipMemcpyAsync(csr.off.p, csr.h_off.data(), (size_t)(nd + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
+    HIPC(h, csr.off.alloc((size_t)nd + 1));
+    HIPC(h, csr.topics.alloc((size_t)csr.total));
+    HIPC(h, csr.weights.alloc((size_t)csr.total));
+    HIPC(h, csr.off.upload(csr.h_off.data(), (size_t)nd + 1, h->stream));
     const size_t lds = (size_t)K * sizeof(double) + (size_t)K;
     for (int64_t c0 = d0; c0 < d1; c0 += chunk) {
         const int64_t c1 = std::min(c0 + chunk, d1);
-        if (chunk < nd) HIPC(h, mvhdp_launch_doc_topic_prop(mm, carry, w.as<double>(), c0, c1, prop.as<double>(), h->stream));
-        hipLaunchKernelGGL(top_fill_kernel, grid(c1 - c0), dim3(WV), lds, h->stream, prop.as<double>(), c1 - c0, K, threshold, maxn, by_topic,
-                           csr.off.as<int64_t>() + (c0 - d0), csr.topics.as<int32_t>(), csr.weights.as<double>());
-        HIPC(h, hipGetLastError());
+        if (chunk < nd) HIPC(h, mvhdp_launch_doc_topic_prop(mm, carry, w, c0, c1, prop, h->stream));
+        LAUNCH(h, top_fill_kernel, grid(c1 - c0), dim3(WV), lds, h->stream, prop, c1 - c0, K, threshold, maxn, by_topic, csr.off + (c0 - d0), csr.topics, csr.weights);
     }
     HIPC(h, hipStreamSynchronize(h->stream));
     return MVHDP_OK;
@@ -455,27 +446,28 @@ extern "C" int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int6
 
     // rows are padded so that every tile of every stripe reads inside the image: a stripe may start at any row
     const int64_t n_pad = (int64_t)n + 2 * SIM_TILE, ld = ((int64_t)dim + SIM_BK - 1) / SIM_BK * SIM_BK;
-    DevBuf x, norm, cls, xn, ctr, cand, skey, ssim;
-    HIPC(h, x.alloc((size_t)n * dim * sizeof(double)));
-    HIPC(h, norm.alloc((size_t)n * sizeof(double)));
+    DevArray<double> x, norm, ssim;
+    DevArray<uint8_t> cls;
+    DevArray<float> xn;
+    DevArray<u64> ctr, cand, skey;
+    HIPC(h, x.alloc((size_t)n * dim));
+    HIPC(h, norm.alloc((size_t)n));
     HIPC(h, cls.alloc((size_t)n_pad));
-    HIPC(h, ctr.alloc(2 * sizeof(u64)));
-    HIPC(h, hipMemsetAsync(cls.p, 0, (size_t)n_pad, h->stream));
-    HIPC(h, hipMemcpyAsync(x.p, a->x, (size_t)n * dim * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(sim_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, x.as<double>(), n, dim, a->min_weight, norm.as<double>(), cls.as<uint8_t>());
-    HIPC(h, hipGetLastError());
+    HIPC(h, ctr.alloc(2));
+    HIPC(h, cls.fill(0, h->stream));
+    HIPC(h, x.upload(a->x, (size_t)n * dim, h->stream));
+    LAUNCH(h, sim_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, x, n, dim, a->min_weight, norm, cls);
     if (!jsd) {
-        HIPC(h, xn.alloc((size_t)n_pad * ld * sizeof(float)));
-        HIPC(h, hipMemsetAsync(xn.p, 0, (size_t)n_pad * ld * sizeof(float), h->stream));
+        HIPC(h, xn.alloc((size_t)n_pad * ld));
+        HIPC(h, xn.fill(0, h->stream));
         const int64_t cells = (int64_t)n * dim;
-        hipLaunchKernelGGL(sim_normalise_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, x.as<double>(), norm.as<double>(), cls.as<uint8_t>(), n, dim, ld, xn.as<float>());
-        HIPC(h, hipGetLastError());
+        LAUNCH(h, sim_normalise_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, x, norm, cls, n, dim, ld, xn);
     }
     u64 ccap = (u64)(a->candidate_capacity > 0 ? a->candidate_capacity : SIM_AUTO_CAPACITY);
     auto size_buffers = [&](u64 c) -> hipError_t {
-        hipError_t e = skey.alloc((size_t)c * sizeof(u64));
-        if (e == hipSuccess) e = ssim.alloc((size_t)c * sizeof(double));
-        if (e == hipSuccess && !jsd) e = cand.alloc((size_t)c * sizeof(u64));
+        hipError_t e = skey.alloc((size_t)c);
+        if (e == hipSuccess) e = ssim.alloc((size_t)c);
+        if (e == hipSuccess && !jsd) e = cand.alloc((size_t)c);
         return e;
     };
     HIPC(h, size_buffers(ccap));
@@ -492,15 +484,12 @@ extern "C" int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int6
         const dim3 grid((unsigned)nb, (unsigned)na);
         u64 hc[2] = {0, 0};
         for (int attempt = 0; ; attempt++) {
-            HIPC(h, hipMemsetAsync(ctr.p, 0, 2 * sizeof(u64), h->stream));
+            HIPC(h, ctr.fill(0, h->stream));
             if (jsd)
-                hipLaunchKernelGGL(sim_jsd_kernel, grid, dim3(256), 0, h->stream, x.as<double>(), cls.as<uint8_t>(), n, dim, (int)r0, (int)r1, a->threshold,
-                                   skey.as<u64>(), ssim.as<double>(), ccap, ctr.as<u64>());
+                LAUNCH(h, sim_jsd_kernel, grid, dim3(256), 0, h->stream, x, cls, n, dim, (int)r0, (int)r1, a->threshold, skey, ssim, ccap, ctr);
             else
-                hipLaunchKernelGGL(sim_screen_kernel, grid, dim3(256), 0, h->stream, xn.as<float>(), ld, (int)(ld / SIM_BK), cls.as<uint8_t>(), n, (int)r0, (int)r1, cut,
-                                   cand.as<u64>(), ccap, ctr.as<u64>());
-            HIPC(h, hipGetLastError());
-            HIPC(h, hipMemcpyAsync(hc, ctr.p, 2 * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+                LAUNCH(h, sim_screen_kernel, grid, dim3(256), 0, h->stream, xn, ld, (int)(ld / SIM_BK), cls, n, (int)r0, (int)r1, cut, cand, ccap, ctr);
+            HIPC(h, ctr.download(hc, 2, h->stream));
             HIPC(h, hipStreamSynchronize(h->stream));
             if (hc[0] <= ccap) break;
             if (attempt) FAIL(h, MVHDP_ERR_HIP, "similar_pairs: a stripe asked for more room twice");   // the count is a function of the data alone
@@ -512,10 +501,9 @@ extern "C" int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int6
         if (!jsd) {
             st.candidates += (int64_t)hc[0];
             if (hc[0]) {
-                hipLaunchKernelGGL(sim_exact_kernel, dim3((unsigned)((hc[0] + 255) / 256)), dim3(256), 0, h->stream, x.as<double>(), norm.as<double>(), dim, a->metric, a->threshold,
-                                   cand.as<u64>(), hc[0], skey.as<u64>(), ssim.as<double>(), ctr.as<u64>() + 1);
-                HIPC(h, hipGetLastError());
-                HIPC(h, hipMemcpyAsync(hc, ctr.p, 2 * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
+                LAUNCH(h, sim_exact_kernel, dim3((unsigned)((hc[0] + 255) / 256)), dim3(256), 0, h->stream, x, norm, dim, a->metric, a->threshold,
+                       cand, hc[0], skey, ssim, ctr + 1);
+                HIPC(h, ctr.download(hc, 2, h->stream));
                 HIPC(h, hipStreamSynchronize(h->stream));
             }
             nsurv = hc[1];
@@ -523,8 +511,8 @@ extern "C" int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int6
             st.candidates += (int64_t)nsurv;
         if (nsurv && !over && emitted + (int64_t)nsurv <= cap) {
             hk.resize((size_t)nsurv); hs.resize((size_t)nsurv);
-            HIPC(h, hipMemcpyAsync(hk.data(), skey.p, (size_t)nsurv * sizeof(u64), hipMemcpyDeviceToHost, h->stream));
-            HIPC(h, hipMemcpyAsync(hs.data(), ssim.p, (size_t)nsurv * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            HIPC(h, skey.download(hk.data(), (size_t)nsurv, h->stream));
+            HIPC(h, ssim.download(hs.data(), (size_t)nsurv, h->stream));
             HIPC(h, hipStreamSynchronize(h->stream));
             const size_t at = stripe.size();
             stripe.resize(at + (size_t)nsurv);
@@ -561,8 +549,8 @@ extern "C" int mvhdp_doc_topics_top(mvhdp_handle h, const double* view_weights, 
     *count = csr.total;
     if (csr.over_cap) FAIL(h, MVHDP_ERR_INVALID_ARG, "doc_topics_top: more entries than cap (count is set)");
     if (!count_only && csr.total > 0) {
-        HIPC(h, hipMemcpyAsync(topics, csr.topics.p, (size_t)csr.total * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-        HIPC(h, hipMemcpyAsync(weights, csr.weights.p, (size_t)csr.total * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPC(h, csr.topics.download(topics, (size_t)csr.total, h->stream));
+        HIPC(h, csr.weights.download(weights, (size_t)csr.total, h->stream));
         HIPC(h, hipStreamSynchronize(h->stream));
     }
     if (row_off) memcpy(row_off, csr.h_off.data(), csr.h_off.size() * sizeof(int64_t));
@@ -594,16 +582,16 @@ extern "C" int mvhdp_entity_topic_distributions(mvhdp_handle h, const double* vi
     }
     double scale = 0.0;
     if (round_digits >= 0) { scale = 1.0; for (int q = 0; q < round_digits; q++) scale = scale * 10.0; }   // exact: 10^15 < 2^53
-    DevBuf moff, mem, dout;
-    HIPC(h, moff.alloc((size_t)(n_groups + 1) * sizeof(int64_t)));
-    HIPC(h, mem.alloc((size_t)nm * sizeof(int64_t)));
-    HIPC(h, dout.alloc((size_t)n_groups * K * sizeof(double)));
-    HIPC(h, hipMemcpyAsync(moff.p, member_off, (size_t)(n_groups + 1) * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    if (nm) HIPC(h, hipMemcpyAsync(mem.p, members, (size_t)nm * sizeof(int64_t), hipMemcpyHostToDevice, h->stream));
-    hipLaunchKernelGGL(group_sum_kernel, dim3((unsigned)(n_groups < 16384 ? n_groups : 16384)), dim3(WV), (size_t)K * sizeof(double), h->stream,
-                       csr.off.as<int64_t>(), csr.topics.as<int32_t>(), csr.weights.as<double>(), n_groups, moff.as<int64_t>(), mem.as<int64_t>(), K, scale, dout.as<double>());
-    HIPC(h, hipGetLastError());
-    HIPC(h, hipMemcpyAsync(out, dout.p, (size_t)n_groups * K * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    DevArray<int64_t> moff, mem;
+    DevArray<double> dout;
+    HIPC(h, moff.alloc((size_t)n_groups + 1));
+    HIPC(h, mem.alloc((size_t)nm));
+    HIPC(h, dout.alloc((size_t)n_groups * K));
+    HIPC(h, moff.upload(member_off, (size_t)n_groups + 1, h->stream));
+    if (nm) HIPC(h, mem.upload(members, (size_t)nm, h->stream));
+    LAUNCH(h, group_sum_kernel, dim3((unsigned)(n_groups < 16384 ? n_groups : 16384)), dim3(WV), (size_t)K * sizeof(double), h->stream,
+           csr.off, csr.topics, csr.weights, n_groups, moff, mem, K, scale, dout);
+    HIPC(h, dout.download(out, (size_t)n_groups * K, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     return MVHDP_OK;
 }

@@ -283,12 +283,6 @@ __global__ __launch_bounds__(256) void xview_rank_kernel(const u64* __restrict__
     }
 }
 
-struct DevBuf {                                                // hipFree on scope exit
-    void* p = nullptr;
-    ~DevBuf() { if (p) hipFree(p); }
-    hipError_t alloc(size_t bytes) { if (p) { hipFree(p); p = nullptr; } return hipMalloc(&p, bytes ? bytes : 1); }
-    template <class T> T* as() const { return (T*)p; }
-};
 
 unsigned wave_blocks(int64_t waves, int num_cus) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)num_cus * 16)); }
 
@@ -364,11 +358,11 @@ int xview_run(mvhdp_ctx* h, const mvhdp_predict_args* a, int64_t d0, int64_t d1,
     hipStream_t s = h->stream;
 
     DocTopicCarry carry{};
-    DevBuf d_w;
+    DevArray<double> d_w;
     if (!a->theta) {
         int rc = mvhdp_doc_topic_prepare(h, carry); if (rc) return rc;
-        HIPC(h, d_w.alloc((size_t)mm.M * sizeof(double)));
-        HIPC(h, hipMemcpyAsync(d_w.p, a->view_weights, (size_t)mm.M * sizeof(double), hipMemcpyHostToDevice, s));
+        HIPC(h, d_w.alloc((size_t)mm.M));
+        HIPC(h, d_w.upload(a->view_weights, (size_t)mm.M, s));
     }
     const int32_t* d_rows = mm.counts + mm.rowbase[m] * K;
     const int32_t* d_nk = mm.counts + mm.rowbase[mm.M] * K + (int64_t)m * K;
@@ -379,33 +373,36 @@ int xview_run(mvhdp_ctx* h, const mvhdp_predict_args* a, int64_t d0, int64_t d1,
     const int64_t block_rows = std::max<int64_t>(1, std::min<int64_t>((int64_t)(bb / ((size_t)V * sizeof(double))), (int64_t)1 << 24));
     const int64_t stripe = std::min<int64_t>(V, per_k);
     const bool one_stripe = stripe >= V;
-    DevBuf d_phi;
-    HIPC(h, d_phi.alloc((size_t)stripe * K * sizeof(double)));
+    DevArray<double> d_phi;
+    HIPC(h, d_phi.alloc((size_t)stripe * K));
     auto launch_phi = [&](int64_t v0, int64_t nv) {
         const int64_t cells = nv * K;
         hipLaunchKernelGGL(xview_phi_kernel, dim3((unsigned)std::min<int64_t>((cells + 255) / 256, (int64_t)h->num_cus * 16)), dim3(256), 0, s,
-                           d_rows + v0 * K, d_nk, mm.inactive, K, cells, mm.beta[m], mm.beta_sum[m], d_phi.as<double>());
+                           d_rows + v0 * K, d_nk, mm.inactive, K, cells, mm.beta[m], mm.beta_sum[m], d_phi.get());
         return hipGetLastError();
     };
     if (one_stripe) HIPC(h, launch_phi(0, V));
 
     const int32_t n_cap = pr ? (int32_t)std::min<int64_t>(pr->n, V) : 0;
-    DevBuf d_theta, d_S, d_ent, d_list, d_counts, d_selk, d_seli, d_items, d_scores, d_prow, d_pitem, d_pscore, d_prank;
+    DevArray<double> d_theta, d_S, d_scores, d_pscore;          // d_S and d_pscore are also read as u64 keys (the mark, rank and select kernels)
+    DevArray<int64_t> d_ent;
+    DevArray<int32_t> d_list, d_counts, d_seli, d_items, d_prow, d_pitem, d_prank;
+    DevArray<u64> d_selk;
     std::vector<int64_t> h_ent;
     std::vector<int32_t> h_list, h_prow, h_pitem, c_items, c_counts, c_rank;
     std::vector<double> c_scores, c_pscore;
     int64_t pcur = 0;                                          // score_items: the next pair of pw->order
     const int64_t max_range = std::min(range_len, d1 - d0), max_nr = std::min(block_rows, pw ? std::min(pw->n, d1 - d0) : d1 - d0);
-    HIPC(h, d_theta.alloc((size_t)max_range * K * sizeof(double)));
-    HIPC(h, d_S.alloc((size_t)max_nr * V * sizeof(double)));
-    if (excl) HIPC(h, d_ent.alloc((size_t)max_nr * sizeof(int64_t)));
-    if (pw) HIPC(h, d_list.alloc((size_t)max_nr * sizeof(int32_t)));
+    HIPC(h, d_theta.alloc((size_t)max_range * K));
+    HIPC(h, d_S.alloc((size_t)max_nr * V));
+    if (excl) HIPC(h, d_ent.alloc((size_t)max_nr));
+    if (pw) HIPC(h, d_list.alloc((size_t)max_nr));
     else {
-        HIPC(h, d_counts.alloc((size_t)max_nr * sizeof(int32_t)));
-        HIPC(h, d_selk.alloc((size_t)max_nr * n_cap * sizeof(u64)));
-        HIPC(h, d_seli.alloc((size_t)max_nr * n_cap * sizeof(int32_t)));
-        HIPC(h, d_items.alloc((size_t)max_nr * n_cap * sizeof(int32_t)));
-        HIPC(h, d_scores.alloc((size_t)max_nr * n_cap * sizeof(double)));
+        HIPC(h, d_counts.alloc((size_t)max_nr));
+        HIPC(h, d_selk.alloc((size_t)max_nr * n_cap));
+        HIPC(h, d_seli.alloc((size_t)max_nr * n_cap));
+        HIPC(h, d_items.alloc((size_t)max_nr * n_cap));
+        HIPC(h, d_scores.alloc((size_t)max_nr * n_cap));
     }
 
     for (int64_t c0 = d0; c0 < d1; c0 += range_len) {
@@ -422,26 +419,25 @@ int xview_run(mvhdp_ctx* h, const mvhdp_predict_args* a, int64_t d0, int64_t d1,
             n_rows_range = (int64_t)h_list.size();
             if (n_rows_range == 0) continue;
         }
-        if (a->theta) HIPC(h, hipMemcpyAsync(d_theta.p, a->theta + (c0 - d0) * K, (size_t)(c1 - c0) * K * sizeof(double), hipMemcpyHostToDevice, s));
-        else HIPC(h, mvhdp_launch_doc_topic_prop(mm, carry, d_w.as<double>(), c0, c1, d_theta.as<double>(), s));
+        if (a->theta) HIPC(h, d_theta.upload(a->theta + (c0 - d0) * K, (size_t)(c1 - c0) * K, s));
+        else HIPC(h, mvhdp_launch_doc_topic_prop(mm, carry, d_w, c0, c1, d_theta, s));
 
         for (int64_t r0 = 0; r0 < n_rows_range; r0 += block_rows) {
             const int64_t nr = std::min(block_rows, n_rows_range - r0);
             h_ent.resize((size_t)nr);
             for (int64_t r = 0; r < nr; r++) h_ent[(size_t)r] = c0 + (pw ? (int64_t)h_list[(size_t)(r0 + r)] : r0 + r);
             if (pw)
-                HIPC(h, hipMemcpyAsync(d_list.p, h_list.data() + r0, (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, s));
+                HIPC(h, d_list.upload(h_list.data() + r0, (size_t)nr, s));
             // ---- scores: stripe by stripe of types ----
             ScoreArgs ka{};
-            ka.theta = d_theta.as<double>(); ka.row_list = pw ? d_list.as<int32_t>() : nullptr; ka.row0 = r0;
-            ka.phi = d_phi.as<double>(); ka.S = d_S.as<double>(); ka.ldS = V; ka.n_rows = (int32_t)nr; ka.K = K;
+            ka.theta = d_theta; ka.row_list = pw ? d_list.get() : nullptr; ka.row0 = r0;
+            ka.phi = d_phi; ka.S = d_S; ka.ldS = V; ka.n_rows = (int32_t)nr; ka.K = K;
             for (int64_t v0 = 0; v0 < V; v0 += stripe) {
                 const int64_t nv = std::min(stripe, V - v0);
                 if (!one_stripe) HIPC(h, launch_phi(v0, nv));
                 ka.col0 = v0; ka.n_types = (int32_t)nv; ka.tiles_w = (int32_t)((nv + XV_BW - 1) / XV_BW);
                 const int64_t tiles = ((nr + XV_BE - 1) / XV_BE) * ka.tiles_w;
-                hipLaunchKernelGGL(xview_score_kernel, dim3((unsigned)tiles), dim3(256), 0, s, ka);
-                HIPC(h, hipGetLastError());
+                LAUNCH(h, xview_score_kernel, dim3((unsigned)tiles), dim3(256), 0, s, ka);
             }
             // ---- the pairs of these rows: their scores before anything is marked ----
             int64_t np = 0;
@@ -453,28 +449,24 @@ int xview_run(mvhdp_ctx* h, const mvhdp_predict_args* a, int64_t d0, int64_t d1,
                         h_prow.push_back((int32_t)r); h_pitem.push_back(pw->item[pw->order[(size_t)q]]); q++;
                     }
                 np = q - pcur;
-                HIPC(h, d_prow.alloc((size_t)np * sizeof(int32_t)));
-                HIPC(h, d_pitem.alloc((size_t)np * sizeof(int32_t)));
-                HIPC(h, d_pscore.alloc((size_t)np * sizeof(double)));
-                HIPC(h, d_prank.alloc((size_t)np * sizeof(int32_t)));
-                HIPC(h, hipMemcpyAsync(d_prow.p, h_prow.data(), (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                HIPC(h, hipMemcpyAsync(d_pitem.p, h_pitem.data(), (size_t)np * sizeof(int32_t), hipMemcpyHostToDevice, s));
-                hipLaunchKernelGGL(xview_pair_score_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, d_S.as<double>(), V, np, d_prow.as<int32_t>(),
-                                   d_pitem.as<int32_t>(), d_pscore.as<double>());
-                HIPC(h, hipGetLastError());
+                HIPC(h, d_prow.alloc((size_t)np));
+                HIPC(h, d_pitem.alloc((size_t)np));
+                HIPC(h, d_pscore.alloc((size_t)np));
+                HIPC(h, d_prank.alloc((size_t)np));
+                HIPC(h, d_prow.upload(h_prow.data(), (size_t)np, s));
+                HIPC(h, d_pitem.upload(h_pitem.data(), (size_t)np, s));
+                LAUNCH(h, xview_pair_score_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, s, d_S, V, np, d_prow, d_pitem, d_pscore);
             }
             if (excl) {
-                HIPC(h, hipMemcpyAsync(d_ent.p, h_ent.data(), (size_t)nr * sizeof(int64_t), hipMemcpyHostToDevice, s));
-                hipLaunchKernelGGL(xview_mark_kernel, dim3(wave_blocks(nr, h->num_cus)), dim3(256), 0, s, d_S.as<u64>(), V, nr, d_ent.as<int64_t>(), mm.doc_off[m], mm.tok[m]);
-                HIPC(h, hipGetLastError());
+                HIPC(h, d_ent.upload(h_ent.data(), (size_t)nr, s));
+                LAUNCH(h, xview_mark_kernel, dim3(wave_blocks(nr, h->num_cus)), dim3(256), 0, s, reinterpret_cast<u64*>(d_S.get()), V, nr, d_ent, mm.doc_off[m], mm.tok[m]);
             }
             if (pw) {
-                hipLaunchKernelGGL(xview_rank_kernel, dim3(wave_blocks(np, h->num_cus)), dim3(256), 0, s, d_S.as<u64>(), V, np, d_prow.as<int32_t>(), d_pitem.as<int32_t>(),
-                                   d_pscore.as<u64>(), d_prank.as<int32_t>());
-                HIPC(h, hipGetLastError());
+                LAUNCH(h, xview_rank_kernel, dim3(wave_blocks(np, h->num_cus)), dim3(256), 0, s, reinterpret_cast<u64*>(d_S.get()), V, np, d_prow, d_pitem,
+                       reinterpret_cast<u64*>(d_pscore.get()), d_prank);
                 c_pscore.resize((size_t)np); c_rank.resize((size_t)np);
-                HIPC(h, hipMemcpyAsync(c_pscore.data(), d_pscore.p, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, s));
-                HIPC(h, hipMemcpyAsync(c_rank.data(), d_prank.p, (size_t)np * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                HIPC(h, d_pscore.download(c_pscore.data(), (size_t)np, s));
+                HIPC(h, d_prank.download(c_rank.data(), (size_t)np, s));
                 HIPC(h, hipStreamSynchronize(s));
                 for (int64_t i = 0; i < np; i++) {
                     const size_t at = (size_t)pw->order[(size_t)(pcur + i)];
@@ -484,19 +476,15 @@ int xview_run(mvhdp_ctx* h, const mvhdp_predict_args* a, int64_t d0, int64_t d1,
             } else {
                 const size_t cells = (size_t)nr * n_cap;
                 if ((size_t)V * sizeof(u64) <= select_lds_bytes())
-                    hipLaunchKernelGGL(xview_select_kernel<true>, dim3((unsigned)std::min<int64_t>(nr, (int64_t)h->num_cus * 32)), dim3(64), (size_t)V * sizeof(u64), s,
-                                       d_S.as<u64>(), V, nr, n_cap, d_counts.as<int32_t>(), d_selk.as<u64>(), d_seli.as<int32_t>());
+                    LAUNCH(h, xview_select_kernel<true>, dim3((unsigned)std::min<int64_t>(nr, (int64_t)h->num_cus * 32)), dim3(64), (size_t)V * sizeof(u64), s,
+                           reinterpret_cast<u64*>(d_S.get()), V, nr, n_cap, d_counts, d_selk, d_seli);
                 else
-                    hipLaunchKernelGGL(xview_select_kernel<false>, dim3(wave_blocks(nr, h->num_cus)), dim3(256), 0, s, d_S.as<u64>(), V, nr, n_cap, d_counts.as<int32_t>(),
-                                       d_selk.as<u64>(), d_seli.as<int32_t>());
-                HIPC(h, hipGetLastError());
-                hipLaunchKernelGGL(xview_order_kernel, dim3(wave_blocks(nr, h->num_cus)), dim3(256), 0, s, d_S.as<double>(), V, nr, n_cap, d_counts.as<int32_t>(),
-                                   d_selk.as<u64>(), d_seli.as<int32_t>(), d_items.as<int32_t>(), d_scores.as<double>());
-                HIPC(h, hipGetLastError());
+                    LAUNCH(h, xview_select_kernel<false>, dim3(wave_blocks(nr, h->num_cus)), dim3(256), 0, s, reinterpret_cast<u64*>(d_S.get()), V, nr, n_cap, d_counts, d_selk, d_seli);
+                LAUNCH(h, xview_order_kernel, dim3(wave_blocks(nr, h->num_cus)), dim3(256), 0, s, d_S, V, nr, n_cap, d_counts, d_selk, d_seli, d_items, d_scores);
                 c_items.resize(cells); c_scores.resize(cells); c_counts.resize((size_t)nr);
-                HIPC(h, hipMemcpyAsync(c_items.data(), d_items.p, cells * sizeof(int32_t), hipMemcpyDeviceToHost, s));
-                HIPC(h, hipMemcpyAsync(c_scores.data(), d_scores.p, cells * sizeof(double), hipMemcpyDeviceToHost, s));
-                HIPC(h, hipMemcpyAsync(c_counts.data(), d_counts.p, (size_t)nr * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+                HIPC(h, d_items.download(c_items.data(), cells, s));
+                HIPC(h, d_scores.download(c_scores.data(), cells, s));
+                HIPC(h, d_counts.download(c_counts.data(), (size_t)nr, s));
                 HIPC(h, hipStreamSynchronize(s));
                 for (int64_t r = 0; r < nr; r++) {              // the slots beyond n_cap keep item -1 and score 0.0
                     const size_t to = (size_t)(c0 - d0 + r0 + r) * (size_t)pr->n, from = (size_t)r * n_cap;
