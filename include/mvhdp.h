@@ -475,6 +475,72 @@ int mvhdp_score_items(mvhdp_handle h, const mvhdp_predict_args* a, int64_t d0, i
                       const int64_t* entity /*[n_pairs], in [d0,d1), any order, repeats allowed*/, const int32_t* item /*[n_pairs], in [0,V_m)*/,
                       double* score /*[n_pairs]*/, int32_t* rank /*[n_pairs]*/);
 
+/* Nearest entities: for each of nq query rows the n entities of [c0, c1) of this handle with the largest cosine similarity.  The reference
+ * only compares groups (its Java double loop, FLOW:1320-1532, cannot do more): THIS definition is ours; tests/nearest_numpy.py restates it.
+ * It is pinned to the arithmetic of mvhdp_similar_pairs, so every value can be checked against that entry point bit for bit.
+ * Candidate rows: theta of the entities [c0, c1), the bits of mvhdp_doc_topic_proportions(h, view_weights, ..), its missing-view carry-over
+ *   included.  They are computed on the device and stay there: nothing of size [entities][K] crosses to the host.
+ * Query rows: args.queries, a host array [nq][K] (for example the proportions of folded-in documents from an inference handle); or, with
+ *   queries == NULL, the entities [q0, q1) of this same handle (nq = q1 - q0; args.nq is ignored).  In that form exclude_self != 0 removes
+ *   an entity from its own list; with host rows exclude_self is ignored.
+ * min_weight as in mvhdp_similar_pairs: an entry <= min_weight of a query or candidate row counts as 0; -inf: none.  NaN: MVHDP_ERR_INVALID_ARG.
+ * sim(q, c): the bits of MVHDP_SIM_COS in mvhdp_similar_pairs -- dot = the unfused fp64 chain s = s + q_k * c_k over ascending k from +0.0,
+ *   |row| = sqrt of the same chain of squares, sim = dot / (|q| * |c|).
+ * Order per query: sim descending, equal sims by ascending entity id.  (The comparison is that of the 64-bit pattern made monotone, as for
+ *   mvhdp_predict_items; the chain never yields -0.0 from rows without negative zeros.)
+ * Never listed: a candidate whose norm is 0, Inf or NaN; a pair whose sim is NaN (only where fp64 over- or underflows).  A query whose norm
+ *   is 0, Inf or NaN gets counts[q] = 0.
+ * counts[q] = min(n, candidates that may be listed); ids[q][0 .. counts[q]) are entity ids of this handle, sims[q][.] their values; the
+ *   unused tail holds id -1 and sim 0.0.  n >= 1; n > c1 - c0 is allowed.  n is meant to be small: per query the list is placed by counting,
+ *   for each listed entity, the listed ones in front of it (n^2 / 64), and the device keeps 32 n bytes per query of a block.
+ * Two stages, as in mvhdp_similar_pairs; the screen never decides.
+ * (a) Screen, on the matrix cores: rows normalised in fp64, stored as fp32, a block of queries against a stripe of candidates in
+ *   rectangular 128 x 128 tiles with v_mfma_f32_32x32x2_f32 (one fp32 fma chain over every k).  Per query row let tau be the n-th largest
+ *   screen value over its screened candidates that may be listed (the query itself left out when exclude_self applies).  Candidates of the
+ *   exact stage are the cells with screen >= tau - margin, margin = (K + 4) * 2^-23, the margin of mvhdp_similar_pairs: it is twice the
+ *   bound b on |screen - exact|; n cells have screen >= tau, so their exact values are >= tau - b and so is the n-th largest exact value;
+ *   every member of the true first n, ties at the n-th place included, therefore has screen >= tau - 2 b.  Fewer than n screened cells:
+ *   all of them.  With more than one stripe, a stripe is cut with the n-th largest screen value over the stripes SO FAR, this one included:
+ *   a value <= tau, hence a superset of the cells above (and the same set when one stripe holds every candidate).
+ *   A row with a non-zero |entry| outside [2^-500, 2^500] is not screened: such a candidate is a candidate of every query, such a query
+ *   takes every candidate.  stats.exact_only_rows counts those rows, query rows and candidate rows each.
+ * (b) Exact: every candidate recomputed by the fp64 chain; a wave per query selects the first n by (sim descending, id ascending).
+ * Work proceeds in blocks of block_queries queries (0: 8192; at most 2^26 / stripe) times stripes of stripe_candidates candidates
+ * (0 or more than 8192: 8192), each block with a candidate buffer of candidate_capacity entries (0: 2^22); a block that overflows it is
+ * redone with a buffer of the size it asked for (stats.regrown counts those).  The knobs change no result.  Device memory: 12 K bytes per
+ * query and per candidate row (the fp64 rows and their fp32 image, for the whole call), a block of screen values of at most 256 MiB, and
+ * 24 bytes per candidate of a block.
+ * stats (or NULL): cells_screened = matrix cells of the first stage (128 x 128 per launched tile); candidates = entries of the exact
+ * stage over all blocks; exact_only_rows; blocks; regrown; margin.
+ * Preconditions as mvhdp_doc_topic_proportions: every view's corpus and the hyper-parameters (else MVHDP_ERR_STATE).
+ * MVHDP_ERR_INVALID_ARG, every output untouched: a NULL args, view_weights, ids, sims or counts; n < 1; a candidate range outside
+ * [0, D] or c0 > c1; with queries == NULL a query range outside [0, D] or q0 > q1; with host rows nq < 0; a NaN min_weight; a negative
+ * block_queries, stripe_candidates or candidate_capacity.  MVHDP_ERR_UNSUPPORTED: K > 65536; 2^31 - 128 query or candidate rows or more.
+ * nq == 0: MVHDP_OK, only stats written.  c0 == c1: every count 0.  No model state changes; two calls give the same bits. */
+typedef struct { const double* view_weights /*[M]*/; int64_t c0, c1; const double* queries /*[nq][K] host, or NULL: entities [q0, q1)*/;
+                 int64_t nq, q0, q1; int32_t exclude_self, n; double min_weight;
+                 int32_t block_queries /*0: auto*/, stripe_candidates /*0: auto*/; int64_t candidate_capacity /*0: auto*/; } mvhdp_nearest_args;
+typedef struct { int64_t cells_screened, candidates, exact_only_rows; int32_t blocks, regrown; double margin; } mvhdp_nearest_stats;
+int mvhdp_nearest_entities(mvhdp_handle h, const mvhdp_nearest_args* a, int64_t* ids /*[nq][n]*/, double* sims /*[nq][n]*/,
+                           int32_t* counts /*[nq]*/, mvhdp_nearest_stats* stats /* or NULL */);
+/* Pure host function, no device: margin, blocks and cells_screened of a call with nq query rows, nc candidates and K topics (the other
+ * fields 0).  MVHDP_ERR_INVALID_ARG for nq < 0, nc < 0, K < 1, a negative block_queries or stripe_candidates, or a NULL out;
+ * MVHDP_ERR_UNSUPPORTED for K > 65536. */
+int mvhdp_nearest_probe(int64_t nq, int64_t nc, int32_t K, int32_t block_queries, int32_t stripe_candidates, mvhdp_nearest_stats* out);
+/* Top entities per topic: for every topic k the n entities d of [d0, d1) with the largest theta_d[k], theta the bits of
+ * mvhdp_doc_topic_proportions(h, view_weights, ..).  Ours as well (tests/nearest_numpy.py).  Order: weight descending, equal weights by
+ * ascending entity id.  Only weights > threshold are kept, strictly; -inf keeps every entity; NaN: MVHDP_ERR_INVALID_ARG.  1 <= n <= 1024.
+ * counts[k] = min(n, entities kept); ids[k][0 .. counts[k]) and weights[k][.]; the unused tail holds id -1 and weight 0.0.  Inactive
+ * topics are listed like any other (their proportions are what mvhdp_doc_topic_proportions gives).
+ * On the device theta is produced in chunks of chunk_entities entities (0: as many as fit 256 MiB, also the most); a thread per topic and
+ * slice of slice_entities entities (0: 2048), lanes over topics so that the row-major reads coalesce, keeps the first n of its slice; one
+ * wave per topic merges the slices.  The knobs change no result.  No floating-point atomics: two calls give the same bits.
+ * MVHDP_ERR_INVALID_ARG, every output untouched: a NULL buffer, a bad range, n outside 1..1024, a NaN threshold, a negative chunk_entities
+ * or slice_entities.  MVHDP_ERR_UNSUPPORTED: 2^31 entities or more.  Preconditions as mvhdp_doc_topic_proportions.  d0 == d1: every count 0. */
+int mvhdp_topic_top_entities(mvhdp_handle h, const double* view_weights /*[M]*/, int64_t d0, int64_t d1, int32_t n, double threshold,
+                             int64_t chunk_entities /*0: auto*/, int64_t slice_entities /*0: auto*/,
+                             int64_t* ids /*[K][n]*/, double* weights /*[K][n]*/, int32_t* counts /*[K]*/);
+
 /* ---- topic diagnostics: the step after training (FastQMVWVTopicModelDiagnostics, DIAG = MVTopicModel/FastQMVWVTopicModelDiagnostics.java;
  * SciTopicFlow builds it with N = 20 right after the save, whose saveExperiment / saveTopicsandExperiment call
  * calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230 from PTM:1370 / PTM:1507 and getSortedWords PTM:1792-1811 per view).

@@ -17,6 +17,7 @@ ABI_SYMBOLS = [
     "mvhdp_get_count_histogram", "mvhdp_view_overlap_sums", "mvhdp_model_log_likelihood", "mvhdp_doc_topic_proportions",
     "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
     "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_predict_items", "mvhdp_score_items",
+    "mvhdp_nearest_entities", "mvhdp_nearest_probe", "mvhdp_topic_top_entities",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
@@ -169,6 +170,17 @@ class PredictArgsC(C.Structure):
     _fields_ = [("m", C.c_int32), ("exclude_present", C.c_int32), ("view_weights", C.c_void_p), ("theta", C.c_void_p)]
 
 
+class NearestArgsC(C.Structure):
+    _fields_ = [("view_weights", C.c_void_p), ("c0", C.c_int64), ("c1", C.c_int64), ("queries", C.c_void_p), ("nq", C.c_int64),
+                ("q0", C.c_int64), ("q1", C.c_int64), ("exclude_self", C.c_int32), ("n", C.c_int32), ("min_weight", C.c_double),
+                ("block_queries", C.c_int32), ("stripe_candidates", C.c_int32), ("candidate_capacity", C.c_int64)]
+
+
+class NearestStatsC(C.Structure):
+    _fields_ = [("cells_screened", C.c_int64), ("candidates", C.c_int64), ("exact_only_rows", C.c_int64), ("blocks", C.c_int32),
+                ("regrown", C.c_int32), ("margin", C.c_double)]
+
+
 _lib = None
 _preloaded = []            # keeps the handles of the runtime libraries loaded on the library's behalf alive
 
@@ -285,6 +297,9 @@ def load_library():
     L.mvhdp_heldout_left_to_right.argtypes = [vp, C.POINTER(HeldoutArgsC), i64, vp, vp, vp, vp, vp, C.POINTER(HeldoutStatsC)]
     L.mvhdp_predict_items.argtypes = [vp, C.POINTER(PredictArgsC), i64, i64, i32, vp, vp, vp]
     L.mvhdp_score_items.argtypes = [vp, C.POINTER(PredictArgsC), i64, i64, i64, vp, vp, vp, vp]
+    L.mvhdp_nearest_entities.argtypes = [vp, C.POINTER(NearestArgsC), vp, vp, vp, C.POINTER(NearestStatsC)]
+    L.mvhdp_nearest_probe.argtypes = [i64, i64, i32, i32, i32, C.POINTER(NearestStatsC)]
+    L.mvhdp_topic_top_entities.argtypes = [vp, vp, i64, i64, i32, C.c_double, i64, i64, vp, vp, vp]
     L.mvhdp_gamma_doc_statistics.argtypes = [vp, i32, C.c_double, u64, u32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
     L.mvhdp_dp_table_statistics.argtypes = [vp, i32, vp, i32, vp, u64, u32, vp, vp]
     L.mvhdp_antoniak_draws.argtypes = [vp, i32, vp, vp, u64, u32, vp]

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   EmbConfigC, EmbStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
+                   EmbConfigC, EmbStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
@@ -134,6 +134,90 @@ def sim_probe(n, dim, stripe_rows=0):
     if rc != 0:
         raise MvhdpError(rc, "sim_probe: bad shape" if rc == -1 else "sim_probe: dim > 65536")
     return _sim_stats(st)
+
+
+@dataclass
+class NearestStats:
+    """mvhdp_nearest_stats: what a nearest_entities call did.  cells_screened: matrix cells of the first stage (128 x 128 per launched
+    tile); candidates: pairs the exact stage recomputed; exact_only_rows: query and candidate rows that were not screened."""
+    cells_screened: int = 0
+    candidates: int = 0
+    exact_only_rows: int = 0
+    blocks: int = 0
+    regrown: int = 0
+    margin: float = 0.0
+
+
+@dataclass
+class NearestResult:
+    """mvhdp_nearest_entities: per query row its first counts[q] entities by (sim descending, entity id ascending): ids [nq][n] (-1
+    unfilled), sims [nq][n] (0.0 unfilled), counts [nq]."""
+    ids: np.ndarray
+    sims: np.ndarray
+    counts: np.ndarray
+    stats: NearestStats = None
+
+
+def _nearest_stats(c):
+    return NearestStats(**{f: getattr(c, f) for f, _ in NearestStatsC._fields_})
+
+
+def nearest_probe(nq, nc, K, block_queries=0, stripe_candidates=0):
+    """mvhdp_nearest_probe: margin, blocks and cells_screened of a nearest_entities call of that shape.  No device."""
+    st = NearestStatsC()
+    rc = load_library().mvhdp_nearest_probe(int(nq), int(nc), int(K), int(block_queries), int(stripe_candidates), C.byref(st))
+    if rc != 0:
+        raise MvhdpError(rc, "nearest_probe: bad shape" if rc == -1 else "nearest_probe: K > 65536")
+    return _nearest_stats(st)
+
+
+def _first_n(values, ids, n):
+    """positions of the first n of (value descending, id ascending); NaN values left out"""
+    keep = np.flatnonzero(~np.isnan(values))
+    order = keep[np.lexsort((ids[keep], -values[keep]))]
+    return order[:n]
+
+
+def merge_nearest(results, n):
+    """The NearestResult over the union of the candidate ranges from the results of its parts (document shards, or pieces of one
+    range), ids already in one numbering: per query the first n of all listed entries by the same order.  A value belongs to its pair
+    alone, so the merge is exact provided every part was asked for at least n.  No device."""
+    results = list(results)
+    n = int(n)
+    nq = len(results[0].counts)
+    if any(len(r.counts) != nq for r in results):
+        raise ValueError("merge_nearest: the results disagree on the number of queries")
+    ids = np.full((nq, n), -1, dtype=np.int64)
+    sims = np.zeros((nq, n), dtype=np.float64)
+    counts = np.zeros(nq, dtype=np.int32)
+    for q in range(nq):
+        i = np.concatenate([r.ids[q, :r.counts[q]] for r in results])
+        v = np.concatenate([r.sims[q, :r.counts[q]] for r in results])
+        o = _first_n(v, i, n)
+        counts[q] = len(o)
+        ids[q, :len(o)], sims[q, :len(o)] = i[o], v[o]
+    st = [r.stats for r in results if r.stats is not None]
+    stats = NearestStats(sum(x.cells_screened for x in st), sum(x.candidates for x in st), sum(x.exact_only_rows for x in st),
+                         sum(x.blocks for x in st), sum(x.regrown for x in st), max(x.margin for x in st)) if st else None
+    return NearestResult(ids, sims, counts, stats)
+
+
+def merge_topic_top_entities(parts, n):
+    """(ids [K][n], weights [K][n], counts [K]) over the union of the entity ranges from the same triples of its parts, ids in one
+    numbering: per topic the first n by (weight descending, id ascending).  Exact, as merge_nearest is.  No device."""
+    parts = list(parts)
+    n = int(n)
+    K = len(parts[0][2])
+    ids = np.full((K, n), -1, dtype=np.int64)
+    weights = np.zeros((K, n), dtype=np.float64)
+    counts = np.zeros(K, dtype=np.int32)
+    for k in range(K):
+        i = np.concatenate([p[0][k, :p[2][k]] for p in parts])
+        v = np.concatenate([p[1][k, :p[2][k]] for p in parts])
+        o = _first_n(v, i, n)
+        counts[k] = len(o)
+        ids[k, :len(o)], weights[k, :len(o)] = i[o], v[o]
+    return ids, weights, counts
 
 
 @dataclass
@@ -675,6 +759,51 @@ class NativeSampler:
         self._ck(self.L.mvhdp_score_items(self.h, C.byref(a), d0, d1, len(ent), _ptr(ent), _ptr(it), _ptr(score), _ptr(rank)))
         return ItemScores(score, rank)
 
+    # -- retrieval (include/mvhdp.h mvhdp_nearest_entities / mvhdp_topic_top_entities) --
+    def nearest_entities(self, view_weights, n, queries=None, q0=0, q1=None, c0=0, c1=None, exclude_self=True, min_weight=-np.inf,
+                         block_queries=0, stripe_candidates=0, candidate_capacity=0):
+        """Per query row the n entities of [c0, c1) with the largest cosine similarity of their topic proportions
+        (doc_topic_proportions(view_weights), formed on the device), sim descending, equal sims by entity id: a NearestResult.  Queries:
+        the rows of `queries` [nq][K] -- the proportions of folded-in documents, say -- or, without them, the entities [q0, q1) of this
+        handle, each left out of its own list unless exclude_self is False.  An entry <= min_weight counts as 0.  Every sim has the bits
+        of similar_pairs(.., "cos", ..) for the same pair.  block_queries, stripe_candidates, candidate_capacity: work sizes (0: auto)."""
+        w = np.ascontiguousarray(view_weights, dtype=np.float64)
+        if w.shape != (self.M,):
+            raise ValueError("view_weights must be [M]")
+        n = int(n)
+        c1 = self.D if c1 is None else int(c1)
+        q1 = self.D if q1 is None else int(q1)
+        a = NearestArgsC(w.ctypes.data, int(c0), c1, None, 0, int(q0), q1, 1 if exclude_self else 0, n, float(min_weight),
+                         int(block_queries), int(stripe_candidates), int(candidate_capacity))
+        x = None
+        if queries is not None:
+            x = np.ascontiguousarray(queries, dtype=np.float64)
+            if x.ndim != 2 or x.shape[1] != self.K:
+                raise ValueError("queries must be [nq][K]")
+            a.queries, a.nq = x.ctypes.data, x.shape[0]
+        nq = x.shape[0] if x is not None else max(q1 - int(q0), 0)
+        ids = np.full((nq, max(n, 0)), -1, dtype=np.int64)
+        sims = np.zeros((nq, max(n, 0)), dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.int32)
+        st = NearestStatsC()
+        self._ck(self.L.mvhdp_nearest_entities(self.h, C.byref(a), _ptr(ids), _ptr(sims), _ptr(counts), C.byref(st)))
+        return NearestResult(ids, sims, counts, _nearest_stats(st))
+
+    def topic_top_entities(self, view_weights, n, threshold=-np.inf, d0=0, d1=None, chunk_entities=0, slice_entities=0):
+        """Per topic the n (<= 1024) entities of [d0, d1) with the largest proportion > threshold, weight descending, equal weights by
+        entity id: (ids [K][n] (-1 unfilled), weights [K][n], counts [K]).  chunk_entities, slice_entities: work sizes (0: auto)."""
+        w = np.ascontiguousarray(view_weights, dtype=np.float64)
+        if w.shape != (self.M,):
+            raise ValueError("view_weights must be [M]")
+        n = int(n)
+        d1 = self.D if d1 is None else int(d1)
+        ids = np.full((self.K, max(n, 0)), -1, dtype=np.int64)
+        weights = np.zeros((self.K, max(n, 0)), dtype=np.float64)
+        counts = np.zeros(self.K, dtype=np.int32)
+        self._ck(self.L.mvhdp_topic_top_entities(self.h, _ptr(w), int(d0), d1, n, float(threshold), int(chunk_entities), int(slice_entities),
+                                                 _ptr(ids), _ptr(weights), _ptr(counts)))
+        return ids, weights, counts
+
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
     def top_words(self, m, n):
         """getSortedWords(m) PTM:1792-1811 cut at n: (types [K][n] (-1 unfilled), counts [K][n], nonzero [K])."""
@@ -1136,6 +1265,29 @@ class NativeGroup:
             r = s.score_items(m, view_weights, ent[at] - b, it[at], lo, hi, exclude_present, None if th is None else th[b + lo - d0:b + hi - d0])
             score[at], rank[at] = r.score, r.rank
         return ItemScores(score, rank)
+
+    def nearest_entities(self, view_weights, n, queries, min_weight=-np.inf, **knobs):
+        """NativeSampler.nearest_entities for host-row queries over the LOCAL members: every member answers for its own entities, its
+        ids are moved to the group's numbering (entity ids count through the members in their order) and the lists are merged
+        (merge_nearest): per pair the values are a single handle's, bit for bit.  (As with doc_topic_proportions on a shard, the
+        carry-over of a missing view does not reach across a member's first entity.)"""
+        bases = np.concatenate([[0], np.cumsum([s.D for s in self.members])]).astype(np.int64)
+        parts = []
+        for s, b in zip(self.members, bases[:-1]):
+            r = s.nearest_entities(view_weights, n, queries=queries, min_weight=min_weight, **knobs)
+            r.ids[r.ids >= 0] += int(b)
+            parts.append(r)
+        return merge_nearest(parts, n)
+
+    def topic_top_entities(self, view_weights, n, threshold=-np.inf, **knobs):
+        """NativeSampler.topic_top_entities over the LOCAL members' entities, merged the same way (merge_topic_top_entities)."""
+        bases = np.concatenate([[0], np.cumsum([s.D for s in self.members])]).astype(np.int64)
+        parts = []
+        for s, b in zip(self.members, bases[:-1]):
+            ids, weights, counts = s.topic_top_entities(view_weights, n, threshold, **knobs)
+            ids[ids >= 0] += int(b)
+            parts.append((ids, weights, counts))
+        return merge_topic_top_entities(parts, n)
 
     def sweep(self, sweep_idx, seed, flags=0):
         """One sweep of the whole model; the list of the local members' statistics."""
