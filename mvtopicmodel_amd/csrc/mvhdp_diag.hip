@@ -8,7 +8,7 @@
 // Integer outputs are exact.  No floating-point atomics anywhere: every fp64 sum is a per-thread / per-wave sum over a static share
 // of the work followed by a reduction in a fixed order, so the same model gives the same bits on every call.
 #include "mvhdp_ctx.h"
-#include "mvhdp_wave.h"
+#include "mvhdp_select.h"
 
 namespace {
 
@@ -17,8 +17,6 @@ __constant__ double c_doc_proportions[DIAG_NPROP] = {0.01, 0.02, 0.05, 0.1, 0.2,
 constexpr int ROWS_BLOCKS = 512;                   // fixed: the summation order of skewSum is part of the result
 constexpr int DOC_WAVES = 4096;                    // waves of the document pass (c log c partials: one [K] row each)
 constexpr int NCOL = 7;                            // diag_columns_kernel outputs per topic
-
-__device__ __forceinline__ unsigned long long ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 // ---------------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void diag_transpose_kernel(const int32_t* __restrict__ nwk, int V, int K, int32_t* __restrict__ nkw)

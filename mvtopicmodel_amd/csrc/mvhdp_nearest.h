@@ -13,9 +13,7 @@
 #include <stdint.h>
 #include "mvhdp_sim.h"
 
-enum { NEAR_TILE = 128,                      // the screen's block tile: 128 queries x 128 candidates, 4 waves of 2 x 2 MFMA tiles of 32 x 32
-       NEAR_BK = 32,                         // k-slab staged in LDS per step
-       NEAR_MAX_STRIPE = 8192,               // candidates per stripe: a stripe's 32-bit keys of one query sit in LDS (32 KiB) while tau is found
+enum { NEAR_MAX_STRIPE = 8192,              // candidates per stripe: a stripe's 32-bit keys of one query sit in LDS (32 KiB) while tau is found
        NEAR_AUTO_BLOCK = 8192,               // queries per block
        NEAR_MAX_TOPN = 1024,                 // mvhdp_topic_top_entities: n at most
        NEAR_AUTO_SLICE = 2048 };             // mvhdp_topic_top_entities: entities one thread walks per topic
@@ -37,7 +35,7 @@ static inline int64_t near_blocks(int64_t nq, int64_t nc, int32_t block_queries,
     const int64_t B = near_block(block_queries, stripe_candidates);
     return nq < 1 || nc < 1 ? 0 : (nq + B - 1) / B;
 }
-static inline int64_t near_tiles(int64_t rows) { return (rows + NEAR_TILE - 1) / NEAR_TILE; }
+static inline int64_t near_tiles(int64_t rows) { return (rows + SCREEN_TILE - 1) / SCREEN_TILE; }
 // matrix cells the screen computes: 128 x 128 per launched tile, every block of queries against every stripe of candidates
 static inline int64_t near_cells(int64_t nq, int64_t nc, int32_t block_queries, int32_t stripe_candidates)
 {
@@ -46,7 +44,7 @@ static inline int64_t near_cells(int64_t nq, int64_t nc, int32_t block_queries, 
     if (nq < 1 || nc < 1) return 0;
     for (int64_t q0 = 0; q0 < nq; q0 += B) {
         const int64_t tq = near_tiles((q0 + B < nq ? q0 + B : nq) - q0);
-        for (int64_t s0 = 0; s0 < nc; s0 += S) cells += tq * near_tiles((s0 + S < nc ? s0 + S : nc) - s0) * NEAR_TILE * NEAR_TILE;
+        for (int64_t s0 = 0; s0 < nc; s0 += S) cells += tq * near_tiles((s0 + S < nc ? s0 + S : nc) - s0) * SCREEN_TILE * SCREEN_TILE;
     }
     return cells;
 }

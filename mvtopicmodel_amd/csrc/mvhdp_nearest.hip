@@ -3,8 +3,7 @@
 //   mvhdp_nearest_entities     per query row the n candidate entities of largest cosine, by the fp64 chain of mvhdp_similar_pairs
 //   mvhdp_topic_top_entities   per topic the n entities of largest proportion
 // The proportions are produced on the device (mvhdp_launch_doc_topic_prop) and stay there.
-//   near_prepare_kernel        per row: entries <= min_weight zeroed, |row| = sqrt of the fp64 chain of squares, the row's class
-//   near_normalise_kernel      row / |row| in fp64, stored as fp32 into a zero-padded image
+// Both sets of rows are prepared as mvhdp_similar_pairs prepares its own (mvhdp_screen_prepare_rows: cleaned, norms, classes, fp32 image).
 //   near_screen_kernel         the screen: 128 queries x 128 candidates per block on v_mfma_f32_32x32x2_f32; every cell is written to the
 //                              block of scores [queries of the block][candidates of the stripe] as an order-preserving 32-bit key, 0 for a
 //                              cell that is not screened (a row that is not tame, padding, the query itself)
@@ -19,72 +18,18 @@
 //   topk_partial_kernel        a thread per (slice of entities, topic), lanes over topics: the n largest proportions of the slice
 //   topk_merge_kernel          one wave per topic: the first n of all slices, by the same descent
 // No floating-point atomics: every fp64 value is a chain in a fixed order, integers and exact fp64 values decide every comparison.
-#include "mvhdp_ctx.h"
+#include "mvhdp_screen.h"
+#include "mvhdp_select.h"
 #include "mvhdp_nearest.h"
 
 namespace {
 
 constexpr int WV = 64;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
-
-enum : uint8_t { ROW_OUT = 0,                // norm 0, Inf or NaN: never listed, lists nothing
-                 ROW_TAME = 1,               // screened
-                 ROW_WILD = 2 };             // a non-zero |entry| outside [2^-500, 2^500]: fp64 may under- or overflow, never screened
-
-// order-preserving keys: a < b as numbers (no NaN) iff key(a) < key(b); -0.0 < +0.0 here.  A key is never 0 for a number.
-__device__ __forceinline__ uint32_t f32_key(float v) { const uint32_t b = __float_as_uint(v); return (b >> 31) ? ~b : b | 0x80000000u; }
-__device__ __forceinline__ float f32_unkey(uint32_t k) { return __uint_as_float((k >> 31) ? k ^ 0x80000000u : ~k); }
-__device__ __forceinline__ u64 f64_key(double v) { const u64 b = (u64)__double_as_longlong(v); return (b >> 63) ? ~b : b | (1ull << 63); }
-__device__ __forceinline__ double f64_unkey(u64 k) { return __longlong_as_double((long long)((k >> 63) ? k ^ (1ull << 63) : ~k)); }
-
-__device__ __forceinline__ u64 ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-// the sum over the wave, as a scalar (every lane holds it after the butterfly): an atomic that adds it needs no scan over the lanes
-__device__ __forceinline__ int wave_sum(int c) { for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64); return __builtin_amdgcn_readfirstlane(c); }
 
 // ---------------------------------------------------------------------------------------------------------------
-// One thread per row.  x is cleaned in place.
-__global__ __launch_bounds__(256) void near_prepare_kernel(double* __restrict__ x, int n, int dim, double min_weight, double* __restrict__ norm, uint8_t* __restrict__ cls)
-{
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    double* row = x + (int64_t)r * dim;
-    const double lo = 0x1p-500, hi = 0x1p500;
-    double s = 0.0;
-    bool wild = false;
-    for (int k = 0; k < dim; k++) {
-        double v = row[k];
-        if (v <= min_weight) { v = 0.0; row[k] = 0.0; }
-        s = s + v * v;                                         // the chain of squares of mvhdp_similar_pairs: dmul, dadd, ascending
-        const double a = fabs(v);
-        wild = wild || (v != 0.0 && !(a >= lo && a <= hi));
-    }
-    const double nr = sqrt(s);
-    norm[r] = nr;
-    cls[r] = !(nr > 0.0 && nr < INFINITY) ? ROW_OUT : wild ? ROW_WILD : ROW_TAME;
-}
-
-// xn: [n + NEAR_TILE][ld] fp32, zero beyond (n, dim) and for rows that are not ROW_TAME
-__global__ __launch_bounds__(256) void near_normalise_kernel(const double* __restrict__ x, const double* __restrict__ norm, const uint8_t* __restrict__ cls,
-                                                             int n, int dim, int64_t ld, float* __restrict__ xn)
-{
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (int64_t)n * dim) return;
-    const int r = (int)(i / dim), k = (int)(i - (int64_t)r * dim);
-    xn[(int64_t)r * ld + k] = cls[r] == ROW_TAME ? (float)(x[i] / norm[r]) : 0.0f;
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// The screen.  Block (b, a) computes the 128 x 128 cells of queries qb0 + 128 a .. against candidates s0 + 128 b ..  Per k-slab of 32
-// the two row panels go through LDS; wave w owns the 64 x 64 quadrant (w >> 1, w & 1) as 2 x 2 MFMA tiles.  v_mfma_f32_32x32x2_f32 takes
-// A[i = lane & 31][k = lane >> 5] and B[k = lane >> 5][j = lane & 31]; the lane's half h = lane >> 5 reads the 16 consecutive k of its
-// half of the slab (4 x ds_read_b128 per panel row), so step s multiplies k = s (h = 0) and k = 16 + s (h = 1): a permutation of the
-// slab's k order, the same for both operands -- still one fp32 fma chain over every k once, which is all the margin asks for.
-// C/D: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
-// Both images are padded with NEAR_TILE zero rows and zero columns to a multiple of 32: no bounds checks on the loads.  The stores are
-// checked: cell (i, j) is written only for i < q1 and j < s1.
-constexpr int LDS_LD = NEAR_BK + 4;                            // 36 floats: 16-byte aligned rows, b128 reads of a wave spread over the banks
-
+// The screen.  Block (b, a) computes the 128 x 128 cells of queries qb0 + 128 a .. against candidates s0 + 128 b .. with screen_tile
+// (mvhdp_screen.h has the layout); both images are padded with SCREEN_TILE zero rows.  The stores are checked: cell (i, j) is written
+// only for i < q1 and j < s1.
 struct ScreenArgs {
     const float* xq; const float* xc;        // the two images, both [.][ld]
     int64_t ld; int kslabs;
@@ -97,59 +42,14 @@ struct ScreenArgs {
 __global__ __launch_bounds__(256) void near_screen_kernel(const ScreenArgs p)
 {
     const int ta = blockIdx.y, tb = blockIdx.x;
-    __shared__ __attribute__((aligned(16))) float As[NEAR_TILE * LDS_LD];
-    __shared__ __attribute__((aligned(16))) float Bs[NEAR_TILE * LDS_LD];
+    __shared__ __attribute__((aligned(16))) float As[SCREEN_TILE * SCREEN_LDS_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[SCREEN_TILE * SCREEN_LDS_LD];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int wr = (w >> 1) * 64, wc = (w & 1) * 64;
-    const int64_t ld = p.ld, arow0 = p.qb0 + (int64_t)ta * NEAR_TILE, brow0 = p.s0 + (int64_t)tb * NEAR_TILE;
-
+    const int wr = (w >> 1) * 64, wc = (w & 1) * 64, lr = lane & 31, lh = lane >> 5;
+    const int64_t arow0 = p.qb0 + (int64_t)ta * SCREEN_TILE, brow0 = p.s0 + (int64_t)tb * SCREEN_TILE;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int e = 0; e < 16; e++) acc[a][b][e] = 0.0f;
+    screen_tile(p.xq, p.xc, p.ld, p.kslabs, arow0, brow0, As, Bs, acc);
 
-    // staging: 128 rows x 8 float4 per panel, 4 per thread (named registers: an array here ends up in scratch)
-    float4 ga0, ga1, ga2, ga3, gb0, gb1, gb2, gb3;
-    const int srow = t >> 3, sc4 = (t & 7) * 4;                // this thread's cells of a panel: rows srow + 32 q, floats sc4 .. sc4 + 3
-    const float* gpa = p.xq + (arow0 + srow) * ld + sc4;
-    const float* gpb = p.xc + (brow0 + srow) * ld + sc4;
-#define NEAR_GLOAD(slab) { const int64_t ko = (int64_t)(slab) * NEAR_BK; \
-        ga0 = *(const float4*)(gpa + ko); ga1 = *(const float4*)(gpa + 32 * ld + ko); ga2 = *(const float4*)(gpa + 64 * ld + ko); ga3 = *(const float4*)(gpa + 96 * ld + ko); \
-        gb0 = *(const float4*)(gpb + ko); gb1 = *(const float4*)(gpb + 32 * ld + ko); gb2 = *(const float4*)(gpb + 64 * ld + ko); gb3 = *(const float4*)(gpb + 96 * ld + ko); }
-    NEAR_GLOAD(0)
-    const int lr = lane & 31, lh = lane >> 5;
-    for (int slab = 0; slab < p.kslabs; slab++) {
-        __syncthreads();                                       // the previous slab's reads are done
-        {
-            float* sa = As + srow * LDS_LD + sc4;
-            float* sb = Bs + srow * LDS_LD + sc4;
-            *(float4*)sa = ga0; *(float4*)(sa + 32 * LDS_LD) = ga1; *(float4*)(sa + 64 * LDS_LD) = ga2; *(float4*)(sa + 96 * LDS_LD) = ga3;
-            *(float4*)sb = gb0; *(float4*)(sb + 32 * LDS_LD) = gb1; *(float4*)(sb + 64 * LDS_LD) = gb2; *(float4*)(sb + 96 * LDS_LD) = gb3;
-        }
-        __syncthreads();
-        if (slab + 1 < p.kslabs) { NEAR_GLOAD(slab + 1) }      // in flight under the MFMAs
-        float av[2][16], bv[2][16];
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float4 va = *(const float4*)(As + (wr + a * 32 + lr) * LDS_LD + lh * 16 + q * 4);
-                const float4 vb = *(const float4*)(Bs + (wc + a * 32 + lr) * LDS_LD + lh * 16 + q * 4);
-                av[a][q * 4 + 0] = va.x; av[a][q * 4 + 1] = va.y; av[a][q * 4 + 2] = va.z; av[a][q * 4 + 3] = va.w;
-                bv[a][q * 4 + 0] = vb.x; bv[a][q * 4 + 1] = vb.y; bv[a][q * 4 + 2] = vb.z; bv[a][q * 4 + 3] = vb.w;
-            }
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][s], bv[0][s], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][s], bv[1][s], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][s], bv[0][s], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][s], bv[1][s], acc[1][1], 0, 0, 0);
-        }
-    }
-#undef NEAR_GLOAD
     // epilogue: the 32 lanes of a half write 32 consecutive keys of one query row (128 bytes)
     const int64_t jb = brow0 + wc + lr;                        // + 32 b
     const int64_t ib = arow0 + wr + 4 * lh;                    // + 32 a + (e & 3) + 8 (e >> 2)
@@ -196,7 +96,7 @@ __global__ __launch_bounds__(64) void near_select_kernel(const SelectArgs p)
     extern __shared__ uint32_t s_keys[];                       // [ns]
     __shared__ uint32_t s_short[NEAR_SHORT];
     const int lane = threadIdx.x;
-    const u64 below = (1ull << lane) - 1ull;
+    const u64 below = lanes_below(lane);
     for (int r = blockIdx.x; r < p.nrows; r += gridDim.x) {
         const uint8_t cq = p.clsq[p.qb0 + r];
         __syncthreads();                                       // (one wave: the reads of the row before are done)
@@ -227,10 +127,7 @@ __global__ __launch_bounds__(64) void near_select_kernel(const SelectArgs p)
                     for (int w = lane; w < p.ns; w += WV) lmax = max(lmax, s_keys[w]);
                     for (int i = lane; i < rc; i += WV) lmax = max(lmax, rin[i]);
                     if (__popcll(ballot(lmax != 0u)) >= p.ncap)
-                        for (int bit = 31; bit >= 0; bit--) {
-                            const uint32_t trial = T0 | (1u << bit);
-                            if (__popcll(ballot(lmax >= trial)) >= p.ncap) T0 = trial;
-                        }
+                        T0 = key_descent(0u, 31, [&](uint32_t trial) { return __popcll(ballot(lmax >= trial)) >= p.ncap; });
                 }
                 int n_short = -1;                              // >= 0: s_short holds every key >= T0, at least ncap of them
                 if (T0 != 0u && count_keys([&](uint32_t k) { return k >= T0; }) <= NEAR_SHORT) {
@@ -251,10 +148,8 @@ __global__ __launch_bounds__(64) void near_select_kernel(const SelectArgs p)
                     for (int i = lane; i < n_short; i += WV) c += test(s_short[i]) ? 1 : 0;
                     return wave_sum(c);
                 };
-                for (int bit = 31; bit >= 0; bit--) {          // the largest T that at least ncap keys reach (>= 1: every screened key is)
-                    const uint32_t trial = T | (1u << bit);
-                    if (count_top([&](uint32_t k) { return k >= trial; }) >= p.ncap) T = trial;
-                }
+                // the largest T that at least ncap keys reach (>= 1: every screened key is)
+                T = key_descent(0u, 31, [&](uint32_t trial) { return count_top([&](uint32_t k) { return k >= trial; }) >= p.ncap; });
                 need_eq = p.ncap - count_top([&](uint32_t k) { return k > T; });
                 cut = (double)f32_unkey(T) - p.margin;
             }
@@ -315,11 +210,7 @@ __global__ __launch_bounds__(256) void near_exact_kernel(const double* __restric
     if (c >= ncand) return;
     const u64 key = gkey[c];
     const int64_t i = qb0 + (int64_t)(key >> 32), j = (int64_t)(key & 0xffffffffull);
-    const double* a = q + i * dim;
-    const double* b = x + j * dim;
-    double s = 0.0;                                            // dmul, dadd, ascending
-    for (int k = 0; k < dim; k++) s = s + a[k] * b[k];
-    gsim[c] = s / (qnorm[i] * xnorm[j]);                       // dot / (twoNorm * twoNorm)
+    gsim[c] = screen_exact_dot(q + i * dim, x + j * dim, dim) / (qnorm[i] * xnorm[j]);   // dot / (twoNorm * twoNorm)
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -329,7 +220,7 @@ __global__ __launch_bounds__(256) void near_exact_kernel(const double* __restric
 template <class At, class Emit>
 __device__ __forceinline__ int wave_first_n(At&& at, int64_t m, int n_cap, int lane, u64* sel_hi, uint32_t* sel_lo, Emit&& emit)
 {
-    const u64 below = (1ull << lane) - 1ull;
+    const u64 below = lanes_below(lane);
     auto count = [&](auto&& test) -> int64_t {
         int c = 0;
         for (int64_t i = lane; i < m; i += WV) { u64 h; uint32_t l; at(i, h, l); c += (h != 0 && test(h, l)) ? 1 : 0; }
@@ -340,14 +231,8 @@ __device__ __forceinline__ int wave_first_n(At&& at, int64_t m, int n_cap, int l
     if (n_eff == 0) return 0;
     u64 th = 0; uint32_t tl = 0;                               // the n_eff-th largest composite; (0, 0) takes every entry that counts
     if (nv > n_eff) {
-        for (int bit = 63; bit >= 0; bit--) {
-            const u64 trial = th | (1ull << bit);
-            if (count([&](u64 h, uint32_t) { return h >= trial; }) >= n_eff) th = trial;
-        }
-        for (int bit = 31; bit >= 0; bit--) {
-            const uint32_t trial = tl | (1u << bit);
-            if (count([&](u64 h, uint32_t l) { return h > th || (h == th && l >= trial); }) >= n_eff) tl = trial;
-        }
+        th = key_descent(0ull, 63, [&](u64 trial) { return count([&](u64 h, uint32_t) { return h >= trial; }) >= n_eff; });
+        tl = key_descent(0u, 31, [&](uint32_t trial) { return count([&](u64 h, uint32_t l) { return h > th || (h == th && l >= trial); }) >= n_eff; });
     }
     int got = 0;
     for (int64_t base = 0; base < m; base += WV) {
@@ -441,23 +326,6 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const double* __restrict
 
 unsigned row_blocks(int64_t rows, int num_cus) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t)num_cus * 32)); }
 
-// rows [n][dim] on the device -> cleaned in place, norms, classes ([n + NEAR_TILE], ROW_OUT behind n) and the fp32 image ([n + NEAR_TILE][ld], zero-padded)
-struct Rows { DevArray<double> x, norm; DevArray<uint8_t> cls; DevArray<float> xn; };
-
-int prepare_rows(mvhdp_ctx* h, Rows& r, int64_t n, int dim, int64_t ld, double min_weight)
-{
-    HIPC(h, r.norm.alloc((size_t)n));
-    HIPC(h, r.cls.alloc((size_t)(n + NEAR_TILE)));
-    HIPC(h, r.xn.alloc((size_t)(n + NEAR_TILE) * ld));
-    HIPC(h, r.cls.fill(0, h->stream));
-    HIPC(h, r.xn.fill(0, h->stream));
-    if (n == 0) return MVHDP_OK;
-    LAUNCH(h, near_prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.x, (int)n, dim, min_weight, r.norm, r.cls);
-    const int64_t cells = n * dim;
-    LAUNCH(h, near_normalise_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, r.x, r.norm, r.cls, (int)n, dim, ld, r.xn);
-    return MVHDP_OK;
-}
-
 // the proportions of entities [d0, d1) into out [d1 - d0][K], chunk by chunk
 int launch_theta(mvhdp_ctx* h, const DocTopicCarry& carry, const double* d_w, int64_t d0, int64_t d1, double* out)
 {
@@ -497,7 +365,7 @@ extern "C" int mvhdp_nearest_entities(mvhdp_handle h, const mvhdp_nearest_args* 
         FAIL(h, MVHDP_ERR_INVALID_ARG, "nearest_entities: negative block_queries, stripe_candidates or candidate_capacity");
     if (K > SIM_MAX_DIM) FAIL(h, MVHDP_ERR_UNSUPPORTED, "nearest_entities: K > 65536 (the screen's margin would reach 0.01)");
     const int64_t nq = a->queries ? a->nq : a->q1 - a->q0, C = a->c1 - a->c0;
-    if (nq >= ((int64_t)1 << 31) - NEAR_TILE || C >= ((int64_t)1 << 31) - NEAR_TILE) FAIL(h, MVHDP_ERR_UNSUPPORTED, "nearest_entities: 2^31 rows or more");
+    if (nq >= ((int64_t)1 << 31) - SCREEN_TILE || C >= ((int64_t)1 << 31) - SCREEN_TILE) FAIL(h, MVHDP_ERR_UNSUPPORTED, "nearest_entities: 2^31 rows or more");
     DocTopicCarry carry{};
     int rc = mvhdp_doc_topic_prepare(h, carry); if (rc) return rc;
     const int n = a->n;
@@ -520,9 +388,9 @@ extern "C" int mvhdp_nearest_entities(mvhdp_handle h, const mvhdp_nearest_args* 
     hipStream_t s = h->stream;
 
     // the two sets of rows, on the device for the whole call: 12 bytes per entry (fp64 rows for the exact stage, their fp32 image for the screen)
-    const int64_t ld = ((int64_t)K + NEAR_BK - 1) / NEAR_BK * NEAR_BK;
+    const int64_t ld = screen_ld(K);
     DevArray<double> d_w;
-    Rows qr, cr;
+    ScreenRows qr, cr;
     HIPC(h, d_w.alloc((size_t)mm.M));
     HIPC(h, d_w.upload(a->view_weights, (size_t)mm.M, s));
     HIPC(h, cr.x.alloc((size_t)C * K));
@@ -530,11 +398,11 @@ extern "C" int mvhdp_nearest_entities(mvhdp_handle h, const mvhdp_nearest_args* 
     rc = launch_theta(h, carry, d_w, a->c0, a->c1, cr.x); if (rc) return rc;
     if (a->queries) HIPC(h, qr.x.upload(a->queries, (size_t)nq * K, s));
     else { rc = launch_theta(h, carry, d_w, a->q0, a->q1, qr.x); if (rc) return rc; }
-    rc = prepare_rows(h, cr, C, K, ld, a->min_weight); if (rc) return rc;
-    rc = prepare_rows(h, qr, nq, K, ld, a->min_weight); if (rc) return rc;
+    rc = mvhdp_screen_prepare_rows(h, cr, C, K, a->min_weight, SCREEN_TILE, true); if (rc) return rc;
+    rc = mvhdp_screen_prepare_rows(h, qr, nq, K, a->min_weight, SCREEN_TILE, true); if (rc) return rc;
     {
         std::vector<uint8_t> hc((size_t)std::max(nq, C));
-        for (const Rows* r : {&qr, &cr}) {
+        for (const ScreenRows* r : {&qr, &cr}) {
             const size_t cnt = (size_t)(r == &qr ? nq : C);
             HIPC(h, hipMemcpyAsync(hc.data(), r->cls.get(), cnt, hipMemcpyDeviceToHost, s));
             HIPC(h, hipStreamSynchronize(s));
@@ -585,7 +453,7 @@ extern "C" int mvhdp_nearest_entities(mvhdp_handle h, const mvhdp_nearest_args* 
             for (int64_t s0 = 0; s0 < C; s0 += S, flip ^= 1) {
                 const int64_t s1 = std::min(s0 + S, C);
                 ScreenArgs sa{};
-                sa.xq = qr.xn; sa.xc = cr.xn; sa.ld = ld; sa.kslabs = (int)(ld / NEAR_BK); sa.clsq = qr.cls; sa.clsc = cr.cls;
+                sa.xq = qr.xn; sa.xc = cr.xn; sa.ld = ld; sa.kslabs = (int)(ld / SCREEN_BK); sa.clsq = qr.cls; sa.clsc = cr.cls;
                 sa.qb0 = qb0; sa.q1 = q1; sa.s0 = s0; sa.s1 = s1; sa.excl = excl; sa.self_delta = self_delta; sa.S = d_S; sa.ldS = S;
                 LAUNCH(h, near_screen_kernel, dim3((unsigned)near_tiles(s1 - s0), (unsigned)near_tiles(nr)), dim3(256), 0, s, sa);
                 SelectArgs se{};

@@ -22,11 +22,11 @@
 // resolves 64 positions with one inclusive scan and carries one state to the next 64.  A phrase starts at the last position that left
 // the automaton in HOLD and ends in front of the token that broke it; nothing is flushed at the end of the entity.
 #include "mvhdp_ctx.h"
+#include "mvhdp_select.h"
 
 namespace {
 
 constexpr int WV = 64;
-typedef unsigned long long u64;
 
 enum : int { ST_EMPTY = 0, ST_HOLD = 1, ST_OPEN = 2 };
 // state s maps to (map >> 2 s) & 3
@@ -38,8 +38,6 @@ enum { PH_RUNS = 0, PH_BAD = 1, PH_COLLISIONS = 2, PH_WORDS = 3 };
 constexpr u64 SLOT_FREE = ~0ull;
 
 struct PhraseRec { int64_t start; u64 hash; int32_t topic, len; };   // start: index into the view-0 tokens
-
-__device__ __forceinline__ u64 ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
 
 __device__ __forceinline__ int compose(int later, int earlier)  // later after earlier
 {

@@ -4,9 +4,10 @@
 #include <stdint.h>
 #include <cmath>
 
-enum { SIM_TILE = 128,                       // the screen's block tile: 128 x 128 cells, 4 waves of 2 x 2 MFMA tiles of 32 x 32
-       SIM_BK = 32,                          // k-slab staged in LDS per step
+enum { SCREEN_TILE = 128,                    // the cosine screen's block tile (mvhdp_screen.h): 128 x 128 cells, 4 waves of 2 x 2 MFMA tiles of 32 x 32
+       SCREEN_BK = 32,                       // its k-slab staged in LDS per step
        SIM_JSD_TILE = 16,                    // the JSD kernel's block tile (one thread per pair)
+       SIM_JSD_BK = 32,                      // and its slab of topics
        SIM_MAX_DIM = 65536,                  // margin(65536) = 0.0078 < 0.01
        SIM_AUTO_STRIPE = 4096 };
 static const int64_t SIM_AUTO_CAPACITY = (int64_t)1 << 22;

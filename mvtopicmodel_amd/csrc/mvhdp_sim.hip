@@ -9,33 +9,12 @@
 //                           one wave per entity or group, lanes over topics, kept flags from a rank among the weights >= threshold
 // No floating-point atomics: every fp64 sum is a chain in a fixed order.  The integer appends (candidates, survivors) are unordered;
 // the host sorts each stripe's survivors by (i << 32) | j.
-#include "mvhdp_ctx.h"
-#include "mvhdp_sim.h"
+#include "mvhdp_screen.h"
+#include "mvhdp_select.h"
 
 namespace {
 
 constexpr int WV = 64;
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned long long u64;
-
-enum : uint8_t { ROW_OUT = 0,                // norm 0, Inf or NaN: never pairs
-                 ROW_TAME = 1,               // screened
-                 ROW_WILD = 2 };             // a non-zero |entry| outside [2^-500, 2^500]: fp64 may under- or overflow, every pair is a candidate
-
-__device__ __forceinline__ u64 ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
-
-// One wave appends the keys of its lanes with `pass` to buf (capacity cap); *counter goes on counting beyond cap, so that the host
-// learns the size a redo needs.  Wave-uniform control flow.
-__device__ __forceinline__ u64 wave_append_slot(bool pass, u64* counter, int lane)
-{
-    const u64 m = ballot(pass);
-    if (!m) return ~0ull;
-    const int leader = __ffsll((long long)m) - 1;
-    u64 base = 0;
-    if (lane == leader) base = atomicAdd(counter, (u64)__popcll(m));
-    base = __shfl(base, leader);
-    return base + (u64)__popcll(m & ((1ull << lane) - 1ull));
-}
 
 // ---------------------------------------------------------------------------------------------------------------
 // One thread per row.  x is cleaned in place.
@@ -71,73 +50,20 @@ __global__ __launch_bounds__(256) void sim_normalise_kernel(const double* __rest
 
 // ---------------------------------------------------------------------------------------------------------------
 // The screen.  Block (b, a) of the stripe that starts at row r0 computes the 128 x 128 cells rows r0 + 128 a .., columns r0 + 128 b ..
-// (b >= a only).  Per k-slab of 32 the two row panels go through LDS; wave w owns the 64 x 64 quadrant (w >> 1, w & 1) as 2 x 2
-// MFMA tiles.  v_mfma_f32_32x32x2_f32 takes A[i = lane & 31][k = lane >> 5] and B[k = lane >> 5][j = lane & 31]; the lane's half
-// h = lane >> 5 reads the 16 consecutive k of its half of the slab (4 x ds_read_b128 per panel row), so step s multiplies k = s (h = 0)
-// and k = 16 + s (h = 1): a permutation of the slab's k order, the same for both operands -- still one fp32 fma chain over every k
-// once, which is all the margin asks for.  C/D: column = lane & 31, row = (reg & 3) + 8 (reg >> 2) + 4 (lane >> 5).
-// xn is padded with zero rows to r0 + 128 * tiles and zero columns to a multiple of 32: no bounds checks on the loads.
-constexpr int LDS_LD = SIM_BK + 4;                             // 36 floats: 16-byte aligned rows, b128 reads of a wave spread over the banks
-
+// (b >= a only) with screen_tile (mvhdp_screen.h has the layout); xn is padded with zero rows to r0 + 128 * tiles.
 __global__ __launch_bounds__(256) void sim_screen_kernel(const float* __restrict__ xn, int64_t ld, int kslabs, const uint8_t* __restrict__ cls,
                                                          int n, int r0, int r1, double cut, u64* __restrict__ cand, u64 cap, u64* counter)
 {
     const int ta = blockIdx.y, tb = blockIdx.x;
     if (tb < ta) return;
-    __shared__ __attribute__((aligned(16))) float As[SIM_TILE * LDS_LD];
-    __shared__ __attribute__((aligned(16))) float Bs[SIM_TILE * LDS_LD];
+    __shared__ __attribute__((aligned(16))) float As[SCREEN_TILE * SCREEN_LDS_LD];
+    __shared__ __attribute__((aligned(16))) float Bs[SCREEN_TILE * SCREEN_LDS_LD];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const int wr = (w >> 1) * 64, wc = (w & 1) * 64;
-    const int64_t arow0 = (int64_t)r0 + (int64_t)ta * SIM_TILE, brow0 = (int64_t)r0 + (int64_t)tb * SIM_TILE;
-
+    const int wr = (w >> 1) * 64, wc = (w & 1) * 64, lr = lane & 31, lh = lane >> 5;
+    const int64_t arow0 = (int64_t)r0 + (int64_t)ta * SCREEN_TILE, brow0 = (int64_t)r0 + (int64_t)tb * SCREEN_TILE;
     f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++)
-#pragma unroll
-            for (int e = 0; e < 16; e++) acc[a][b][e] = 0.0f;
+    screen_tile(xn, xn, ld, kslabs, arow0, brow0, As, Bs, acc);
 
-    // staging: 128 rows x 8 float4 per panel, 4 per thread (named registers: an array here ends up in scratch)
-    float4 ga0, ga1, ga2, ga3, gb0, gb1, gb2, gb3;
-    const int srow = t >> 3, sc4 = (t & 7) * 4;                // this thread's cells of a panel: rows srow + 32 q, floats sc4 .. sc4 + 3
-    const float* gpa = xn + (arow0 + srow) * ld + sc4;
-    const float* gpb = xn + (brow0 + srow) * ld + sc4;
-#define SIM_GLOAD(slab) { const int64_t ko = (int64_t)(slab) * SIM_BK; \
-        ga0 = *(const float4*)(gpa + ko); ga1 = *(const float4*)(gpa + 32 * ld + ko); ga2 = *(const float4*)(gpa + 64 * ld + ko); ga3 = *(const float4*)(gpa + 96 * ld + ko); \
-        gb0 = *(const float4*)(gpb + ko); gb1 = *(const float4*)(gpb + 32 * ld + ko); gb2 = *(const float4*)(gpb + 64 * ld + ko); gb3 = *(const float4*)(gpb + 96 * ld + ko); }
-    SIM_GLOAD(0)
-    const int lr = lane & 31, lh = lane >> 5;
-    for (int slab = 0; slab < kslabs; slab++) {
-        __syncthreads();                                       // the previous slab's reads are done
-        {
-            float* sa = As + srow * LDS_LD + sc4;
-            float* sb = Bs + srow * LDS_LD + sc4;
-            *(float4*)sa = ga0; *(float4*)(sa + 32 * LDS_LD) = ga1; *(float4*)(sa + 64 * LDS_LD) = ga2; *(float4*)(sa + 96 * LDS_LD) = ga3;
-            *(float4*)sb = gb0; *(float4*)(sb + 32 * LDS_LD) = gb1; *(float4*)(sb + 64 * LDS_LD) = gb2; *(float4*)(sb + 96 * LDS_LD) = gb3;
-        }
-        __syncthreads();
-        if (slab + 1 < kslabs) { SIM_GLOAD(slab + 1) }         // in flight under the MFMAs
-        float av[2][16], bv[2][16];
-#pragma unroll
-        for (int a = 0; a < 2; a++)
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const float4 va = *(const float4*)(As + (wr + a * 32 + lr) * LDS_LD + lh * 16 + q * 4);
-                const float4 vb = *(const float4*)(Bs + (wc + a * 32 + lr) * LDS_LD + lh * 16 + q * 4);
-                av[a][q * 4 + 0] = va.x; av[a][q * 4 + 1] = va.y; av[a][q * 4 + 2] = va.z; av[a][q * 4 + 3] = va.w;
-                bv[a][q * 4 + 0] = vb.x; bv[a][q * 4 + 1] = vb.y; bv[a][q * 4 + 2] = vb.z; bv[a][q * 4 + 3] = vb.w;
-            }
-#pragma unroll
-        for (int s = 0; s < 16; s++) {
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][s], bv[0][s], acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[0][s], bv[1][s], acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][s], bv[0][s], acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[1][s], bv[1][s], acc[1][1], 0, 0, 0);
-        }
-    }
-
-#undef SIM_GLOAD
     // epilogue: cell (i, j) is a candidate when i < j, both rows can pair, and either one is not screened or screen > threshold - margin.
     // Two passes over the accumulators: the block counts its candidates, takes its room with ONE atomic (a wave-level atomic per ballot
     // on the one counter serialises the whole grid: 452 ms instead of 42 at n = 100 000, profiles/similarity.md), then writes.
@@ -169,7 +95,7 @@ __global__ __launch_bounds__(256) void sim_screen_kernel(const float* __restrict
     __syncthreads();
     u64 at = room[4];
     for (int q = 0; q < w; q++) at += room[q];
-    const u64 below = (1ull << lane) - 1ull;
+    const u64 below = lanes_below(lane);
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
@@ -198,21 +124,7 @@ __global__ __launch_bounds__(256) void sim_exact_kernel(const double* __restrict
     if (c < ncand) {
         key = cand[c];
         const int64_t i = (int64_t)(key >> 32), j = (int64_t)(key & 0xffffffffull);
-        const double* a = x + i * dim;
-        const double* b = x + j * dim;
-        double s = 0.0;                                        // SparseVector.dotProductInternal / MatrixOps.dotProduct: dmul, dadd, ascending
-        if ((dim & 1) == 0) {                                  // rows are 16-byte aligned: two entries a load (a lane walks its own two rows, so every
-            const double2* a2 = (const double2*)a;             // load instruction of the wave touches up to 64 lines whatever its width)
-            const double2* b2 = (const double2*)b;
-#pragma unroll 4
-            for (int q = 0; q < dim / 2; q++) {
-                const double2 u = a2[q], v = b2[q];
-                s = s + u.x * v.x;
-                s = s + u.y * v.y;
-            }
-        } else
-            for (int k = 0; k < dim; k++) s = s + a[k] * b[k];
-        sim = s / (norm[i] * norm[j]);                         // NormalizedDotProductMetric.distance: dot / (twoNorm * twoNorm)
+        sim = screen_exact_dot(x + i * dim, x + j * dim, dim) / (norm[i] * norm[j]);   // NormalizedDotProductMetric.distance: dot / (twoNorm * twoNorm)
         if (metric == MVHDP_SIM_COS_FOLDED) sim = 1.0 - fabs(1.0 - sim);   // FLOW:1483
         pass = sim > threshold;                                // NaN compares false, as in Java
     }
@@ -227,22 +139,22 @@ __global__ __launch_bounds__(256) void sim_jsd_kernel(const double* __restrict__
 {
     const int ta = blockIdx.y, tb = blockIdx.x;
     if (tb < ta) return;
-    __shared__ double P[SIM_JSD_TILE][SIM_BK + 1], Q[SIM_JSD_TILE][SIM_BK + 1];
+    __shared__ double P[SIM_JSD_TILE][SIM_JSD_BK + 1], Q[SIM_JSD_TILE][SIM_JSD_BK + 1];
     const int t = threadIdx.x, tx = t & 15, ty = t >> 4, lane = t & 63;
     const int64_t i0 = (int64_t)r0 + ta * SIM_JSD_TILE, j0 = (int64_t)r0 + tb * SIM_JSD_TILE;
     const int64_t i = i0 + ty, j = j0 + tx;
     double klp = 0.0, klq = 0.0;
     bool infp = false, infq = false;
-    for (int k0 = 0; k0 < dim; k0 += SIM_BK) {
+    for (int k0 = 0; k0 < dim; k0 += SIM_JSD_BK) {
         __syncthreads();
-        for (int idx = t; idx < SIM_JSD_TILE * SIM_BK; idx += 256) {
+        for (int idx = t; idx < SIM_JSD_TILE * SIM_JSD_BK; idx += 256) {
             const int row = idx >> 5, kk = idx & 31;
             const bool in = k0 + kk < dim;
             P[row][kk] = (in && i0 + row < n) ? x[(i0 + row) * dim + k0 + kk] : 0.0;
             Q[row][kk] = (in && j0 + row < n) ? x[(j0 + row) * dim + k0 + kk] : 0.0;
         }
         __syncthreads();
-        const int kn = dim - k0 < SIM_BK ? dim - k0 : SIM_BK;
+        const int kn = dim - k0 < SIM_JSD_BK ? dim - k0 : SIM_JSD_BK;
         for (int kk = 0; kk < kn; kk++) {
             const double p = P[ty][kk], q = Q[tx][kk];
             if (p == 0.0 && q == 0.0) continue;                // neither klDivergence loop has a term here
@@ -411,6 +323,22 @@ int top_max(int32_t max, int K) { return (max < 0 || max > K) ? K : max; }   // 
 } // namespace
 
 // ---------------------------------------------------------------------------------------------------------------
+int mvhdp_screen_prepare_rows(mvhdp_ctx* h, ScreenRows& r, int64_t n, int dim, double min_weight, int64_t pad_rows, bool image)
+{
+    const int64_t ld = screen_ld(dim);
+    HIPC(h, r.norm.alloc((size_t)n));
+    HIPC(h, r.cls.alloc((size_t)(n + pad_rows)));
+    if (image) HIPC(h, r.xn.alloc((size_t)(n + pad_rows) * ld));
+    HIPC(h, r.cls.fill(0, h->stream));
+    if (image) HIPC(h, r.xn.fill(0, h->stream));
+    if (n == 0) return MVHDP_OK;
+    LAUNCH(h, sim_prepare_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, r.x, (int)n, dim, min_weight, r.norm, r.cls);
+    if (!image) return MVHDP_OK;
+    const int64_t cells = n * dim;
+    LAUNCH(h, sim_normalise_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, r.x, r.norm, r.cls, (int)n, dim, ld, r.xn);
+    return MVHDP_OK;
+}
+
 extern "C" int mvhdp_sim_probe(int32_t n, int32_t dim, int32_t stripe_rows, mvhdp_sim_stats* out)
 {
     if (!out || n < 0 || dim < 1 || stripe_rows < 0) return MVHDP_ERR_INVALID_ARG;
@@ -418,7 +346,7 @@ extern "C" int mvhdp_sim_probe(int32_t n, int32_t dim, int32_t stripe_rows, mvhd
     memset(out, 0, sizeof *out);
     out->margin = sim_margin(dim);
     out->stripes = sim_stripes(n, stripe_rows);
-    out->pairs_screened = sim_cells(n, stripe_rows, SIM_TILE);
+    out->pairs_screened = sim_cells(n, stripe_rows, SCREEN_TILE);
     return MVHDP_OK;
 }
 
@@ -434,7 +362,7 @@ extern "C" int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int6
     if (cap > 0 && (!oi || !oj || !osim)) FAIL(h, MVHDP_ERR_INVALID_ARG, "similar_pairs: cap > 0 with a null output");
     if (a->dim > SIM_MAX_DIM) FAIL(h, MVHDP_ERR_UNSUPPORTED, "similar_pairs: dim > 65536 (the screen's margin would reach 0.01)");
     const bool jsd = a->metric == MVHDP_SIM_JSD;
-    const int n = a->n, dim = a->dim, tile = jsd ? SIM_JSD_TILE : SIM_TILE;
+    const int n = a->n, dim = a->dim, tile = jsd ? SIM_JSD_TILE : SCREEN_TILE;
     const int64_t S = sim_stripe_rows(a->stripe_rows);
     mvhdp_sim_stats st{};
     st.margin = jsd ? 0.0 : sim_margin(dim);
@@ -444,25 +372,15 @@ extern "C" int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int6
     if (n < 2) { if (stats) *stats = st; return MVHDP_OK; }
     HIPC(h, hipSetDevice(h->device));
 
-    // rows are padded so that every tile of every stripe reads inside the image: a stripe may start at any row
-    const int64_t n_pad = (int64_t)n + 2 * SIM_TILE, ld = ((int64_t)dim + SIM_BK - 1) / SIM_BK * SIM_BK;
-    DevArray<double> x, norm, ssim;
-    DevArray<uint8_t> cls;
-    DevArray<float> xn;
+    // rows are padded so that every tile of every stripe reads inside the image: a stripe may start at any row.  JSD has no image.
+    const int64_t ld = screen_ld(dim);
+    ScreenRows R;
+    DevArray<double> ssim;
     DevArray<u64> ctr, cand, skey;
-    HIPC(h, x.alloc((size_t)n * dim));
-    HIPC(h, norm.alloc((size_t)n));
-    HIPC(h, cls.alloc((size_t)n_pad));
+    HIPC(h, R.x.alloc((size_t)n * dim));
     HIPC(h, ctr.alloc(2));
-    HIPC(h, cls.fill(0, h->stream));
-    HIPC(h, x.upload(a->x, (size_t)n * dim, h->stream));
-    LAUNCH(h, sim_prepare_kernel, dim3((n + 255) / 256), dim3(256), 0, h->stream, x, n, dim, a->min_weight, norm, cls);
-    if (!jsd) {
-        HIPC(h, xn.alloc((size_t)n_pad * ld));
-        HIPC(h, xn.fill(0, h->stream));
-        const int64_t cells = (int64_t)n * dim;
-        LAUNCH(h, sim_normalise_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, h->stream, x, norm, cls, n, dim, ld, xn);
-    }
+    HIPC(h, R.x.upload(a->x, (size_t)n * dim, h->stream));
+    int rc = mvhdp_screen_prepare_rows(h, R, n, dim, a->min_weight, 2 * SCREEN_TILE, !jsd); if (rc) return rc;
     u64 ccap = (u64)(a->candidate_capacity > 0 ? a->candidate_capacity : SIM_AUTO_CAPACITY);
     auto size_buffers = [&](u64 c) -> hipError_t {
         hipError_t e = skey.alloc((size_t)c);
@@ -486,9 +404,9 @@ extern "C" int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int6
         for (int attempt = 0; ; attempt++) {
             HIPC(h, ctr.fill(0, h->stream));
             if (jsd)
-                LAUNCH(h, sim_jsd_kernel, grid, dim3(256), 0, h->stream, x, cls, n, dim, (int)r0, (int)r1, a->threshold, skey, ssim, ccap, ctr);
+                LAUNCH(h, sim_jsd_kernel, grid, dim3(256), 0, h->stream, R.x, R.cls, n, dim, (int)r0, (int)r1, a->threshold, skey, ssim, ccap, ctr);
             else
-                LAUNCH(h, sim_screen_kernel, grid, dim3(256), 0, h->stream, xn, ld, (int)(ld / SIM_BK), cls, n, (int)r0, (int)r1, cut, cand, ccap, ctr);
+                LAUNCH(h, sim_screen_kernel, grid, dim3(256), 0, h->stream, R.xn, ld, (int)(ld / SCREEN_BK), R.cls, n, (int)r0, (int)r1, cut, cand, ccap, ctr);
             HIPC(h, ctr.download(hc, 2, h->stream));
             HIPC(h, hipStreamSynchronize(h->stream));
             if (hc[0] <= ccap) break;
@@ -501,7 +419,7 @@ extern "C" int mvhdp_similar_pairs(mvhdp_handle h, const mvhdp_sim_args* a, int6
         if (!jsd) {
             st.candidates += (int64_t)hc[0];
             if (hc[0]) {
-                LAUNCH(h, sim_exact_kernel, dim3((unsigned)((hc[0] + 255) / 256)), dim3(256), 0, h->stream, x, norm, dim, a->metric, a->threshold,
+                LAUNCH(h, sim_exact_kernel, dim3((unsigned)((hc[0] + 255) / 256)), dim3(256), 0, h->stream, R.x, R.norm, dim, a->metric, a->threshold,
                        cand, hc[0], skey, ssim, ctr + 1);
                 HIPC(h, ctr.download(hc, 2, h->stream));
                 HIPC(h, hipStreamSynchronize(h->stream));

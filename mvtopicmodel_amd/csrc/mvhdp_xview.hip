@@ -20,19 +20,17 @@
 // Work is cut on the host: theta in ranges of entities, scores in blocks of rows, phi in stripes of types, each within XVIEW_BLOCK_BYTES.
 // Everything runs on the handle's stream.
 #include "mvhdp_ctx.h"
+#include "mvhdp_select.h"
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr size_t XVIEW_BLOCK_BYTES = (size_t)256 << 20;        // the block of scores, the phi stripe and the theta range: each at most this
 constexpr int XV_TE = 4, XV_TW = 8;                            // a thread's tile: entities x types
 constexpr int XV_BE = 16 * XV_TE, XV_BW = 16 * XV_TW;          // a block's tile: 64 x 128
 constexpr int XV_KS = 16;                                      // topics per slab
 constexpr size_t XV_SELECT_LDS_BYTES = 64 << 10;                  // a row of keys up to this size is selected from LDS (V_m <= 8192)
-constexpr u64 XV_EXCLUDED = ~0ull;                             // the bits written over an excluded type's score: key 0
-
-// order-preserving: a < b as doubles (no NaN) iff key(a) < key(b); -0.0 < +0.0 here, and the chain never yields -0.0 (it starts at +0.0)
-__device__ __forceinline__ u64 score_key(u64 bits) { return (bits >> 63) ? ~bits : bits | (1ull << 63); }
+constexpr u64 XV_EXCLUDED = ~0ull;                             // the bits written over an excluded type's score: f64_bits_key gives 0
+// (the scores are read as their bits and ordered by f64_bits_key; the chain never yields -0.0: it starts at +0.0)
 
 __global__ __launch_bounds__(256) void xview_phi_kernel(const int32_t* __restrict__ rows /*n_wk of the stripe's first type*/, const int32_t* __restrict__ nk,
                                                         const uint8_t* __restrict__ inactive, int K, int64_t cells, double beta, double beta_sum, double* __restrict__ phi)
@@ -162,7 +160,7 @@ __global__ __launch_bounds__(256) void xview_mark_kernel(u64* __restrict__ S, in
     }
 }
 
-__device__ __forceinline__ int64_t wave_count(bool p) { return (int64_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(p)); }
+__device__ __forceinline__ int64_t wave_count(bool p) { return (int64_t)__builtin_popcountll(ballot(p)); }
 
 // one wave per row: counts[r] = min(n, entries that are not excluded); the first counts[r] entries of the order (key descending, equal
 // keys by ascending type) go to sel_key / sel_id [r][n_cap] in ascending type id.  The descent reads the row once per bit that the keys
@@ -174,32 +172,31 @@ __global__ __launch_bounds__(IN_LDS ? 64 : 256) void xview_select_kernel(const u
 {
     extern __shared__ u64 s_keys[];                            // IN_LDS: [V]
     const int lane = threadIdx.x & 63;
-    const u64 lt_mask = (1ull << lane) - 1;
+    const u64 lt_mask = lanes_below(lane);
     const int64_t wave = IN_LDS ? (int64_t)blockIdx.x : (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = IN_LDS ? (int64_t)gridDim.x : (int64_t)gridDim.x * 4;
     for (int64_t r = wave; r < n_rows; r += nwaves) {
         const u64* __restrict__ row = S + r * V;
-        auto key_at = [&](int64_t w) -> u64 { return w < V ? (IN_LDS ? s_keys[w] : score_key(row[w])) : 0; };
+        auto key_at = [&](int64_t w) -> u64 { return w < V ? (IN_LDS ? s_keys[w] : f64_bits_key(row[w])) : 0; };
         // how many keys of the row pass the test: every lane counts its own (w = lane, lane + 64, ..), the 64 counts are added at the end
         auto count_keys = [&](auto&& test) -> int64_t {
             int c = 0;
 #pragma unroll 8
-            for (int64_t w = lane; w < V; w += 64) c += test(IN_LDS ? s_keys[w] : score_key(row[w])) ? 1 : 0;
-            for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-            return (int64_t)c;
+            for (int64_t w = lane; w < V; w += 64) c += test(IN_LDS ? s_keys[w] : f64_bits_key(row[w])) ? 1 : 0;
+            return (int64_t)wave_sum(c);
         };
         if (IN_LDS) {
             __syncthreads();                                   // (one wave: the reads of the row before are done)
-            for (int64_t w = lane; w < V; w += 64) s_keys[w] = score_key(row[w]);
+            for (int64_t w = lane; w < V; w += 64) s_keys[w] = f64_bits_key(row[w]);
             __syncthreads();
         }
         int nv = 0;
         u64 all_and = ~0ull, all_or = 0;
 #pragma unroll 8
         for (int64_t w = lane; w < V; w += 64) {
-            const u64 key = IN_LDS ? s_keys[w] : score_key(row[w]);
+            const u64 key = IN_LDS ? s_keys[w] : f64_bits_key(row[w]);
             if (key != 0) { nv++; all_and &= key; all_or |= key; }
         }
-        for (int o = 32; o > 0; o >>= 1) { nv += __shfl_xor(nv, o, 64); all_and &= __shfl_xor(all_and, o, 64); all_or |= __shfl_xor(all_or, o, 64); }
+        for (int o = 32; o > 0; o >>= 1) { nv += __shfl_xor(nv, o, 64); all_and &= __shfl_xor(all_and, o, 64); all_or |= __shfl_xor(all_or, o, 64); }   // one butterfly for the three
         const int64_t valid = nv;
         const int64_t n_eff = valid < (int64_t)n_cap ? valid : (int64_t)n_cap;
         if (lane == 0) counts[r] = (int32_t)n_eff;
@@ -209,11 +206,7 @@ __global__ __launch_bounds__(IN_LDS ? 64 : 256) void xview_select_kernel(const u
         u64 T = all_and;
         if (diff) {
             const int hb = 63 - __builtin_clzll(diff);
-            T = hb == 63 ? 0 : all_and & ~((2ull << hb) - 1);
-            for (int bit = hb; bit >= 0; bit--) {
-                const u64 trial = T | (1ull << bit);
-                if (count_keys([&](u64 key) { return key >= trial; }) >= n_eff) T = trial;
-            }
+            T = key_descent(hb == 63 ? 0 : all_and & ~((2ull << hb) - 1), hb, [&](u64 trial) { return count_keys([&](u64 key) { return key >= trial; }) >= n_eff; });
         }
         const int64_t need_eq = n_eff - count_keys([&](u64 key) { return key > T; });                // >= 1: fewer than n_eff keys lie above T
         int64_t taken_eq = 0, at = 0;
@@ -222,9 +215,9 @@ __global__ __launch_bounds__(IN_LDS ? 64 : 256) void xview_select_kernel(const u
         for (int64_t base = 0; base < V; base += 64) {
             const int64_t w = base + lane;
             const u64 key = key_at(w);
-            const u64 eq_b = __builtin_amdgcn_ballot_w64(key == T && key != 0);
+            const u64 eq_b = ballot(key == T && key != 0);
             const bool sel = key > T || (key == T && key != 0 && taken_eq + (int64_t)__builtin_popcountll(eq_b & lt_mask) < need_eq);
-            const u64 sel_b = __builtin_amdgcn_ballot_w64(sel);
+            const u64 sel_b = ballot(sel);
             if (sel) {
                 const int64_t pos = at + (int64_t)__builtin_popcountll(sel_b & lt_mask);
                 ok[pos] = key; oi[pos] = (int32_t)w;
@@ -272,11 +265,11 @@ __global__ __launch_bounds__(256) void xview_rank_kernel(const u64* __restrict__
     for (int64_t p = wave; p < n_pairs; p += nwaves) {
         const u64* __restrict__ row = S + (int64_t)pair_row[p] * V;
         const int64_t q = pair_item[p];
-        const u64 kq = score_key(pair_score[p]);
+        const u64 kq = f64_bits_key(pair_score[p]);
         int64_t c = 0;
         for (int64_t base = 0; base < V; base += 64) {
             const int64_t w = base + lane;
-            const u64 key = w < V ? score_key(row[w]) : 0;
+            const u64 key = w < V ? f64_bits_key(row[w]) : 0;
             c += wave_count(key != 0 && w != q && (key > kq || (key == kq && w < q)));
         }
         if (lane == 0) rank[p] = (int32_t)c;

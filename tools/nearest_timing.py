@@ -117,7 +117,7 @@ def kernel_trace(argv, limit=420):
             return None
         out = {}
         for row in csv.DictReader(open(files[0])):
-            k = re.search(r"near_\w+|topk_\w+|doc_topic_prop_kernel", row["Name"])
+            k = re.search(r"near_\w+|topk_\w+|sim_prepare_kernel|sim_normalise_kernel|doc_topic_prop_kernel", row["Name"])
             if k:
                 out[k.group(0)] = (int(row["Calls"]), float(row["TotalDurationNs"]) / 1e6)
         return out or None
