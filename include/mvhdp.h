@@ -438,6 +438,77 @@ int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_args* a, int
         double* doc_ll /*[D] or NULL*/, double* position_sum /*[N] or NULL: S[n], 0 for OOV*/,
         int64_t* doc_tokens /*[D] or NULL*/, mvhdp_heldout_stats* stats);
 
+/* Fold-in: the topic proportions of a batch of UNSEEN documents over the M views, on the trained handle, in one call: tokens to theta.  The
+ * rows feed mvhdp_nearest_entities (args.queries) and mvhdp_predict_items (args.theta) as they are.  The reference's route
+ * (inferTopicDistributionsOnNewDocs INF:114-330: a second model, inference trees, frozen sweeps) stays available through a second handle
+ * (mvhdp_set_counts, mvhdp_build_inference_trees, mvhdp_init_assignments_from_trees, MVHDP_SWEEP_FROZEN, mvhdp_doc_topic_proportions);
+ * THIS definition is ours: the reference sampler's conditional written densely over all K topics, a chain of our own;
+ * tests/native/foldin_ref.c restates this paragraph sequentially and the device equals it bit for bit.
+ * Model: n_wk[m], n_k[m], beta[m], betaSum[m], gamma[m], alpha[m][0..K), alphaSum[m] of every view and inActiveTopicIndex, frozen for the
+ *   call and taken AS THE HANDLE HOLDS THEM -- the state rule of mvhdp_heldout_left_to_right: MVHDP_ERR_STATE without counts or
+ *   hyper-parameters; stale counts and the pending deltas of a MVHDP_SWEEP_NO_APPLY sweep are neither refused nor applied.  A vectors mix
+ *   (mvhdp_set_vectors_mix) is ignored (the inferencer's worker runs with lambda = 0, INF:251-252).  The documents come with the call; the
+ *   handle's corpus and assignments are neither needed nor touched.
+ * Document d (global id doc_base + d): its view-m span is tokens[m][doc_off[m][d] .. doc_off[m][d + 1]); doc_off[m] == NULL: no document
+ *   has view m (every span empty).  len_m = the span's length, out-of-vocabulary tokens included (the length mvhdp_doc_topic_proportions
+ *   uses).  A token >= V_m is out of vocabulary: never visited, holds no topic (z = -1 in the output), in no count.  Every other token
+ *   starts unassigned.
+ * Weights, all fp64, every operation rounded on its own (no fused multiply-add):
+ *   a_m[k] = gamma[m] * alpha[m][k];  Lp_m = (double)len_m + gamma[m] * alphaSum[m];  rinv_m[k] = 1.0 / ((double)n_k[m][k] + betaSum[m]),
+ *   once per call;  phi_{m,w}[k] = ((double)n_wk[m][w][k] + beta[m]) * rinv_m[k], and exactly 0.0 for a topic in inActiveTopicIndex
+ *   (PTM:2670-2671), which is therefore never drawn.
+ * Coupling: P = args.coupling, [M][M] row-major on the host, every entry finite and >= 0 (else MVHDP_ERR_INVALID_ARG).  With NULL:
+ *   P[m][m] = 1, P[m][i] = p_a[m][i] / (p_a[m][i] + p_b[m][i]) of the handle's hyper-parameters (the mean of the reference's per-entity
+ *   Beta draw, WRK:331-333, unrounded), and 0 where p_a[m][i] == 0.
+ * One iteration (it = 1 .. iterations): views in ascending m, within a view the positions in ascending order (WRK:393,425).  At the start
+ *   of view m's pass, from the CURRENT counts of the other views (WRK:395-410, the same operation order), for every topic k:
+ *     s = 0.0;  for i ascending, i != m, len_i != 0:  s = s + P[m][i] * ((double)n_dk[i][k] + a_i[k]) / Lp_i   (product, then quotient);
+ *     o_m[k] = s * Lp_m;  base_m[k] = a_m[k] + o_m[k].
+ *   A view with len_m == 0 has no pass.  A visit of an in-vocabulary token w at position pos: if the token has a topic, take it out of
+ *   n_dk[m];  wt[k] = (P[m][m] * (double)n_dk[m][k] + base_m[k]) * phi_{m,w}[k];  draw a topic, give it to the token and add it to
+ *   n_dk[m].  A visit has no divide.
+ * Draw: lane ownership (T, lane l owns the topics l T + j), the in-lane prefix sums, the wave scan, total, and "the first topic in
+ *   ascending order with wt > 0.0 whose running sum exceeds u * total, else the last topic with wt > 0.0" are exactly the summation-order
+ *   paragraph of mvhdp_heldout_left_to_right above.  total == 0.0 or not finite: the token is left as it was before the visit (an
+ *   unassigned one stays unassigned and uncounted).  u = bits_to_unit(x0, x1) of Philox4x32-10 with key = seed (low word, high word) and
+ *   counter (low 32 bits of doc_base + d,  high 32 bits of doc_base + d,  it + m * 2^16,  pos): a document's draws depend on nothing but
+ *   its global id, the seed and its own tokens.
+ * Samples: S = args.samples >= 1, args.thin >= 1; the recorded states are those after the iterations iterations - (S - 1 - s) * thin,
+ *   s = 0 .. S - 1; each of them must be >= 1 and iterations >= 1 (else MVHDP_ERR_INVALID_ARG).  counts_sum[d][m][k] = the integer sum of
+ *   n_dk[m][k] over the recorded states.  S = 1: the final state, as the reference reports; S > 1: the average of MALLET's
+ *   getSampledDistribution, which a six-token side view needs.
+ * theta[d][k]: the expression of mvhdp_doc_topic_proportions, the same operations in the same order, with n_dk[m][k] replaced by
+ *   (double)counts_sum[d][m][k] / (double)S (the count itself for S = 1) and len_m as above.  Every view takes part as present: an empty
+ *   span scores with zeros, as mvhdp_set_view_presence = 1 does; nothing carries over between documents.  view_weights as in that entry:
+ *   finite, none negative, their sum > 0 (else MVHDP_ERR_INVALID_ARG); it may be NULL when theta is NULL.
+ * z[m][n]: the final state of every position (-1: out of vocabulary or unassigned); z, or any z[m], may be NULL.  stats: tokens (in
+ *   vocabulary) and oov over all views; visits = weight vectors formed = tokens * iterations; kernel_ms = the kernel's time on the stream.
+ * mvhdp_foldin_args, in this order: int32 iterations, samples, thin; uint64 seed; int64 doc_base; the two host pointers (48 bytes with
+ *   the padding behind thin); mvhdp_foldin_stats: three int64 and a double (32 bytes).  tests/test_foldin_kats.py pins both.
+ * Limits: K <= MVHDP_MAX_TOPICS, M <= 8, iterations <= 65535 (the counter's 16 bits), a span of at most 2^31 - 1 tokens, otherwise any
+ *   length.  MVHDP_ERR_INVALID_ARG: a NULL args, doc_off or tokens array, a negative num_docs, token or doc_base, a doc_off[m] that does
+ *   not start at 0 or decreases, the cases named above; -1 for a NULL handle.  num_docs == 0: MVHDP_OK.  Every output is untouched on error.
+ * Guarantees: two calls with the same arguments return the same bytes (kernel_ms aside); a document's result does not depend on which
+ *   other documents share the call; the counts, the assignments, the tuning and what mvhdp_counts_written / mvhdp_trees_current would
+ *   report are what they were.  Pending work on the handle's stream lands first.
+ * Departures from the frozen-sweep inferencer: the reference adds the other views' mass only for the topics in the document's non-zero
+ *   list, which never grows during a visit, and reaches gamma * alpha * p_wt through a stored tree and a three-way branch -- we form the
+ *   same sum densely over every topic; it draws p per entity from Beta(0.2, 1), rounded to three decimals, from a stream that cannot be
+ *   seeded (INF:221-224, WRK:331-336) -- we take a fixed matrix; it zeroes the coupling of a view whose beta == 0.0001 (WRK:335-336) -- we
+ *   do not, the caller passes a zero; its initial topics come from trees of p_wt alone (INF:169-199) -- ours come from the first
+ *   iteration's visits of unassigned tokens; its out-of-vocabulary tokens keep topic 0 and are counted in it by printDocumentTopics --
+ *   ours hold none.
+ * Cost: tokens * iterations visits, each gathering one count row; device scratch is bounded per chunk of documents (mvhdp_foldin.hip). */
+typedef struct { int32_t iterations, samples, thin; uint64_t seed; int64_t doc_base;
+                 const double* coupling /*[M][M] host, or NULL*/;
+                 const double* view_weights /*[M], or NULL without theta*/; } mvhdp_foldin_args;
+typedef struct { int64_t tokens /* in vocabulary */, oov, visits; double kernel_ms; } mvhdp_foldin_stats;
+int mvhdp_fold_in(mvhdp_handle h, const mvhdp_foldin_args* a, int64_t num_docs,
+        const int64_t* const* doc_off /*[M] -> [num_docs+1]; an entry may be NULL: no document has that view*/,
+        const int32_t* const* tokens /*[M] -> [N_m]*/,
+        double* theta /*[num_docs][K] or NULL*/, int32_t* const* z /*[M] -> [N_m]; entries or the array itself may be NULL*/,
+        int32_t* counts_sum /*[num_docs][M][K] or NULL*/, mvhdp_foldin_stats* stats /* or NULL */);
+
 /* Cross-view prediction: the types of view m ranked per entity by the model's own expectation, score(d, w) = sum_k theta_d[k] * phi[w][k].
  * The reference has no counterpart (its flow ends at the similarity SQL): THIS definition is ours; tests/native/xview_ref.c restates it.
  * theta_d[k]: the bits of mvhdp_doc_topic_proportions(h, view_weights, d, d + 1), its missing-view carry-over included.  A caller who

@@ -16,7 +16,7 @@ ABI_SYMBOLS = [
     "mvhdp_get_counts", "mvhdp_set_counts", "mvhdp_get_tree", "mvhdp_get_doc_topic_hist",
     "mvhdp_get_count_histogram", "mvhdp_view_overlap_sums", "mvhdp_model_log_likelihood", "mvhdp_doc_topic_proportions",
     "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
-    "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_predict_items", "mvhdp_score_items",
+    "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_fold_in", "mvhdp_predict_items", "mvhdp_score_items",
     "mvhdp_nearest_entities", "mvhdp_nearest_probe", "mvhdp_topic_top_entities",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
@@ -166,6 +166,15 @@ class HeldoutStatsC(C.Structure):
     _fields_ = [("log_likelihood", C.c_double), ("tokens", C.c_int64), ("oov", C.c_int64), ("visits", C.c_int64)]
 
 
+class FoldinArgsC(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("samples", C.c_int32), ("thin", C.c_int32), ("seed", C.c_uint64), ("doc_base", C.c_int64),
+                ("coupling", C.c_void_p), ("view_weights", C.c_void_p)]
+
+
+class FoldinStatsC(C.Structure):
+    _fields_ = [("tokens", C.c_int64), ("oov", C.c_int64), ("visits", C.c_int64), ("kernel_ms", C.c_double)]
+
+
 class PredictArgsC(C.Structure):
     _fields_ = [("m", C.c_int32), ("exclude_present", C.c_int32), ("view_weights", C.c_void_p), ("theta", C.c_void_p)]
 
@@ -295,6 +304,7 @@ def load_library():
     L.mvhdp_sim_probe.argtypes = [i32, i32, i32, C.POINTER(SimStatsC)]
     L.mvhdp_topic_phrases.argtypes = [vp, C.POINTER(PhraseArgsC), i64, i64, vp, vp, vp, vp, vp, vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(PhraseStatsC)]
     L.mvhdp_heldout_left_to_right.argtypes = [vp, C.POINTER(HeldoutArgsC), i64, vp, vp, vp, vp, vp, C.POINTER(HeldoutStatsC)]
+    L.mvhdp_fold_in.argtypes = [vp, C.POINTER(FoldinArgsC), i64, vp, vp, vp, vp, vp, C.POINTER(FoldinStatsC)]
     L.mvhdp_predict_items.argtypes = [vp, C.POINTER(PredictArgsC), i64, i64, i32, vp, vp, vp]
     L.mvhdp_score_items.argtypes = [vp, C.POINTER(PredictArgsC), i64, i64, i64, vp, vp, vp, vp]
     L.mvhdp_nearest_entities.argtypes = [vp, C.POINTER(NearestArgsC), vp, vp, vp, C.POINTER(NearestStatsC)]

@@ -18,6 +18,7 @@
 // token) stay within HELDOUT_SCRATCH_BYTES.  Everything runs on the handle's stream.
 #include "mvhdp_ctx.h"
 #include "mvhdp_wave.h"
+#include "mvhdp_lanes.h"
 
 namespace {
 
@@ -40,34 +41,6 @@ struct HeldoutArgs {
     double beta, alpha_sum;
     uint32_t seed_lo, seed_hi;
 };
-
-__device__ __forceinline__ int64_t uniform_i64(int64_t x)
-{
-    const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x), hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((u64)x >> 32));
-    return (int64_t)(((u64)hi << 32) | lo);
-}
-
-// the count cells of lane's T topics of row w; cells beyond K read as 0
-template <int T, bool VEC>
-__device__ __forceinline__ void gather_row(const int32_t* __restrict__ rows, int w, int K, int lane, int (&row)[T])
-{
-    const int32_t* __restrict__ rp = rows + (int64_t)w * K;
-    if constexpr (VEC) {
-#pragma unroll
-        for (int j = 0; j < T; j += 4) {
-            const int k = lane * T + j;
-            int4 v = make_int4(0, 0, 0, 0);
-            if (k < K) v = *reinterpret_cast<const int4*>(rp + k);    // K % 4 == 0: the four cells are inside the row together, 16-byte aligned
-            row[j] = v.x; row[j + 1] = v.y; row[j + 2] = v.z; row[j + 3] = v.w;
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < T; j++) {
-            const int k = lane * T + j;
-            row[j] = k < K ? rp[k] : 0;
-        }
-    }
-}
 
 template <int T, bool VEC>
 __global__ __launch_bounds__(256) void heldout_ltr_kernel(const HeldoutArgs a)

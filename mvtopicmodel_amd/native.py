@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   EmbConfigC, EmbStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
+                   EmbConfigC, EmbStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
@@ -293,6 +293,20 @@ class HeldoutResult:
     @property
     def perplexity(self):
         return float(np.exp(-self.log_likelihood / self.tokens)) if self.tokens else float("nan")
+
+
+@dataclass
+class FoldinResult:
+    """mvhdp_fold_in: theta [D][K], the topic proportions of the folded-in documents (None without view_weights); z, a list of M arrays
+    (-1: out of vocabulary or unassigned; None for a view no document has) or None; counts_sum [D][M][K], n_dk added over the recorded
+    states, or None; tokens (in vocabulary) and oov over all views; visits = weight vectors formed; kernel_ms = the kernel's time."""
+    theta: np.ndarray
+    z: list
+    counts_sum: np.ndarray
+    tokens: int = 0
+    oov: int = 0
+    visits: int = 0
+    kernel_ms: float = 0.0
 
 
 @dataclass
@@ -710,6 +724,49 @@ class NativeSampler:
         st = HeldoutStatsC()
         self._ck(self.L.mvhdp_heldout_left_to_right(self.h, C.byref(a), D, _ptr(doc_off), _ptr(tokens), _ptr(doc_ll), _ptr(pos), _ptr(doc_tokens), C.byref(st)))
         return HeldoutResult(st.log_likelihood, doc_ll, pos, doc_tokens, st.tokens, st.oov, st.visits, int(particles))
+
+    def fold_in(self, doc_off, tokens, view_weights, iterations=10, samples=1, thin=1, seed=0, doc_base=0, coupling=None, want_z=False,
+                want_counts=False):
+        """The topic proportions of unseen documents against this handle's frozen counts (include/mvhdp.h mvhdp_fold_in): a FoldinResult
+        whose theta rows go to nearest_entities(queries=...) and predict_items(theta=...) as they are.  doc_off and tokens: lists of
+        length M, None for a view no document has; a token >= V[m] is out of vocabulary.  view_weights [M] as doc_topic_proportions
+        takes them (None: no theta).  samples > 1 averages the states after the last `samples` iterations that lie `thin` apart.
+        coupling: [M][M], how much of view i's topic mass view m's conditional sees (None: the mean of the handle's Beta(p_a, p_b))."""
+        if len(doc_off) != self.M or len(tokens) != self.M:
+            raise ValueError("doc_off and tokens: one entry per view (None for a view no document has)")
+        offs, toks, D = [], [], None
+        for o, t in zip(doc_off, tokens):
+            if o is None:
+                offs.append(None); toks.append(None)
+                continue
+            o, t = _heldout_docs(o, np.zeros(0, dtype=np.int32) if t is None else t)
+            if D is not None and len(o) - 1 != D:
+                raise ValueError("every view's doc_off must describe the same documents")
+            D = len(o) - 1
+            offs.append(o); toks.append(t)
+        D = 0 if D is None else D
+        a = FoldinArgsC(int(iterations), int(samples), int(thin), int(seed), int(doc_base), None, None)
+        w = p = None
+        if view_weights is not None:
+            w = np.ascontiguousarray(view_weights, dtype=np.float64)
+            if w.shape != (self.M,):
+                raise ValueError("view_weights must be [M]")
+            a.view_weights = w.ctypes.data
+        if coupling is not None:
+            p = np.ascontiguousarray(coupling, dtype=np.float64)
+            if p.shape != (self.M, self.M):
+                raise ValueError("coupling must be [M][M]")
+            a.coupling = p.ctypes.data
+        vpM = C.c_void_p * self.M
+        theta = np.zeros((D, self.K), dtype=np.float64) if w is not None else None
+        z = [None if o is None else np.full(len(t), -1, dtype=np.int32) for o, t in zip(offs, toks)] if want_z else None
+        cs = np.zeros((D, self.M, self.K), dtype=np.int32) if want_counts else None
+        c_off = vpM(*[None if o is None else o.ctypes.data for o in offs])
+        c_tok = vpM(*[None if t is None else t.ctypes.data for t in toks])
+        c_z = vpM(*[None if x is None else x.ctypes.data for x in z]) if want_z else None
+        st = FoldinStatsC()
+        self._ck(self.L.mvhdp_fold_in(self.h, C.byref(a), D, c_off, c_tok, _ptr(theta), c_z, _ptr(cs), C.byref(st)))
+        return FoldinResult(theta, z, cs, st.tokens, st.oov, st.visits, st.kernel_ms)
 
     # -- cross-view prediction (include/mvhdp.h mvhdp_predict_items / mvhdp_score_items) --
     def _predict_args(self, m, view_weights, d0, d1, exclude_present, theta):
@@ -1217,6 +1274,14 @@ class NativeGroup:
         return HeldoutResult(total, doc_ll, np.concatenate([p.position_sum for p in parts]) if want_position_sums else None,
                              np.concatenate([p.doc_tokens for p in parts]), sum(p.tokens for p in parts), sum(p.oov for p in parts),
                              sum(p.visits for p in parts), int(particles))
+
+    def fold_in(self, doc_off, tokens, view_weights, iterations=10, samples=1, thin=1, seed=0, doc_base=0, coupling=None, want_z=False,
+                want_counts=False):
+        """NativeSampler.fold_in on the first LOCAL member, the group drained first: the model is replicated, so any member's answer is
+        the group's."""
+        if self.g is not None:
+            self.drain()
+        return self.members[0].fold_in(doc_off, tokens, view_weights, iterations, samples, thin, seed, doc_base, coupling, want_z, want_counts)
 
     def _member_ranges(self, d0, d1):
         """the LOCAL members' entities as one sequence, member after member: (member, first global id, local d0, local d1) of every
