@@ -546,6 +546,58 @@ int mvhdp_score_items(mvhdp_handle h, const mvhdp_predict_args* a, int64_t d0, i
                       const int64_t* entity /*[n_pairs], in [d0,d1), any order, repeats allowed*/, const int32_t* item /*[n_pairs], in [0,V_m)*/,
                       double* score /*[n_pairs]*/, int32_t* rank /*[n_pairs]*/);
 
+/* Entities for an item: the candidate entities [c0, c1) of this handle ranked per QUERY by the same expectation, taken from the item's side:
+ * score(d, j) = sum_k theta_d[k] * psi_j[k], psi_j a weighted set of phi rows of view m (a tag, a cited paper, a few query words) or a row
+ * of the caller's.  The reference has no counterpart: THIS definition is ours; tests/native/xview_entities_ref.c restates it.
+ * theta_d[k]: the bits of mvhdp_doc_topic_proportions(h, view_weights, d, d + 1), its missing-view carry-over included; formed on the device
+ *   in blocks and never shipped to the host.  view_weights: finite, none negative, their sum > 0; a caller who predicts view m from the
+ *   other views passes view_weights[m] = 0.
+ * phi[w][k]: exactly that of mvhdp_predict_items -- one correctly rounded division, exactly 0.0 for a topic in inActiveTopicIndex.  A
+ *   vectors mix is NOT applied.
+ * Query row psi_j[k], item form (psi == NULL): query j is the list q_items[q_off[j] .. q_off[j + 1]) with weights c_i = q_weights[i] (1.0
+ *   with q_weights == NULL):  p = +0.0; for i ascending: p = fma(c_i, phi[w_i][k], p).  One item of weight 1.0 gives the bits of phi[w][k].
+ *   Every item must lie in [0, V_m) (unlike a corpus token, an item >= V_m is an error); every weight finite, >= 0 and <= 2^53; a query
+ *   holds at most 2^20 items, so psi stays finite.  Repeated items are allowed and each occurrence adds.  An empty query is a row of zeros.
+ *   Host form (psi != NULL): the caller's rows [nq][K], every entry finite and >= 0 -- a topic mixture, or phi rows of another model;
+ *   q_off, q_items, q_weights and exclude_present are then ignored.
+ * score(d, j): s = +0.0; for k = 0 .. K - 1 ascending: s = fma(theta_d[k], psi_j[k], s) -- one fused fp64 chain, no partial sums, no
+ *   reassociation.  For a one-item weight-1 query it is mvhdp_score_items' score(d, w) in every bit (the product commutes inside the fma).
+ * Order of the candidates for a query: score descending, equal scores by ascending entity id; compared by the monotone 64-bit pattern, as for
+ *   mvhdp_predict_items.  With the arguments admitted every score is finite and >= +0.0.
+ * Excluded for query j (item form with exclude_present != 0 only): an entity whose view-m span in the handle's corpus holds at least one
+ *   item of query j.  Excluded entities are never listed and never counted in a rank.
+ * mvhdp_predict_entities: per query the first min(n, candidates not excluded) entities in that order -- ids of this handle and their
+ *   scores; counts[j] says how many; unused slots hold id -1 and score 0.0.  1 <= n <= 1024; n > c1 - c0 is allowed.
+ * mvhdp_rank_entities: for pair i, score[i] = score(entity[i], query[i]), the same bits, and rank[i] = the number of candidates
+ *   d != entity[i] of [c0, c1) that are not excluded for that query and precede entity[i] in the order (0-based).  The queried entity is
+ *   scored and ranked even when it is itself excluded.  It must lie in [c0, c1), the query index in [0, nq).  Pairs may repeat and come in
+ *   any order; only queries that have pairs are computed.  Cost: n_pairs x (c1 - c0) comparisons, behind the scores of every candidate
+ *   for every query that has a pair.
+ * Preconditions: as mvhdp_predict_items (every view's corpus, the hyper-parameters, counts that are current), else MVHDP_ERR_STATE.
+ * MVHDP_ERR_INVALID_ARG, every output untouched: a NULL args or output; a bad view or candidate range; nq < 0; n outside 1..1024; a q_off
+ *   that does not start at 0 or decreases; a bad item, weight or psi entry; bad view weights; a negative block_entities or block_queries;
+ *   a bad pair.  -1 for a NULL handle.  MVHDP_ERR_UNSUPPORTED: 2^31 candidates or more.  nq == 0 or n_pairs == 0: MVHDP_OK, only stats
+ *   written.  c0 == c1: every count 0.  Pending work on the handle's stream lands first.
+ * On the device: queries in blocks of block_queries (0: 4096), candidates in blocks of block_entities (0: 8192, a query's row of keys then
+ *   fits the selection's 64 KiB of LDS; a longer row is selected from memory), the block of scores [queries][entities] within 256 MiB (the
+ *   knobs are cut to that).  The tiled fp64 kernel of mvhdp_predict_items computes the block with the roles swapped; one wave per query
+ *   merges the block's first n with the n carried from the blocks before.  The knobs change no result.  No floating-point atomics: two calls
+ *   with the same arguments return the same bytes (kernel_ms aside).  Nothing of the handle moves: the counts, the assignments, the
+ *   tuning and what mvhdp_counts_written / mvhdp_trees_current would report are what they were.
+ * stats (or NULL): cells = scores computed; excluded = (entity, query) cells marked; blocks = blocks of scores; kernel_ms = the stream's
+ *   time from the first kernel to the last.
+ * mvhdp_entities_args, in this order: int32 m, exclude_present; the view_weights pointer; int64 c0, c1, nq; the four host pointers q_off,
+ *   q_items, q_weights, psi; int64 block_entities, block_queries (88 bytes).  mvhdp_entities_stats: two int64, an int32, a double
+ *   (32 bytes with the padding behind blocks).  tests/test_xview_entities_kats.py pins both. */
+typedef struct { int32_t m; int32_t exclude_present; const double* view_weights /*[M]*/; int64_t c0, c1;      /* candidate entities [c0, c1) */
+                 int64_t nq; const int64_t* q_off /*[nq+1]*/; const int32_t* q_items; const double* q_weights /* or NULL: every weight 1.0 */;
+                 const double* psi /*[nq][K] host, or NULL*/; int64_t block_entities /*0: auto*/, block_queries /*0: auto*/; } mvhdp_entities_args;
+typedef struct { int64_t cells /* scores computed */, excluded /* (entity, query) cells marked */; int32_t blocks; double kernel_ms; } mvhdp_entities_stats;
+int mvhdp_predict_entities(mvhdp_handle h, const mvhdp_entities_args* a, int32_t n, int64_t* ids /*[nq][n]*/, double* scores /*[nq][n]*/,
+                           int32_t* counts /*[nq]*/, mvhdp_entities_stats* stats /* or NULL */);
+int mvhdp_rank_entities(mvhdp_handle h, const mvhdp_entities_args* a, int64_t n_pairs, const int64_t* query /*[n_pairs]*/, const int64_t* entity /*[n_pairs]*/,
+                        double* score /*[n_pairs]*/, int64_t* rank /*[n_pairs]*/);
+
 /* Nearest entities: for each of nq query rows the n entities of [c0, c1) of this handle with the largest cosine similarity.  The reference
  * only compares groups (its Java double loop, FLOW:1320-1532, cannot do more): THIS definition is ours; tests/nearest_numpy.py restates it.
  * It is pinned to the arithmetic of mvhdp_similar_pairs, so every value can be checked against that entry point bit for bit.

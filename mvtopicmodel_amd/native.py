@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   EmbConfigC, EmbStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
+                   EmbConfigC, EmbStatsC, EntitiesArgsC, EntitiesStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
@@ -200,6 +200,62 @@ def merge_nearest(results, n):
     stats = NearestStats(sum(x.cells_screened for x in st), sum(x.candidates for x in st), sum(x.exact_only_rows for x in st),
                          sum(x.blocks for x in st), sum(x.regrown for x in st), max(x.margin for x in st)) if st else None
     return NearestResult(ids, sims, counts, stats)
+
+
+@dataclass
+class EntitiesStats:
+    """mvhdp_entities_stats: cells = scores computed, excluded = (entity, query) cells marked, blocks = blocks of scores, kernel_ms = the
+    stream's time from the first kernel to the last."""
+    cells: int = 0
+    excluded: int = 0
+    blocks: int = 0
+    kernel_ms: float = 0.0
+
+
+@dataclass
+class EntityRanking:
+    """mvhdp_predict_entities: per query its first counts[j] candidate entities by (score descending, entity id ascending): ids [nq][n]
+    (-1 unfilled), scores [nq][n] (0.0 unfilled), counts [nq]."""
+    ids: np.ndarray
+    scores: np.ndarray
+    counts: np.ndarray
+    stats: EntitiesStats = None
+
+
+@dataclass
+class EntityRanks:
+    """mvhdp_rank_entities: per (query, entity) pair its score and the number of candidates that are not excluded and precede it."""
+    score: np.ndarray
+    rank: np.ndarray
+
+    def recall_at(self, n):
+        return float(np.mean(self.rank < n)) if len(self.rank) else float("nan")
+
+    def mrr(self):
+        return float(np.mean(1.0 / (self.rank + 1.0))) if len(self.rank) else float("nan")
+
+
+def merge_predicted_entities(results, n):
+    """The EntityRanking over the union of the candidate ranges from the results of its parts (document shards, or pieces of one range),
+    ids already in one numbering: per query the first n of all listed entries by (score descending, id ascending).  A score belongs to
+    its (entity, query) alone, so the merge is exact provided every part was asked for at least n.  No device."""
+    results = list(results)
+    n = int(n)
+    nq = len(results[0].counts)
+    if any(len(r.counts) != nq for r in results):
+        raise ValueError("merge_predicted_entities: the results disagree on the number of queries")
+    ids = np.full((nq, n), -1, dtype=np.int64)
+    scores = np.zeros((nq, n), dtype=np.float64)
+    counts = np.zeros(nq, dtype=np.int32)
+    for q in range(nq):
+        i = np.concatenate([r.ids[q, :r.counts[q]] for r in results])
+        v = np.concatenate([r.scores[q, :r.counts[q]] for r in results])
+        o = _first_n(v, i, n)
+        counts[q] = len(o)
+        ids[q, :len(o)], scores[q, :len(o)] = i[o], v[o]
+    st = [r.stats for r in results if r.stats is not None]
+    stats = EntitiesStats(sum(x.cells for x in st), sum(x.excluded for x in st), sum(x.blocks for x in st), sum(x.kernel_ms for x in st)) if st else None
+    return EntityRanking(ids, scores, counts, stats)
 
 
 def merge_topic_top_entities(parts, n):
@@ -816,6 +872,72 @@ class NativeSampler:
         self._ck(self.L.mvhdp_score_items(self.h, C.byref(a), d0, d1, len(ent), _ptr(ent), _ptr(it), _ptr(score), _ptr(rank)))
         return ItemScores(score, rank)
 
+    # -- entities for an item (include/mvhdp.h mvhdp_predict_entities / mvhdp_rank_entities) --
+    def _entities_args(self, m, view_weights, items, weights, psi, c0, c1, exclude_present, block_entities, block_queries):
+        w = np.ascontiguousarray(view_weights, dtype=np.float64)
+        if w.shape != (self.M,):
+            raise ValueError("view_weights must be [M]")
+        c1 = self.D if c1 is None else int(c1)
+        a = EntitiesArgsC(int(m), 1 if exclude_present else 0, w.ctypes.data, int(c0), c1, 0, None, None, None, None, int(block_entities), int(block_queries))
+        keep = [w]
+        if psi is not None:
+            if items is not None or weights is not None:
+                raise ValueError("either items (with weights) or psi")
+            x = np.ascontiguousarray(psi, dtype=np.float64)
+            if x.ndim != 2 or x.shape[1] != self.K:
+                raise ValueError("psi must be [nq][K]")
+            keep.append(x)
+            a.psi, a.nq = x.ctypes.data, x.shape[0]
+            return a, keep
+        if items is None:
+            raise ValueError("neither items nor psi")
+        one = isinstance(items, np.ndarray) and items.ndim == 1              # one item per query
+        lists = [[int(i)] for i in items] if one else [list(q) for q in items]
+        off = np.concatenate([[0], np.cumsum([len(q) for q in lists])]).astype(np.int64)
+        flat = np.ascontiguousarray([i for q in lists for i in q], dtype=np.int32)
+        keep += [off, flat]
+        a.nq, a.q_off, a.q_items = len(lists), off.ctypes.data, flat.ctypes.data if len(flat) else None
+        if weights is not None:
+            wl = [[float(x)] for x in weights] if one else [list(q) for q in weights]
+            if [len(q) for q in wl] != [len(q) for q in lists]:
+                raise ValueError("weights: one per item")
+            fw = np.ascontiguousarray([x for q in wl for x in q], dtype=np.float64)
+            keep.append(fw)
+            a.q_weights = fw.ctypes.data if len(fw) else None
+        return a, keep
+
+    def predict_entities(self, m, view_weights, n, items=None, weights=None, psi=None, c0=0, c1=None, exclude_present=True, block_entities=0, block_queries=0):
+        """Per query the first n (<= 1024) entities of [c0, c1) by score(d, j) = sum_k theta_d[k] psi_j[k], score descending, equal scores
+        by entity id: an EntityRanking.  Queries: `items`, a list of lists of types of view m (or a 1-D array: one item per query) with
+        optional `weights` of the same shape -- psi_j is the weighted sum of their phi rows -- or `psi`, rows [nq][K] of the caller's.
+        theta_d is doc_topic_proportions(view_weights), formed on the device; pass view_weights[m] = 0 to predict the view from the
+        others.  exclude_present (item form): an entity whose view-m span holds an item of the query is not listed.  For a one-item
+        query every score has the bits of score_items for the same (entity, item).  block_entities, block_queries: work sizes (0: auto)."""
+        a, keep = self._entities_args(m, view_weights, items, weights, psi, c0, c1, exclude_present, block_entities, block_queries)
+        n = int(n)
+        nq = int(a.nq)
+        ids = np.full((nq, max(n, 0)), -1, dtype=np.int64)
+        scores = np.zeros((nq, max(n, 0)), dtype=np.float64)
+        counts = np.zeros(nq, dtype=np.int32)
+        st = EntitiesStatsC()
+        self._ck(self.L.mvhdp_predict_entities(self.h, C.byref(a), n, _ptr(ids), _ptr(scores), _ptr(counts), C.byref(st)))
+        return EntityRanking(ids, scores, counts, EntitiesStats(st.cells, st.excluded, st.blocks, st.kernel_ms))
+
+    def rank_entities(self, m, view_weights, queries, entities, items=None, weights=None, psi=None, c0=0, c1=None, exclude_present=True,
+                      block_entities=0, block_queries=0):
+        """Score and rank given (query index, entity) pairs -- the held-back links of an evaluation from the item's side: an EntityRanks.
+        rank counts the candidates of [c0, c1) that are not excluded for the query and come before the entity (the entity itself is
+        ranked even if it is excluded).  Pairs may repeat and come in any order."""
+        a, keep = self._entities_args(m, view_weights, items, weights, psi, c0, c1, exclude_present, block_entities, block_queries)
+        qi = np.ascontiguousarray(queries, dtype=np.int64)
+        ent = np.ascontiguousarray(entities, dtype=np.int64)
+        if qi.ndim != 1 or qi.shape != ent.shape:
+            raise ValueError("queries and entities: two arrays of one length")
+        score = np.zeros(len(qi), dtype=np.float64)
+        rank = np.zeros(len(qi), dtype=np.int64)
+        self._ck(self.L.mvhdp_rank_entities(self.h, C.byref(a), len(qi), _ptr(qi), _ptr(ent), _ptr(score), _ptr(rank)))
+        return EntityRanks(score, rank)
+
     # -- retrieval (include/mvhdp.h mvhdp_nearest_entities / mvhdp_topic_top_entities) --
     def nearest_entities(self, view_weights, n, queries=None, q0=0, q1=None, c0=0, c1=None, exclude_self=True, min_weight=-np.inf,
                          block_queries=0, stripe_candidates=0, candidate_capacity=0):
@@ -1343,6 +1465,19 @@ class NativeGroup:
             r.ids[r.ids >= 0] += int(b)
             parts.append(r)
         return merge_nearest(parts, n)
+
+    def predict_entities(self, m, view_weights, n, items=None, weights=None, psi=None, exclude_present=True, **knobs):
+        """NativeSampler.predict_entities over the LOCAL members: the counts are replicated, so every member builds the same psi and
+        answers for its own entities; its ids are moved to the group's numbering (entity ids count through the members in their
+        order) and the lists are merged (merge_predicted_entities): per (entity, query) the values are a single handle's, bit for
+        bit.  (The carry-over of a missing view does not reach across a member's first entity.)"""
+        bases = np.concatenate([[0], np.cumsum([s.D for s in self.members])]).astype(np.int64)
+        parts = []
+        for s, b in zip(self.members, bases[:-1]):
+            r = s.predict_entities(m, view_weights, n, items=items, weights=weights, psi=psi, exclude_present=exclude_present, **knobs)
+            r.ids[r.ids >= 0] += int(b)
+            parts.append(r)
+        return merge_predicted_entities(parts, n)
 
     def topic_top_entities(self, view_weights, n, threshold=-np.inf, **knobs):
         """NativeSampler.topic_top_entities over the LOCAL members' entities, merged the same way (merge_topic_top_entities)."""
