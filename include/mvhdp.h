@@ -664,6 +664,60 @@ int mvhdp_topic_top_entities(mvhdp_handle h, const double* view_weights /*[M]*/,
                              int64_t chunk_entities /*0: auto*/, int64_t slice_entities /*0: auto*/,
                              int64_t* ids /*[K][n]*/, double* weights /*[K][n]*/, int32_t* counts /*[K]*/);
 
+/* The topic map: Gram sums and co-occurrence counts of every pair of topics over a tall matrix X with K columns -- which topics are
+ * near-duplicates by their word distributions (the question behind mergeSimilarTopics PTM:677-843 and CalcTopicSimilarities
+ * FLOW:1084-1196), which topics occur together in the same entities (the topic graph a front end draws).  The reference has no
+ * counterpart with a fixed order: THIS definition is ours; tests/native/gram_ref.c restates it.
+ * Rows X_r[k], r in [r0, r1), by args.source:
+ *   MVHDP_GRAM_ENTITIES: the bits of mvhdp_doc_topic_proportions(h, view_weights, r, r + 1), its missing-view carry-over included;
+ *     0 <= r0 <= r1 <= D; preconditions as that entry (every view's corpus, the hyper-parameters, else MVHDP_ERR_STATE); view_weights
+ *     finite, none negative, their sum > 0.  m is ignored.
+ *   MVHDP_GRAM_WORDS: phi[r][k] of view m exactly as mvhdp_predict_items defines it -- one correctly rounded division, exactly 0.0 for a
+ *     topic in inActiveTopicIndex; a vectors mix is NOT applied; 0 <= r0 <= r1 <= V_m.  The counts must be current and no NO_APPLY delta
+ *     pending, else MVHDP_ERR_STATE, as in that entry.
+ *   MVHDP_GRAM_HOST: the caller's rows x [r1 - r0][K], every entry finite and >= 0; 0 <= r0 <= r1.  The handle supplies the device and
+ *     the stream only (and K).
+ * Transform: y_r[k] = X_r[k] (MVHDP_GRAM_IDENTITY) or sqrt(X_r[k]), correctly rounded (MVHDP_GRAM_SQRT).  With SQRT over WORDS gram[k][l]
+ *   is the Bhattacharyya coefficient of two topics' word distributions (Hellinger = sqrt(1 - BC) on the host); with IDENTITY
+ *   gram[k][l] / sqrt(gram[k][k] * gram[l][l]) is their cosine; with IDENTITY over ENTITIES gram, sums and stats.rows give the Pearson
+ *   correlation of two topics across entities.
+ * Order.  All arithmetic is fp64 and every operation is rounded on its own except the fma named here.  Block b holds the rows
+ *   [r0 + b * B, min(r0 + (b + 1) * B, r1)), B = MVHDP_GRAM_BLOCK_ROWS.
+ *   Block partial: p = +0.0; for r ascending in the block: p = fma(y_r[k], y_r[l], p)  -- one fused chain, no partial sums inside a block.
+ *   gram[k][l]: g = +0.0; for b ascending: g = g + P_b[k][l].
+ *   sums[k]: the same two levels with plain adds: q = +0.0; q = q + y_r[k] inside a block; then the blocks ascending.
+ *   Why there are blocks: one chain over 10^6 rows is serial.  A partial per 1024 rows is the unit of parallelism, and its size is part of
+ *   the definition.  The result is symmetric in every bit, because the product commutes inside the fma.
+ *   blocks_per_pass: how many block partials live on the device at once; 0: as many as fit 256 MiB.  Either way a pass is cut so that its
+ *   rows fit 1 GiB.  It changes no result.
+ * Integers, both taken on X, before the transform, and the comparison is strict:
+ *   n_above[k] = #{r : X_r[k] > threshold};  co_above[k][l] = #{r : X_r[k] > threshold and X_r[l] > threshold}, so co_above[k][k] =
+ *   n_above[k].  A NaN threshold: MVHDP_ERR_INVALID_ARG; -inf counts every row, +inf none.  Either output may be NULL; with both NULL
+ *   that work is skipped.
+ * MVHDP_ERR_INVALID_ARG, every output untouched: a NULL args, gram or sums; a bad source, transform, m (WORDS) or range; a negative
+ *   blocks_per_pass; bad view weights (ENTITIES); a NULL x or a bad x entry (HOST).  -1 for a NULL handle.  MVHDP_ERR_UNSUPPORTED: more
+ *   than 2^40 rows.  r0 == r1: MVHDP_OK, all outputs zero, blocks == 0.  Pending work on the handle's stream lands first.  Nothing of
+ *   the handle moves: the counts, the assignments, the tuning and what mvhdp_counts_written / mvhdp_trees_current would report are what
+ *   they were.  No floating-point atomics: two calls with the same arguments give the same bytes (kernel_ms aside).
+ * On the device: per pass theta (or phi, or the caller's rows) is formed for blocks_per_pass blocks and stays there.  A workgroup owns one
+ *   block of rows and one tile of 64 x 128 cells (k, l), each thread 4 x 8 fp64 accumulators fed by vector fp64 fma from slabs of 16
+ *   rows in LDS -- the tile kernel of mvhdp_predict_items without its transposition, X being row-major over the topics; only tiles on and
+ *   above the diagonal run.  A small kernel then adds the pass's partials into gram and sums in ascending block order, one thread per
+ *   cell.  Counts: a ballot over 64 rows gives per topic a 64-bit mask of the rows above the threshold, a block is 16 such words per
+ *   topic, and co_above[k][l] grows by popcount(mask_k & mask_l) through integer atomics (integer adds commute, so they stay exact).
+ * stats (or NULL): rows = r1 - r0; blocks = blocks of rows; passes; kernel_ms = the stream's time from the first kernel to the last.
+ * mvhdp_topic_gram_args, in this order: int32 source, m, transform, blocks_per_pass; the pointers view_weights and x; int64 r0, r1; double
+ *   threshold (56 bytes).  mvhdp_topic_gram_stats: an int64, two int32, a double (24 bytes).  tests/test_gram_kats.py pins both. */
+#define MVHDP_GRAM_BLOCK_ROWS 1024
+typedef enum { MVHDP_GRAM_ENTITIES = 0, MVHDP_GRAM_WORDS = 1, MVHDP_GRAM_HOST = 2 } mvhdp_gram_source;
+typedef enum { MVHDP_GRAM_IDENTITY = 0, MVHDP_GRAM_SQRT = 1 } mvhdp_gram_transform;
+typedef struct { int32_t source, m, transform, blocks_per_pass /*0: auto*/;
+                 const double* view_weights /*[M], ENTITIES only*/; const double* x /*[r1-r0][K] host, HOST only*/;
+                 int64_t r0, r1; double threshold; } mvhdp_topic_gram_args;
+typedef struct { int64_t rows; int32_t blocks, passes; double kernel_ms; } mvhdp_topic_gram_stats;
+int mvhdp_topic_gram(mvhdp_handle h, const mvhdp_topic_gram_args* a, double* gram /*[K][K]*/, double* sums /*[K]*/,
+                     int64_t* n_above /*[K] or NULL*/, int64_t* co_above /*[K][K] or NULL*/, mvhdp_topic_gram_stats* stats /* or NULL */);
+
 /* ---- topic diagnostics: the step after training (FastQMVWVTopicModelDiagnostics, DIAG = MVTopicModel/FastQMVWVTopicModelDiagnostics.java;
  * SciTopicFlow builds it with N = 20 right after the save, whose saveExperiment / saveTopicsandExperiment call
  * calcDiscrWeightAcrossTopicsPerModality PTM:2181-2230 from PTM:1370 / PTM:1507 and getSortedWords PTM:1792-1811 per view).

@@ -18,6 +18,7 @@ ABI_SYMBOLS = [
     "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
     "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_fold_in", "mvhdp_predict_items", "mvhdp_score_items",
     "mvhdp_nearest_entities", "mvhdp_nearest_probe", "mvhdp_topic_top_entities", "mvhdp_predict_entities", "mvhdp_rank_entities",
+    "mvhdp_topic_gram",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
@@ -189,6 +190,15 @@ class EntitiesStatsC(C.Structure):
     _fields_ = [("cells", C.c_int64), ("excluded", C.c_int64), ("blocks", C.c_int32), ("kernel_ms", C.c_double)]
 
 
+class TopicGramArgsC(C.Structure):
+    _fields_ = [("source", C.c_int32), ("m", C.c_int32), ("transform", C.c_int32), ("blocks_per_pass", C.c_int32),
+                ("view_weights", C.c_void_p), ("x", C.c_void_p), ("r0", C.c_int64), ("r1", C.c_int64), ("threshold", C.c_double)]
+
+
+class TopicGramStatsC(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("blocks", C.c_int32), ("passes", C.c_int32), ("kernel_ms", C.c_double)]
+
+
 class NearestArgsC(C.Structure):
     _fields_ = [("view_weights", C.c_void_p), ("c0", C.c_int64), ("c1", C.c_int64), ("queries", C.c_void_p), ("nq", C.c_int64),
                 ("q0", C.c_int64), ("q1", C.c_int64), ("exclude_self", C.c_int32), ("n", C.c_int32), ("min_weight", C.c_double),
@@ -319,6 +329,7 @@ def load_library():
     L.mvhdp_score_items.argtypes = [vp, C.POINTER(PredictArgsC), i64, i64, i64, vp, vp, vp, vp]
     L.mvhdp_predict_entities.argtypes = [vp, C.POINTER(EntitiesArgsC), i32, vp, vp, vp, C.POINTER(EntitiesStatsC)]
     L.mvhdp_rank_entities.argtypes = [vp, C.POINTER(EntitiesArgsC), i64, vp, vp, vp, vp]
+    L.mvhdp_topic_gram.argtypes = [vp, C.POINTER(TopicGramArgsC), vp, vp, vp, vp, C.POINTER(TopicGramStatsC)]
     L.mvhdp_nearest_entities.argtypes = [vp, C.POINTER(NearestArgsC), vp, vp, vp, C.POINTER(NearestStatsC)]
     L.mvhdp_nearest_probe.argtypes = [i64, i64, i32, i32, i32, C.POINTER(NearestStatsC)]
     L.mvhdp_topic_top_entities.argtypes = [vp, vp, i64, i64, i32, C.c_double, i64, i64, vp, vp, vp]

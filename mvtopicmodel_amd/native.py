@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 import numpy as np
 
 from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
-                   EmbConfigC, EmbStatsC, EntitiesArgsC, EntitiesStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TuningC,
+                   EmbConfigC, EmbStatsC, EntitiesArgsC, EntitiesStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TopicGramArgsC, TopicGramStatsC, TuningC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
@@ -256,6 +256,113 @@ def merge_predicted_entities(results, n):
     st = [r.stats for r in results if r.stats is not None]
     stats = EntitiesStats(sum(x.cells for x in st), sum(x.excluded for x in st), sum(x.blocks for x in st), sum(x.kernel_ms for x in st)) if st else None
     return EntityRanking(ids, scores, counts, stats)
+
+
+@dataclass
+class TopicGramStats:
+    """mvhdp_topic_gram_stats: rows = r1 - r0, blocks = blocks of MVHDP_GRAM_BLOCK_ROWS rows, passes = passes of blocks_per_pass blocks,
+    kernel_ms = the stream's time from the first kernel to the last."""
+    rows: int = 0
+    blocks: int = 0
+    passes: int = 0
+    kernel_ms: float = 0.0
+
+
+@dataclass
+class TopicGram:
+    """mvhdp_topic_gram: gram [K][K] = sum_r y_r[k] y_r[l] and sums [K] = sum_r y_r[k] in the contract's fixed order (y = X or sqrt(X) by
+    `transform`), n_above [K] and co_above [K][K] the exact counts of rows with X > threshold (None when no threshold was given), rows =
+    the number of rows.  The methods below are HOST derivations by numpy: convenient, not pinned to bits."""
+    gram: np.ndarray
+    sums: np.ndarray
+    n_above: np.ndarray
+    co_above: np.ndarray
+    rows: int
+    transform: str
+    stats: TopicGramStats = None
+
+    def _need(self, transform, what):
+        if self.transform != transform:
+            raise ValueError(f"{what} needs transform={transform!r}")
+
+    def _need_counts(self, what):
+        if self.n_above is None or self.co_above is None:
+            raise ValueError(f"{what} needs a threshold")
+
+    def cosine(self):
+        """gram[k][l] / sqrt(gram[k][k] gram[l][l]) (identity transform); NaN where a column is all zero.  A host derivation, not pinned
+        to bits."""
+        self._need("identity", "cosine")
+        d = np.sqrt(np.diag(self.gram))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.gram / np.outer(d, d)
+
+    def correlation(self):
+        """Pearson correlation of two columns across the rows, from gram, sums and rows (identity transform); NaN for a constant column.
+        A host derivation, not pinned to bits."""
+        self._need("identity", "correlation")
+        n = float(self.rows)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            cov = self.gram / n - np.outer(self.sums, self.sums) / (n * n)
+            d = np.sqrt(np.diag(cov))
+            return cov / np.outer(d, d)
+
+    def bhattacharyya(self):
+        """sum_r sqrt(X_r[k] X_r[l]) = the gram of the sqrt transform, each cell divided by sqrt(S_k S_l), S_k = gram[k][k] = the column's
+        sum of X: columns that are distributions (phi over a whole view) have S_k = 1 up to rounding.  A host derivation, not pinned to bits."""
+        self._need("sqrt", "bhattacharyya")
+        d = np.sqrt(np.diag(self.gram))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return self.gram / np.outer(d, d)
+
+    def hellinger(self):
+        """sqrt(1 - bhattacharyya()), clipped at 0.  A host derivation, not pinned to bits."""
+        return np.sqrt(np.clip(1.0 - self.bhattacharyya(), 0.0, None))
+
+    def jaccard(self):
+        """co_above / (n_above[k] + n_above[l] - co_above); NaN where neither column has a row above.  A host derivation."""
+        self._need_counts("jaccard")
+        co = self.co_above.astype(np.float64)
+        n = self.n_above.astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return co / (n[:, None] + n[None, :] - co)
+
+    def npmi(self):
+        """Normalised pointwise mutual information of 'above the threshold' across the rows: log(p_kl / (p_k p_l)) / -log(p_kl); -1 where
+        two topics never meet, NaN where a topic has no row above.  A host derivation, not pinned to bits."""
+        self._need_counts("npmi")
+        n = float(self.rows)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            pkl = self.co_above / n
+            pk = self.n_above / n
+            out = np.log(pkl / np.outer(pk, pk)) / -np.log(pkl)
+            out[(self.co_above == 0) & (np.outer(self.n_above, self.n_above) > 0)] = -1.0
+        return out
+
+
+def merge_topic_grams(parts):
+    """The TopicGram over the union of the rows of its parts (document shards, or pieces of one range): the integers are added exactly;
+    gram and sums are added in list order, cell by cell in fp64 -- the list-order sum of the parts' results, not the bits a single call
+    over all the rows would give.  No device."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_topic_grams: no parts")
+    if any(p.transform != parts[0].transform or p.gram.shape != parts[0].gram.shape for p in parts):
+        raise ValueError("merge_topic_grams: the parts disagree on the transform or on K")
+    if any((p.n_above is None) != (parts[0].n_above is None) for p in parts):
+        raise ValueError("merge_topic_grams: some parts have counts and some do not")
+    gram = np.zeros_like(parts[0].gram)
+    sums = np.zeros_like(parts[0].sums)
+    for p in parts:
+        gram = gram + p.gram
+        sums = sums + p.sums
+    n_above = co_above = None
+    if parts[0].n_above is not None:
+        n_above = np.sum([p.n_above for p in parts], axis=0, dtype=np.int64)
+        co_above = np.sum([p.co_above for p in parts], axis=0, dtype=np.int64)
+    st = [p.stats for p in parts if p.stats is not None]
+    stats = TopicGramStats(sum(x.rows for x in st), sum(x.blocks for x in st), sum(x.passes for x in st), sum(x.kernel_ms for x in st)) if st else None
+    return TopicGram(gram, sums, n_above, co_above, sum(int(p.rows) for p in parts), parts[0].transform, stats)
 
 
 def merge_topic_top_entities(parts, n):
@@ -983,6 +1090,51 @@ class NativeSampler:
                                                  _ptr(ids), _ptr(weights), _ptr(counts)))
         return ids, weights, counts
 
+    # -- the topic map (include/mvhdp.h mvhdp_topic_gram) --
+    def topic_gram(self, source, m=0, view_weights=None, r0=0, r1=None, transform="identity", threshold=None, blocks_per_pass=0):
+        """K x K sums over the rows of `source`: "entities" (theta of the entities [r0, r1), doc_topic_proportions(view_weights), formed
+        on the device), "words" (phi of view m over the types [r0, r1)) or an ndarray [n][K] of the caller's (finite, >= 0; r0 and r1
+        cut it).  transform "identity" or "sqrt".  A TopicGram: gram and sums in the contract's fixed order (blocks of 1024 rows, one fma
+        chain per block and cell, the blocks added in ascending order), and with a `threshold` the exact counts n_above and co_above of
+        the rows with X > threshold (strictly; taken before the transform).  blocks_per_pass: a work size (0: auto); it changes no result."""
+        srcs = {"entities": 0, "words": 1}
+        tr = {"identity": 0, "sqrt": 1}
+        if transform not in tr:
+            raise ValueError('transform must be "identity" or "sqrt"')
+        keep = []
+        a = TopicGramArgsC(0, int(m), tr[transform], int(blocks_per_pass), None, None, int(r0), 0, 0.0 if threshold is None else float(threshold))
+        if isinstance(source, str):
+            if source not in srcs:
+                raise ValueError('source must be "entities", "words" or an array [n][K]')
+            a.source = srcs[source]
+            a.r1 = (self.D if source == "entities" else int(self.V[int(m)])) if r1 is None else int(r1)
+            if source == "entities":
+                w = np.ascontiguousarray(view_weights, dtype=np.float64)
+                if w.shape != (self.M,):
+                    raise ValueError("view_weights must be [M]")
+                keep.append(w)
+                a.view_weights = w.ctypes.data
+        else:
+            x = np.ascontiguousarray(source, dtype=np.float64)
+            if x.ndim != 2 or x.shape[1] != self.K:
+                raise ValueError("source rows must be [n][K]")
+            r1 = x.shape[0] if r1 is None else int(r1)
+            if not 0 <= int(r0) <= r1 <= x.shape[0]:
+                raise ValueError("bad row range")
+            x = np.ascontiguousarray(x[int(r0):r1]) if r1 > int(r0) else np.zeros((1, self.K))
+            keep.append(x)
+            a.source, a.x, a.r1 = 2, x.ctypes.data, r1
+        gram = np.zeros((self.K, self.K), dtype=np.float64)
+        sums = np.zeros(self.K, dtype=np.float64)
+        n_above = co_above = None
+        if threshold is not None:
+            n_above = np.zeros(self.K, dtype=np.int64)
+            co_above = np.zeros((self.K, self.K), dtype=np.int64)
+        st = TopicGramStatsC()
+        self._ck(self.L.mvhdp_topic_gram(self.h, C.byref(a), _ptr(gram), _ptr(sums), None if n_above is None else _ptr(n_above),
+                                         None if co_above is None else _ptr(co_above), C.byref(st)))
+        return TopicGram(gram, sums, n_above, co_above, int(st.rows), transform, TopicGramStats(st.rows, st.blocks, st.passes, st.kernel_ms))
+
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
     def top_words(self, m, n):
         """getSortedWords(m) PTM:1792-1811 cut at n: (types [K][n] (-1 unfilled), counts [K][n], nonzero [K])."""
@@ -1488,6 +1640,16 @@ class NativeGroup:
             ids[ids >= 0] += int(b)
             parts.append((ids, weights, counts))
         return merge_topic_top_entities(parts, n)
+
+    def topic_gram(self, source, m=0, view_weights=None, transform="identity", threshold=None, blocks_per_pass=0):
+        """NativeSampler.topic_gram over the LOCAL members.  "words" and host rows go to the first member: the counts are replicated.
+        "entities" runs on every member over its own entities and the results are merged in member order (merge_topic_grams): the
+        integers n_above and co_above equal a single handle's; gram and sums are the member-order sum of the members' results, NOT a
+        single handle's bits.  (The carry-over of a missing view does not reach across a member's first entity.)"""
+        if not (isinstance(source, str) and source == "entities"):
+            return self.members[0].topic_gram(source, m=m, view_weights=view_weights, transform=transform, threshold=threshold, blocks_per_pass=blocks_per_pass)
+        return merge_topic_grams([s.topic_gram("entities", view_weights=view_weights, transform=transform, threshold=threshold, blocks_per_pass=blocks_per_pass)
+                                  for s in self.members])
 
     def sweep(self, sweep_idx, seed, flags=0):
         """One sweep of the whole model; the list of the local members' statistics."""
