@@ -778,6 +778,57 @@ int mvhdp_discr_weights(mvhdp_handle h, double* per_view /*[M]*/, int32_t m, dou
  * MVHDP_ERR_STATE, outputs untouched. */
 int mvhdp_diagnostics(mvhdp_handle h, const mvhdp_diag_args* args, mvhdp_diag_out* out);
 
+/* ---- topic words per cohort: what a topic looks like inside a set of entities -- its words in the papers of one year, its tags and cited
+ * papers (views 1 and 2) at one venue, its vocabulary in one author's work.  The counterpart in token units of the "Trends" of
+ * CalcEntityTopicDistributionsAndTrends (FLOW:807-1083, mvhdp_entity_topic_distributions); the definition is ours.
+ * A cohort is a list of entity ids, in the CSR form of mvhdp_entity_topic_distributions: cohort g lists members[member_off[g] ..
+ *   member_off[g + 1]).  An entity may be listed in several cohorts and more than once in one cohort; every listing counts.
+ * What is read: tokens, z and doc_off of view m as the handle holds them -- the rule of mvhdp_topic_phrases: whatever the last sweep left on
+ *   the device, live or deferred.  An entity without view m is an empty span.  Only listed entities are read.
+ * A token is counted when 0 <= type < V_m and 0 <= z < K.  A token with z == -1 or type >= V_m is skipped; stats.skipped counts the skipped
+ *   tokens once per listing.  A z outside [-1, K) or a negative type in a listed entity: MVHDP_ERR_STATE.
+ * Per cohort g and topic k:
+ *   c_g[w][k]     = the counted tokens of type w and topic k, summed over the listings of g;
+ *   tokens[g][k]  = sum_w c_g[w][k] (the trend in token units);
+ *   docs[g][k]    = the listings of g whose entity holds at least one counted token of topic k in view m;
+ *   nonzero[g][k] = the types with c_g[w][k] >= 1.
+ * The list of (g, k): the types with c_g[w][k] >= min_count in the chosen order, cut at n; unfilled slots hold -1 / 0, as in
+ *   mvhdp_top_words.
+ *   MVHDP_COHORT_BY_COUNT: count descending, equal counts by descending type id (IDSorter.compareTo, the order of mvhdp_top_words).
+ *   MVHDP_COHORT_BY_SHARE: by the exact rational c_g[w][k] / n_wk[m][w][k] descending -- the part of the word's topic-k tokens that lies in
+ *     the cohort -- compared by 64-bit cross products, never by a floating-point quotient; equal shares by count descending, then by
+ *     descending type id.  BY_COUNT returns mostly a topic's head words in every cohort; the share order shows a cohort's own vocabulary,
+ *     and min_count keeps singletons out of it.
+ * Preconditions: a corpus of view m (else MVHDP_ERR_STATE); BY_COUNT needs nothing else, no counts and no hyper-parameters.  BY_SHARE also
+ *   needs current counts and no pending MVHDP_SWEEP_NO_APPLY delta, the rule of mvhdp_top_words, else MVHDP_ERR_STATE.
+ * MVHDP_ERR_INVALID_ARG: a NULL args or member_off; m out of range; n outside 1..MVHDP_DIAG_MAX_TOP_WORDS; min_count < 1; scratch_bytes < 0;
+ *   an order that is neither value; one of types / counts NULL and the other not; n_cohorts < 0; member_off[0] != 0 or member_off
+ *   decreasing; a member outside [0, D); the listings of one cohort holding more than 2^31 - 1 tokens of view m, counted or not (summed on
+ *   the host from the spans' lengths before any device work: a count cell cannot overflow).  -1 for a NULL handle.
+ *   MVHDP_ERR_UNSUPPORTED: more than 16384 topics.  n_cohorts == 0 (after these checks): MVHDP_OK.  Every output is untouched on any error.
+ * scratch_bytes bounds the device scratch of the count tables, one [K][V_m] int32 table per cohort of a pass; 0: 1 GiB.  A value smaller
+ *   than one table means one cohort per pass, never an error.  It changes no result.
+ * Guarantees: integers only, so two calls with the same arguments return the same bytes (kernel_ms aside); a cohort's result does not
+ *   depend on which other cohorts share the call; nothing of the handle moves: the counts, the assignments, the tuning and what
+ *   mvhdp_counts_written / mvhdp_trees_current would report are what they were.  Pending work on the handle's stream lands first.  With
+ *   types, counts and nonzero all NULL only the trends (tokens, docs) are computed and no count table is needed.
+ * Cost: one pass over the listed tokens (8 bytes read per token, an int32 atomic into the table, one atomic each into tokens and docs per
+ *   listing and topic seen), plus per cohort one clear and one scan of a K x V_m int32 table: 8 K V_m bytes per cohort.
+ * On the device: one wave per listing, lanes over the span's tokens; the table is topic-major, so the selection -- one block per cohort and
+ *   topic, the sorted top-n list of mvhdp_top_words per wave -- reads a topic's column contiguously, and BY_SHARE reads n_wk only for
+ *   the types that reach min_count.  Outputs are staged and copied out once, after the whole call has succeeded.
+ * stats (or NULL): listings = member_off[n_cohorts]; tokens = the counted tokens over all listings; skipped; passes; cohorts_per_pass;
+ *   kernel_ms = the stream's time from the first kernel to the last.
+ * mvhdp_cohort_args, in this order: int32 m, n, order, min_count; int64 scratch_bytes (24 bytes).  mvhdp_cohort_stats: int64 listings,
+ *   tokens, skipped; int32 passes, cohorts_per_pass; double kernel_ms (40 bytes).  tests/test_cohort_kats.py pins both. */
+typedef enum { MVHDP_COHORT_BY_COUNT = 0, MVHDP_COHORT_BY_SHARE = 1 } mvhdp_cohort_order;
+typedef struct { int32_t m, n, order, min_count; int64_t scratch_bytes /*0: auto*/; } mvhdp_cohort_args;
+typedef struct { int64_t listings, tokens, skipped; int32_t passes, cohorts_per_pass; double kernel_ms; } mvhdp_cohort_stats;
+int mvhdp_cohort_top_words(mvhdp_handle h, const mvhdp_cohort_args* a, int64_t n_cohorts, const int64_t* member_off /*[n_cohorts+1]*/,
+                           const int64_t* members, int32_t* types /*[G][K][n] or NULL*/, int32_t* counts /*[G][K][n] or NULL*/,
+                           int32_t* nonzero /*[G][K] or NULL*/, int64_t* tokens /*[G][K] or NULL*/, int64_t* docs /*[G][K] or NULL*/,
+                           mvhdp_cohort_stats* stats /* or NULL */);
+
 /* ---- word and topic embeddings: trainTypeVectors (PTM:517-524, 1186-1206, 1495-1498) and SciTopicFlow.runWordEmbeddings (FLOW:115-136).
  * TWE = MVTopicModel/TopicWordEmbeddings.java, TWER = MVTopicModel/TopicWordEmbeddingRunnable.java.  WordEmbeddings is TWE with no
  * topics and no context columns: the same trainer with with_topics = 0 (a WordEmbeddings host makes a K = 1, M = 1 handle over its

@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
     "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_fold_in", "mvhdp_predict_items", "mvhdp_score_items",
     "mvhdp_nearest_entities", "mvhdp_nearest_probe", "mvhdp_topic_top_entities", "mvhdp_predict_entities", "mvhdp_rank_entities",
-    "mvhdp_topic_gram",
+    "mvhdp_topic_gram", "mvhdp_cohort_top_words",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
@@ -199,6 +199,18 @@ class TopicGramStatsC(C.Structure):
     _fields_ = [("rows", C.c_int64), ("blocks", C.c_int32), ("passes", C.c_int32), ("kernel_ms", C.c_double)]
 
 
+COHORT_BY_COUNT, COHORT_BY_SHARE = 0, 1             # mvhdp_cohort_order
+
+
+class CohortArgsC(C.Structure):
+    _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("order", C.c_int32), ("min_count", C.c_int32), ("scratch_bytes", C.c_int64)]
+
+
+class CohortStatsC(C.Structure):
+    _fields_ = [("listings", C.c_int64), ("tokens", C.c_int64), ("skipped", C.c_int64), ("passes", C.c_int32),
+                ("cohorts_per_pass", C.c_int32), ("kernel_ms", C.c_double)]
+
+
 class NearestArgsC(C.Structure):
     _fields_ = [("view_weights", C.c_void_p), ("c0", C.c_int64), ("c1", C.c_int64), ("queries", C.c_void_p), ("nq", C.c_int64),
                 ("q0", C.c_int64), ("q1", C.c_int64), ("exclude_self", C.c_int32), ("n", C.c_int32), ("min_weight", C.c_double),
@@ -330,6 +342,7 @@ def load_library():
     L.mvhdp_predict_entities.argtypes = [vp, C.POINTER(EntitiesArgsC), i32, vp, vp, vp, C.POINTER(EntitiesStatsC)]
     L.mvhdp_rank_entities.argtypes = [vp, C.POINTER(EntitiesArgsC), i64, vp, vp, vp, vp]
     L.mvhdp_topic_gram.argtypes = [vp, C.POINTER(TopicGramArgsC), vp, vp, vp, vp, C.POINTER(TopicGramStatsC)]
+    L.mvhdp_cohort_top_words.argtypes = [vp, C.POINTER(CohortArgsC), i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CohortStatsC)]
     L.mvhdp_nearest_entities.argtypes = [vp, C.POINTER(NearestArgsC), vp, vp, vp, C.POINTER(NearestStatsC)]
     L.mvhdp_nearest_probe.argtypes = [i64, i64, i32, i32, i32, C.POINTER(NearestStatsC)]
     L.mvhdp_topic_top_entities.argtypes = [vp, vp, i64, i64, i32, C.c_double, i64, i64, vp, vp, vp]

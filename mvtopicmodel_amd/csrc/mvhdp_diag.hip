@@ -66,22 +66,7 @@ __global__ __launch_bounds__(256) void diag_rows_kernel(const int32_t* __restric
 // ---------------------------------------------------------------------------------------------------------------
 // Top n of one topic's column (IDSorter order: count descending, equal counts by descending type id).  A key (count << 32 | type)
 // orders exactly so; every lane of a wave holds one entry of the wave's sorted list (lane i: the i-th largest so far), a key enters
-// only when it beats the n-th, by one ballot and one shuffle.  The four waves' lists are merged by wave 0.
-__device__ __forceinline__ void topn_offer(unsigned long long& list, unsigned long long& thr, unsigned long long key, int n, int lane)
-{
-    unsigned long long cand = ballot(key > thr);
-    while (cand) {
-        const int j = __ffsll((long long)cand) - 1;
-        const unsigned long long x = __shfl(key, j, WAVE);
-        const int pos = __popcll(ballot(list > x));
-        const unsigned long long up = __shfl_up(list, 1, WAVE);
-        if (lane == pos) list = x; else if (lane > pos) list = up;
-        thr = __shfl(list, n - 1, WAVE);
-        cand &= (j == 63) ? 0ull : ~((2ull << j) - 1);
-        cand &= ballot(key > thr);
-    }
-}
-
+// only when it beats the n-th, by one ballot and one shuffle (topn_offer, mvhdp_select.h).  The four waves' lists are merged by wave 0.
 __global__ __launch_bounds__(256) void diag_topn_kernel(const int32_t* __restrict__ nkw, int V, int n, int32_t* __restrict__ types,
                                                         int32_t* __restrict__ counts, int32_t* __restrict__ nonzero)
 {
@@ -96,7 +81,7 @@ __global__ __launch_bounds__(256) void diag_topn_kernel(const int32_t* __restric
         const int w = base + lane;
         unsigned long long key = 0;
         if (w < e) { const int c = col[w]; if (c > 0) { nz++; key = ((unsigned long long)(uint32_t)c << 32) | (uint32_t)w; } }
-        if (__builtin_amdgcn_ballot_w64(key > thr)) topn_offer(list, thr, key, n, lane);
+        if (__builtin_amdgcn_ballot_w64(key > thr)) topn_offer(list, thr, key, n, lane, KeyDescending());
     }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) nz += __shfl_xor(nz, o, WAVE);
@@ -104,7 +89,7 @@ __global__ __launch_bounds__(256) void diag_topn_kernel(const int32_t* __restric
     if (lane == 0) nzs[wave] = nz;
     __syncthreads();
     if (wave != 0) return;
-    for (int w2 = 1; w2 < 4; w2++) topn_offer(list, thr, lists[w2][lane], n, lane);
+    for (int w2 = 1; w2 < 4; w2++) topn_offer(list, thr, lists[w2][lane], n, lane, KeyDescending());
     if (lane < n) {
         types[(int64_t)k * n + lane] = list ? (int32_t)(uint32_t)list : -1;              // unfilled slots: -1 / 0
         counts[(int64_t)k * n + lane] = (int32_t)(list >> 32);

@@ -1,5 +1,5 @@
 // mvhdp_select.h — wave-level (64-lane) device helpers of the kernels that count, compact and select: ballots, appends, order-preserving
-// keys and the bitwise descent to the n-th largest key.  Integers only; every function keeps the wave's control flow uniform.
+// keys, the sorted top-n list and the bitwise descent to the n-th largest key.  Integers only; every function keeps the wave's control flow uniform.
 #pragma once
 #include "mvhdp_wave.h"
 
@@ -30,6 +30,30 @@ __device__ __forceinline__ float f32_unkey(uint32_t k) { return __uint_as_float(
 __device__ __forceinline__ u64 f64_bits_key(u64 b) { return (b >> 63) ? ~b : b | (1ull << 63); }   // of a double held as its bits
 __device__ __forceinline__ u64 f64_key(double v) { return f64_bits_key((u64)__double_as_longlong(v)); }
 __device__ __forceinline__ double f64_unkey(u64 k) { return __longlong_as_double((long long)((k >> 63) ? k ^ (1ull << 63) : ~k)); }
+
+// The sorted top-n list of a wave: lane i holds the i-th entry so far (n <= 64; the lanes from n on hold the list's tail, which nothing
+// reads).  topn_offer enters the lanes' keys that come before the n-th entry `thr`, one per turn: a ballot finds the place, a shuffle
+// makes the room.  before(a, b) is a strict total order on the real entries, with the empty entry after every real one and not before
+// itself; an entry type of a kernel's own brings its lane_get / lane_up1 along.  Wave-uniform control flow.
+__device__ __forceinline__ u64 lane_get(const u64& v, int j) { return __shfl(v, j, WAVE); }
+__device__ __forceinline__ u64 lane_up1(const u64& v) { return __shfl_up(v, 1, WAVE); }
+struct KeyDescending { __device__ __forceinline__ bool operator()(u64 a, u64 b) const { return a > b; } };   // u64 keys, larger first; 0 is the empty entry
+
+template <class E, class Before>
+__device__ __forceinline__ void topn_offer(E& list, E& thr, E key, int n, int lane, Before before)
+{
+    u64 cand = ballot(before(key, thr));
+    while (cand) {
+        const int j = __ffsll((long long)cand) - 1;
+        const E x = lane_get(key, j);
+        const int pos = __popcll(ballot(before(list, x)));
+        const E up = lane_up1(list);
+        if (lane == pos) list = x; else if (lane > pos) list = up;
+        thr = lane_get(list, n - 1);
+        cand &= (j == 63) ? 0ull : ~((2ull << j) - 1);
+        cand &= ballot(before(key, thr));
+    }
+}
 
 // The bitwise descent: bits top_bit .. 0 of T, from the top, are set wherever reach(T | bit) holds.  With reach(t) = "at least n keys
 // are >= t" (wave-uniform) and those bits of T clear, this is the largest such value that at least n keys reach: the n-th largest key.

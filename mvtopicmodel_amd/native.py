@@ -11,7 +11,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
+from ._lib import (COHORT_BY_COUNT, COHORT_BY_SHARE, CohortArgsC, CohortStatsC, DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
                    EmbConfigC, EmbStatsC, EntitiesArgsC, EntitiesStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TopicGramArgsC, TopicGramStatsC, TuningC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
@@ -363,6 +363,59 @@ def merge_topic_grams(parts):
     st = [p.stats for p in parts if p.stats is not None]
     stats = TopicGramStats(sum(x.rows for x in st), sum(x.blocks for x in st), sum(x.passes for x in st), sum(x.kernel_ms for x in st)) if st else None
     return TopicGram(gram, sums, n_above, co_above, sum(int(p.rows) for p in parts), parts[0].transform, stats)
+
+
+def _member_csr(groups):
+    """(member_off [G+1], members) as int64 from a list of entity-id lists, or from the pair itself"""
+    if isinstance(groups, tuple):
+        moff = np.ascontiguousarray(groups[0], dtype=np.int64)
+        mem = np.ascontiguousarray(groups[1], dtype=np.int64)
+    else:
+        moff = np.zeros(len(groups) + 1, dtype=np.int64)
+        moff[1:] = np.cumsum([len(g) for g in groups])
+        mem = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.int64) for g in groups]) if len(groups) else [], dtype=np.int64)
+    if moff.ndim != 1 or len(moff) < 1 or len(mem) != int(moff[-1]):
+        raise ValueError("member_off / members shape mismatch")
+    return moff, mem
+
+
+@dataclass
+class CohortStats:
+    """mvhdp_cohort_stats: listings = member_off[n_cohorts], tokens = the counted tokens over all listings, skipped = the skipped ones
+    (z == -1 or out of the vocabulary), once per listing; passes of cohorts_per_pass cohorts; kernel_ms = the stream's time from the
+    first kernel to the last."""
+    listings: int = 0
+    tokens: int = 0
+    skipped: int = 0
+    passes: int = 0
+    cohorts_per_pass: int = 0
+    kernel_ms: float = 0.0
+
+
+@dataclass
+class CohortWords:
+    """mvhdp_cohort_top_words: per cohort g and topic k the top types [G][K][n] (-1 unfilled) with their counts inside the cohort
+    [G][K][n], nonzero [G][K] = the types with a count, tokens [G][K] = the cohort's tokens of the topic, docs [G][K] = the listings that
+    hold the topic.  types, counts and nonzero are None for a trends-only call."""
+    types: np.ndarray
+    counts: np.ndarray
+    nonzero: np.ndarray
+    tokens: np.ndarray
+    docs: np.ndarray
+    stats: CohortStats = None
+
+    def trend(self):
+        """tokens normalised per cohort: [G][K] rows that sum to 1 (a row of zeros for a cohort without counted tokens).
+        A host derivation by numpy, not pinned to bits."""
+        t = self.tokens.astype(np.float64)
+        tot = t.sum(axis=1, keepdims=True)
+        return np.divide(t, tot, out=np.zeros_like(t), where=tot > 0)
+
+    def words(self, g, k, vocabulary=None):
+        """The list of cohort g and topic k as [(type id or vocabulary[type], count)], the unfilled slots dropped.  A host derivation."""
+        if self.types is None:
+            raise ValueError("words needs a call that was not trends-only")
+        return [(int(t) if vocabulary is None else vocabulary[int(t)], int(c)) for t, c in zip(self.types[g, k], self.counts[g, k]) if t >= 0]
 
 
 def merge_topic_top_entities(parts, n):
@@ -798,15 +851,7 @@ class NativeSampler:
         w = np.ascontiguousarray(view_weights, dtype=np.float64)
         if w.shape != (self.M,):
             raise ValueError("view_weights must be [M]")
-        if isinstance(groups, tuple):
-            moff = np.ascontiguousarray(groups[0], dtype=np.int64)
-            mem = np.ascontiguousarray(groups[1], dtype=np.int64)
-        else:
-            moff = np.zeros(len(groups) + 1, dtype=np.int64)
-            moff[1:] = np.cumsum([len(g) for g in groups])
-            mem = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.int64) for g in groups]) if len(groups) else [], dtype=np.int64)
-        if moff.ndim != 1 or len(moff) < 1 or len(mem) != int(moff[-1]):
-            raise ValueError("member_off / members shape mismatch")
+        moff, mem = _member_csr(groups)
         ng = len(moff) - 1
         out = np.zeros((ng, self.K), dtype=np.float64)
         self._ck(self.L.mvhdp_entity_topic_distributions(self.h, _ptr(w), float(threshold), int(max_topics), int(round_digits), ng, _ptr(moff),
@@ -1134,6 +1179,32 @@ class NativeSampler:
         self._ck(self.L.mvhdp_topic_gram(self.h, C.byref(a), _ptr(gram), _ptr(sums), None if n_above is None else _ptr(n_above),
                                          None if co_above is None else _ptr(co_above), C.byref(st)))
         return TopicGram(gram, sums, n_above, co_above, int(st.rows), transform, TopicGramStats(st.rows, st.blocks, st.passes, st.kernel_ms))
+
+    # -- topic words per cohort (include/mvhdp.h mvhdp_cohort_top_words) --
+    def cohort_top_words(self, m, cohorts, n=20, order="count", min_count=1, trends_only=False, scratch_bytes=0):
+        """A topic's words inside sets of entities: cohorts is a list of entity-id lists (or (member_off, members)), as the groups of
+        entity_topic_distributions; an entity may be listed in several cohorts and more than once, every listing counts.  A CohortWords:
+        per cohort and topic the top n types of view m by their count inside the cohort (order "count", the order of top_words) or by
+        the exact share of the word's topic tokens that lies in the cohort (order "share"; needs current counts), among the types with
+        at least min_count tokens there; tokens and docs are the trend in token and in listing units.  trends_only: tokens and docs
+        alone, without a count table.  scratch_bytes bounds the device scratch of the count tables (0: auto); it changes no result."""
+        orders = {"count": COHORT_BY_COUNT, "share": COHORT_BY_SHARE}
+        if order not in orders:
+            raise ValueError('order must be "count" or "share"')
+        moff, mem = _member_csr(cohorts)
+        G, n = len(moff) - 1, int(n)
+        a = CohortArgsC(int(m), n, orders[order], int(min_count), int(scratch_bytes))
+        types = counts = nonzero = None
+        if not trends_only:
+            types = np.full((G, self.K, max(n, 1)), -1, dtype=np.int32)
+            counts = np.zeros((G, self.K, max(n, 1)), dtype=np.int32)
+            nonzero = np.zeros((G, self.K), dtype=np.int32)
+        tokens = np.zeros((G, self.K), dtype=np.int64)
+        docs = np.zeros((G, self.K), dtype=np.int64)
+        st = CohortStatsC()
+        self._ck(self.L.mvhdp_cohort_top_words(self.h, C.byref(a), G, _ptr(moff), _ptr(mem) if len(mem) else None, _ptr(types), _ptr(counts),
+                                               _ptr(nonzero), _ptr(tokens), _ptr(docs), C.byref(st)))
+        return CohortWords(types, counts, nonzero, tokens, docs, CohortStats(**{f: getattr(st, f) for f, _ in CohortStatsC._fields_}))
 
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
     def top_words(self, m, n):
