@@ -2,7 +2,7 @@
 // Owns the device state of one model shard (one HIP device), launches the
 // kernels of mvhdp_kernels.hip on one stream and copies results back.
 // There is NO CPU fallback: without a gfx950 device mvhdp_create fails.
-#include "mvhdp_ctx.h"
+#include "mvhdp_side.h"                      // check_offsets (set_corpus)
 
 static thread_local std::string g_create_error;
 
@@ -288,12 +288,7 @@ extern "C" int mvhdp_set_corpus(mvhdp_handle h, int32_t m, int64_t D, const int6
         if (any_other) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_corpus: every view must list the same entities (empty span = view absent)");
     }
     if (mm.doc_id_base + D >= (1LL << 29)) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_corpus: too many entities");
-    if (doc_off[0] != 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_corpus: doc_off[0] must be 0");
-    for (int64_t d = 0; d < D; d++) {
-        int64_t len = doc_off[d + 1] - doc_off[d];
-        if (len < 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_corpus: doc_off must be non-decreasing");
-        if (len >= (1 << 20)) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_corpus: a view of one entity is limited to 2^20-1 tokens");
-    }
+    if (const char* r = check_offsets(doc_off, D, (1 << 20) - 1)) FAIL(h, MVHDP_ERR_INVALID_ARG, std::string("set_corpus: doc_off (a view of one entity: at most 2^20 - 1 tokens) ") + r);
     const int64_t N = doc_off[D];
     if (N > 0 && !tokens) FAIL(h, MVHDP_ERR_INVALID_ARG, "set_corpus: tokens is null");
     HIPC(h, hipSetDevice(h->device));

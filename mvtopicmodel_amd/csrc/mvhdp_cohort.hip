@@ -11,7 +11,7 @@
 //                                mvhdp_top_words.  ShareOrder: an entry carries the handle's n_wk cell beside its key, read only for the
 //                                types that reach min_count, and two entries compare by 64-bit cross products.
 // The cohorts go in passes of as many tables as fit scratch_bytes; a pass clears its tables, counts its listings and selects.
-#include "mvhdp_ctx.h"
+#include "mvhdp_side.h"
 #include "mvhdp_select.h"
 
 namespace {
@@ -143,11 +143,6 @@ __global__ __launch_bounds__(256) void cohort_select_kernel(const int32_t* __res
     if (lane == 0) nonzero[cell] = nzs[0] + nzs[1] + nzs[2] + nzs[3];
 }
 
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 // every check comes before any device work and before the first output is touched
 int check_args(mvhdp_ctx* h, const mvhdp_cohort_args* a, int64_t G, const int64_t* member_off, const int64_t* members, const int32_t* types, const int32_t* counts)
 {
@@ -158,15 +153,11 @@ int check_args(mvhdp_ctx* h, const mvhdp_cohort_args* a, int64_t G, const int64_
     if (a->order != MVHDP_COHORT_BY_COUNT && a->order != MVHDP_COHORT_BY_SHARE) FAIL(h, MVHDP_ERR_INVALID_ARG, "cohort_top_words: bad order");
     if (a->min_count < 1 || a->scratch_bytes < 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "cohort_top_words: min_count < 1 or negative scratch_bytes");
     if ((types == nullptr) != (counts == nullptr)) FAIL(h, MVHDP_ERR_INVALID_ARG, "cohort_top_words: types and counts go together");
-    if (member_off[0] != 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "cohort_top_words: member_off[0] != 0");
-    for (int64_t g = 0; g < G; g++)
-        if (member_off[g + 1] < member_off[g]) FAIL(h, MVHDP_ERR_INVALID_ARG, "cohort_top_words: member_off decreases");
+    if (const char* r = check_offsets(member_off, G, INT64_MAX)) FAIL(h, MVHDP_ERR_INVALID_ARG, std::string("cohort_top_words: member_off ") + r);
     if (member_off[G] > 0 && !members) FAIL(h, MVHDP_ERR_INVALID_ARG, "cohort_top_words: null members");
     if (!h->have_corpus[a->m]) FAIL(h, MVHDP_ERR_STATE, "cohort_top_words: no corpus of the view (set_corpus)");
-    if (a->order == MVHDP_COHORT_BY_SHARE) {
-        if (!h->st.have_counts() || h->st.counts_stale()) FAIL(h, MVHDP_ERR_STATE, "cohort_top_words: BY_SHARE needs current counts (build_counts / set_counts first)");
-        if (h->st.delta_pending()) FAIL(h, MVHDP_ERR_STATE, "cohort_top_words: BY_SHARE while a NO_APPLY sweep's deltas are pending (mvhdp_apply_delta first)");
-    }
+    if (a->order == MVHDP_COHORT_BY_SHARE)
+        if (int rc = require_current_counts(h, "cohort_top_words: BY_SHARE needs current counts")) return rc;
     const std::vector<int64_t>& off = h->h_doc_off[a->m];
     for (int64_t g = 0; g < G; g++) {
         int64_t span = 0;
@@ -193,8 +184,7 @@ int cohort_run(mvhdp_ctx* h, const mvhdp_cohort_args* a, int64_t G, const int64_
     const int K = mm.K, V = mm.V[a->m], n = a->n;
     const int64_t nm = member_off[G], cells = (int64_t)K * V;
     const bool table = want_lists || want_nz;
-    HIPC(h, hipSetDevice(h->device));
-    HIPC(h, hipStreamSynchronize(h->stream));                  // what is pending on the handle lands first
+    if (int rc = side_begin(h)) return rc;
     hipStream_t s = h->stream;
 
     // cohorts per pass: the tables that fit the scratch, at least one; a pass's (cohort, topic) cells within one grid
@@ -226,10 +216,9 @@ int cohort_run(mvhdp_ctx* h, const mvhdp_cohort_args* a, int64_t G, const int64_
     const size_t lds = (size_t)wpb * K * sizeof(int32_t);
     HIPC(h, hipFuncSetAttribute((const void*)cohort_count_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     HIPC(h, hipFuncSetAttribute((const void*)cohort_count_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    EventPair ev;
-    HIPC(h, hipEventCreate(&ev.a));
-    HIPC(h, hipEventCreate(&ev.b));
-    HIPC(h, hipEventRecord(ev.a, s));
+    StreamTimer timer;
+    HIPC(h, timer.create());
+    HIPC(h, timer.start(s));
 
     const int32_t* nwk = mm.counts + mm.rowbase[a->m] * K;
     for (int64_t g0 = 0; g0 < G; g0 += B) {
@@ -257,7 +246,7 @@ int cohort_run(mvhdp_ctx* h, const mvhdp_cohort_args* a, int64_t G, const int64_
         }
         st.passes++;
     }
-    HIPC(h, hipEventRecord(ev.b, s));
+    HIPC(h, timer.stop(s));
     u64 ctl[CH_WORDS] = {};
     HIPC(h, d_ctl.download(ctl, CH_WORDS, s));
     HIPC(h, hipStreamSynchronize(s));
@@ -275,13 +264,11 @@ int cohort_run(mvhdp_ctx* h, const mvhdp_cohort_args* a, int64_t G, const int64_
         HIPC(h, d_nz.download(out.nonzero.data(), out.nonzero.size(), s));
     }
     HIPC(h, hipStreamSynchronize(s));
-    float ms = 0.0f;
-    HIPC(h, hipEventElapsedTime(&ms, ev.a, ev.b));
+    HIPC(h, timer.elapsed_ms(&st.kernel_ms));
     st.listings = nm;
     st.tokens = (int64_t)ctl[CH_TOKENS];
     st.skipped = (int64_t)ctl[CH_SKIPPED];
     st.cohorts_per_pass = (int32_t)std::min<int64_t>(B, INT32_MAX);
-    st.kernel_ms = (double)ms;
     return MVHDP_OK;
 }
 

@@ -7,7 +7,7 @@
 //   diag_columns_kernel     the K x V_0 column sums of uniform_dist, corpus_dist, eff_num_words and discrWeight (DIAG:262-404, PTM:2243-2262)
 // Integer outputs are exact.  No floating-point atomics anywhere: every fp64 sum is a per-thread / per-wave sum over a static share
 // of the work followed by a reduction in a fixed order, so the same model gives the same bits on every call.
-#include "mvhdp_ctx.h"
+#include "mvhdp_side.h"
 #include "mvhdp_select.h"
 
 namespace {
@@ -279,8 +279,7 @@ int diag_ready(mvhdp_ctx* h, bool need_hyper)
 {
     for (int m = 0; m < h->mm.M; m++)
         if (!h->have_corpus[m]) FAIL(h, MVHDP_ERR_STATE, "diagnostics: set_corpus has not been called for every view");
-    if (!h->st.have_counts() || h->st.counts_stale()) FAIL(h, MVHDP_ERR_STATE, "diagnostics: the counts are not current (build_counts / set_counts first)");
-    if (h->st.delta_pending()) FAIL(h, MVHDP_ERR_STATE, "diagnostics: a NO_APPLY sweep's deltas are pending (mvhdp_apply_delta first)");
+    if (int rc = require_current_counts(h, "diagnostics")) return rc;
     if (need_hyper && !h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "diagnostics before set_hyper");
     return MVHDP_OK;
 }

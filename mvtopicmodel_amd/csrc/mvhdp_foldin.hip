@@ -17,7 +17,7 @@
 // bytes a document) stay within FOLDIN_SCRATCH_BYTES (a chunk is at least one document); the global state slices, where used, are at most
 // num_cus * 2 blocks x 4 waves x 2 M 64 T x 4 bytes (256 MiB at M = 8, K = 2048 on 256 CUs).  Everything runs on the handle's stream; the
 // call only reads the handle (no ModelState transition).
-#include "mvhdp_ctx.h"
+#include "mvhdp_side.h"
 #include "mvhdp_wave.h"
 #include "mvhdp_lanes.h"
 
@@ -241,11 +241,6 @@ hipError_t launch_foldin(const FoldinArgs& ka, bool vec, unsigned blocks, size_t
     return hipGetLastError();
 }
 
-struct EventPair {                                             // the kernel's time on the stream
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) hipEventDestroy(a); if (b) hipEventDestroy(b); }
-};
-
 } // namespace
 
 extern "C" int mvhdp_fold_in(mvhdp_handle h, const mvhdp_foldin_args* a, int64_t num_docs, const int64_t* const* doc_off, const int32_t* const* tokens,
@@ -259,50 +254,40 @@ extern "C" int mvhdp_fold_in(mvhdp_handle h, const mvhdp_foldin_args* a, int64_t
     if (a->samples < 1 || a->thin < 1 || (int64_t)a->iterations - ((int64_t)a->samples - 1) * a->thin < 1)
         FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: samples and thin must be >= 1 and every recorded iteration >= 1");
     if (a->doc_base < 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: negative doc_base");
+    const std::string who("fold_in: ");
     if (a->coupling)
-        for (int i = 0; i < M * M; i++)
-            if (!std::isfinite(a->coupling[i]) || a->coupling[i] < 0.0) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: a coupling entry is negative or not finite");
+        if (const char* r = check_nonneg_finite(a->coupling, (int64_t)M * M)) FAIL(h, MVHDP_ERR_INVALID_ARG, who + "a coupling entry " + r);
     if (theta) {
         if (!a->view_weights) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: theta without view_weights");
-        double sum = 0.0;
-        for (int m = 0; m < M; m++) {
-            if (!std::isfinite(a->view_weights[m]) || a->view_weights[m] < 0.0) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: a view weight is negative or not finite");
-            sum += a->view_weights[m];
-        }
-        if (!(sum > 0.0) || !std::isfinite(sum)) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: the view weights must have a positive finite sum");
+        if (const char* r = check_view_weights(a->view_weights, M)) FAIL(h, MVHDP_ERR_INVALID_ARG, who + r);
     }
     int64_t N[MVHDP_MAXM] = {};
     for (int m = 0; m < M; m++) {
         const int64_t* off = doc_off[m];
         if (!off) continue;
-        if (off[0] != 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: doc_off[0] must be 0");
-        for (int64_t d = 0; d < num_docs; d++)
-            if (off[d + 1] < off[d] || off[d + 1] - off[d] > (int64_t)INT32_MAX) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: doc_off is not monotone (or a span beyond 2^31 - 1 tokens)");
+        if (const char* r = check_offsets(off, num_docs, INT32_MAX)) FAIL(h, MVHDP_ERR_INVALID_ARG, who + "doc_off (a span: at most 2^31 - 1 tokens) " + r);
         N[m] = off[num_docs];
         if (N[m] > 0 && !tokens[m]) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: null tokens");
-        for (int64_t i = 0; i < N[m]; i++)
-            if (tokens[m][i] < 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "fold_in: negative token");
+        if (const char* r = check_tokens_nonneg(tokens[m], N[m])) FAIL(h, MVHDP_ERR_INVALID_ARG, who + r);
     }
     if (K > 64 * 32) FAIL(h, MVHDP_ERR_UNSUPPORTED, "fold_in: more than 2048 topics");   // (mvhdp_create admits none: MVHDP_MAX_TOPICS)
     // the counts as the handle holds them: stale counts, or counts that lack a NO_APPLY sweep's pending deltas, are taken as they are (the header says so)
     if (!h->have_hyper || !h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "fold_in before set_hyper / counts (build_counts, set_counts or a sweep)");
     mvhdp_foldin_stats st{};
     if (num_docs == 0) { if (stats) *stats = st; return MVHDP_OK; }
-    HIPC(h, hipSetDevice(h->device));
-    HIPC(h, hipStreamSynchronize(h->stream));                  // what is pending on the handle lands first
+    if (int rc = side_begin(h)) return rc;
 
     // ---- the frozen model in the order the lanes read it ----
-    int T = 1;
-    while (64 * T < K) T <<= 1;
-    const int KT = 64 * T;
-    const bool vec = T >= 4 && K % 4 == 0;
+    const LaneTiling lt = lane_tiling(K);
+    const int T = lt.T, KT = 64 * T;
+    const bool vec = lt.vec;
     std::vector<int32_t> nk((size_t)M * K);
     HIPC(h, hipMemcpyAsync(nk.data(), mm.counts + mm.rowbase[M] * K, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
     std::vector<double> tab((size_t)M * 2 * KT, 0.0);
     for (int m = 0; m < M; m++)
         for (int k = 0; k < K; k++) {
-            const size_t at = (size_t)m * 2 * KT + (size_t)(k % T) * 64 + (size_t)(k / T);
+            const size_t at = (size_t)m * 2 * KT + lane_slot(k, T);
             tab[at] = mm.gamma[m] * h->h_alpha[(size_t)m * (K + 1) + k];
             const bool off_topic = !h->h_inactive.empty() && h->h_inactive[(size_t)k] != 0;
             tab[at + KT] = off_topic ? 0.0 : 1.0 / ((double)nk[(size_t)m * K + k] + mm.beta_sum[m]);   // phi of an inactive topic is exactly 0.0
@@ -334,9 +319,8 @@ extern "C" int mvhdp_fold_in(mvhdp_handle h, const mvhdp_foldin_args* a, int64_t
     const size_t slice_ints = (size_t)2 * M * KT;
     const bool lds_state = 4 * slice_ints * sizeof(int32_t) <= FOLDIN_LDS_STATE_BYTES;
     const int64_t max_blocks = (int64_t)h->num_cus * (lds_state ? 8 : 2);
-    EventPair ev;
-    HIPC(h, hipEventCreate(&ev.a));
-    HIPC(h, hipEventCreate(&ev.b));
+    StreamTimer timer;                                         // the kernel's time on the stream, chunk by chunk
+    HIPC(h, timer.create());
 
     // ---- what the host can count ----
     std::vector<int64_t> doc_len((size_t)num_docs, 0);
@@ -368,9 +352,7 @@ extern "C" int mvhdp_fold_in(mvhdp_handle h, const mvhdp_foldin_args* a, int64_t
         do { bytes += doc_bytes + (size_t)doc_len[(size_t)d1] * 6; d1++; }
         while (d1 < num_docs && bytes + doc_bytes + (size_t)doc_len[(size_t)d1] * 6 <= FOLDIN_SCRATCH_BYTES && d1 - d0 < (int64_t)INT32_MAX);
         const int64_t Dc = d1 - d0;
-        c_order.resize((size_t)Dc);
-        for (int64_t d = 0; d < Dc; d++) c_order[(size_t)d] = (int32_t)d;
-        std::stable_sort(c_order.begin(), c_order.end(), [&](int32_t l, int32_t r) { return doc_len[(size_t)(d0 + l)] > doc_len[(size_t)(d0 + r)]; });
+        order_by_length_desc(c_order, Dc, [&](int32_t d) { return doc_len[(size_t)(d0 + d)]; });
         DevArray<int64_t> d_off[MVHDP_MAXM];
         DevArray<int32_t> d_tok[MVHDP_MAXM], d_order, d_cs;
         DevArray<uint16_t> d_zs[MVHDP_MAXM];
@@ -401,18 +383,10 @@ extern "C" int mvhdp_fold_in(mvhdp_handle h, const mvhdp_foldin_args* a, int64_t
         ka.state = lds_state ? nullptr : d_state.get();
         ka.n_docs = Dc; ka.doc_global0 = a->doc_base + d0;
         const size_t lds = lds_state ? 4 * slice_ints * sizeof(int32_t) : 0;
-        HIPC(h, hipEventRecord(ev.a, h->stream));
-        hipError_t e = hipErrorInvalidValue;
-        switch (T) {
-        case 1: e = launch_foldin<1>(ka, vec, blocks, lds, h->stream); break;
-        case 2: e = launch_foldin<2>(ka, vec, blocks, lds, h->stream); break;
-        case 4: e = launch_foldin<4>(ka, vec, blocks, lds, h->stream); break;
-        case 8: e = launch_foldin<8>(ka, vec, blocks, lds, h->stream); break;
-        case 16: e = launch_foldin<16>(ka, vec, blocks, lds, h->stream); break;
-        case 32: e = launch_foldin<32>(ka, vec, blocks, lds, h->stream); break;
-        }
+        HIPC(h, timer.start(h->stream));
+        const hipError_t e = dispatch_T(T, [&](auto t) { return launch_foldin<decltype(t)::value>(ka, vec, blocks, lds, h->stream); });
         HIPC(h, e);
-        HIPC(h, hipEventRecord(ev.b, h->stream));
+        HIPC(h, timer.stop(h->stream));
         if (theta) HIPC(h, d_theta.download(h_theta.data() + (size_t)d0 * K, (size_t)Dc * K, h->stream));
         if (counts_sum) HIPC(h, d_cs.download(h_cs.data() + (size_t)d0 * M * K, (size_t)Dc * M * K, h->stream));
         for (int m = 0; m < M; m++)
@@ -421,9 +395,9 @@ extern "C" int mvhdp_fold_in(mvhdp_handle h, const mvhdp_foldin_args* a, int64_t
                 if (Nc > 0) HIPC(h, d_zs[m].download(h_z[m].data() + t0, (size_t)Nc, h->stream));
             }
         HIPC(h, hipStreamSynchronize(h->stream));
-        float ms = 0.f;
-        HIPC(h, hipEventElapsedTime(&ms, ev.a, ev.b));
-        kernel_ms += (double)ms;
+        double ms = 0.0;
+        HIPC(h, timer.elapsed_ms(&ms));
+        kernel_ms += ms;
         d0 = d1;
     }
 

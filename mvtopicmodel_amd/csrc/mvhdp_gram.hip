@@ -20,7 +20,7 @@
 //                         of the pass's 64-row groups, a thread 4 x 4 cells; the cost does not depend on how many rows lie above.
 // The integer tables grow by 64-bit integer atomics, which commute; there are no floating-point atomics.  Everything runs on the handle's
 // stream; theta (mvhdp_launch_doc_topic_prop) and phi (xview_phi_kernel) are formed per pass and never leave the device.
-#include "mvhdp_ctx.h"
+#include "mvhdp_side.h"
 #include "mvhdp_select.h"
 #include "mvhdp_xview.h"
 
@@ -210,11 +210,6 @@ __global__ __launch_bounds__(256) void gram_co_kernel(const u64* __restrict__ ma
         }
 }
 
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 // every check comes before the first output is touched
 int check_args(mvhdp_ctx* h, const mvhdp_topic_gram_args* a, const double* gram, const double* sums)
 {
@@ -227,28 +222,19 @@ int check_args(mvhdp_ctx* h, const mvhdp_topic_gram_args* a, const double* gram,
     if (a->source == MVHDP_GRAM_HOST) {
         if (!a->x) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: null x");
         if (a->r0 < 0 || a->r0 > a->r1) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: bad row range");
-        const int64_t n = (a->r1 - a->r0) * mm.K;
-        for (int64_t i = 0; i < n; i++)
-            if (!(a->x[i] >= 0.0) || !std::isfinite(a->x[i])) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: an x entry is negative or not finite");
+        if (const char* r = check_nonneg_finite(a->x, (a->r1 - a->r0) * mm.K)) FAIL(h, MVHDP_ERR_INVALID_ARG, std::string("topic_gram: an x entry ") + r);
         return MVHDP_OK;
     }
     if (a->source == MVHDP_GRAM_WORDS && (a->m < 0 || a->m >= mm.M)) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: bad view");
     int rc = require_corpus(h); if (rc) return rc;
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, "topic_gram before set_hyper");
     if (a->source == MVHDP_GRAM_WORDS) {
-        if (!h->st.have_counts() || h->st.counts_stale()) FAIL(h, MVHDP_ERR_STATE, "topic_gram: the counts are not current (build_counts / set_counts first)");
-        if (h->st.delta_pending()) FAIL(h, MVHDP_ERR_STATE, "topic_gram: a NO_APPLY sweep's deltas are pending (mvhdp_apply_delta first)");
+        rc = require_current_counts(h, "topic_gram"); if (rc) return rc;
         if (a->r0 < 0 || a->r1 > mm.V[a->m] || a->r0 > a->r1) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: bad type range");
         return MVHDP_OK;
     }
     if (a->r0 < 0 || a->r1 > mm.D || a->r0 > a->r1) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: bad entity range");
-    if (!a->view_weights) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: null view_weights");
-    double sum = 0.0;
-    for (int m = 0; m < mm.M; m++) {
-        if (!std::isfinite(a->view_weights[m]) || a->view_weights[m] < 0.0) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: a view weight is negative or not finite");
-        sum += a->view_weights[m];
-    }
-    if (!(sum > 0.0) || !std::isfinite(sum)) FAIL(h, MVHDP_ERR_INVALID_ARG, "topic_gram: the view weights do not sum to a positive number");
+    if (const char* r = check_view_weights(a->view_weights, mm.M)) FAIL(h, MVHDP_ERR_INVALID_ARG, std::string("topic_gram: ") + r);
     return MVHDP_OK;
 }
 
@@ -263,8 +249,7 @@ int gram_run(mvhdp_ctx* h, const mvhdp_topic_gram_args* a, bool want_n, bool wan
     const int K = mm.K;
     const int64_t KK = (int64_t)K * K, R = a->r1 - a->r0, NB = (R + GRAM_B - 1) / GRAM_B;
     const bool counts = want_n || want_co;
-    HIPC(h, hipSetDevice(h->device));
-    HIPC(h, hipStreamSynchronize(h->stream));                  // what is pending on the handle lands first
+    if (int rc = side_begin(h)) return rc;
     hipStream_t s = h->stream;
 
     // blocks per pass: what the caller asks for, else the partials within 256 MiB; either way the rows of a pass within 1 GiB
@@ -310,10 +295,9 @@ int gram_run(mvhdp_ctx* h, const mvhdp_topic_gram_args* a, bool want_n, bool wan
             HIPC(h, d_cotiles.upload(h_cotiles.data(), h_cotiles.size(), s));
         }
     }
-    EventPair ev;
-    HIPC(h, hipEventCreate(&ev.a));
-    HIPC(h, hipEventCreate(&ev.b));
-    HIPC(h, hipEventRecord(ev.a, s));
+    StreamTimer timer;
+    HIPC(h, timer.create());
+    HIPC(h, timer.start(s));
 
     const unsigned wide = (unsigned)h->num_cus * 16;
     for (int64_t b0 = 0; b0 < NB; b0 += BP) {
@@ -343,7 +327,7 @@ int gram_run(mvhdp_ctx* h, const mvhdp_topic_gram_args* a, bool want_n, bool wan
         LAUNCH(h, gram_reduce_kernel, dim3((unsigned)((KK + K + 255) / 256)), dim3(256), 0, s, d_P, d_Psum, nb, K, d_gram, d_sums);
         st.passes++;
     }
-    HIPC(h, hipEventRecord(ev.b, s));
+    HIPC(h, timer.stop(s));
     HIPC(h, d_gram.download(out.gram.data(), (size_t)KK, s));
     HIPC(h, d_sums.download(out.sums.data(), (size_t)K, s));
     if (counts) HIPC(h, d_n.download(out.n_above.data(), (size_t)K, s));
@@ -354,11 +338,9 @@ int gram_run(mvhdp_ctx* h, const mvhdp_topic_gram_args* a, bool want_n, bool wan
             out.gram[(size_t)k * K + l] = out.gram[(size_t)l * K + k];
             if (want_co) out.co[(size_t)k * K + l] = out.co[(size_t)l * K + k];
         }
-    float ms = 0.0f;
-    HIPC(h, hipEventElapsedTime(&ms, ev.a, ev.b));
+    HIPC(h, timer.elapsed_ms(&st.kernel_ms));
     st.rows = R;
     st.blocks = (int32_t)NB;
-    st.kernel_ms = (double)ms;
     return MVHDP_OK;
 }
 

@@ -16,7 +16,7 @@
 //                                log S[n] - log R in a fixed order.
 // Work is cut into document chunks on the host so that the per-particle buffers (p_r[n]: 8 bytes, z beyond the cap: 2 bytes, per particle and
 // token) stay within HELDOUT_SCRATCH_BYTES.  Everything runs on the handle's stream.
-#include "mvhdp_ctx.h"
+#include "mvhdp_side.h"
 #include "mvhdp_wave.h"
 #include "mvhdp_lanes.h"
 
@@ -214,25 +214,22 @@ extern "C" int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_a
     if (a->m < 0 || a->m >= mm.M) FAIL(h, MVHDP_ERR_INVALID_ARG, "heldout_left_to_right: bad view");
     if (a->particles < 1 || a->particles > HELDOUT_MAX_PARTICLES) FAIL(h, MVHDP_ERR_INVALID_ARG, "heldout_left_to_right: particles outside 1..2^20");
     if (a->doc_base < 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "heldout_left_to_right: negative doc_base");
-    if (doc_off[0] != 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "heldout_left_to_right: doc_off[0] must be 0");
-    for (int64_t d = 0; d < num_docs; d++)
-        if (doc_off[d + 1] < doc_off[d] || doc_off[d + 1] - doc_off[d] > (int64_t)INT32_MAX) FAIL(h, MVHDP_ERR_INVALID_ARG, "heldout_left_to_right: doc_off is not monotone (or a document beyond 2^31 - 1 tokens)");
+    const std::string who("heldout_left_to_right: ");
+    if (const char* r = check_offsets(doc_off, num_docs, INT32_MAX)) FAIL(h, MVHDP_ERR_INVALID_ARG, who + "doc_off (a span: at most 2^31 - 1 tokens) " + r);
     const int64_t N = doc_off[num_docs];
     if (N > 0 && !tokens) FAIL(h, MVHDP_ERR_INVALID_ARG, "heldout_left_to_right: null tokens");
-    for (int64_t i = 0; i < N; i++)
-        if (tokens[i] < 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "heldout_left_to_right: negative token");
+    if (const char* r = check_tokens_nonneg(tokens, N)) FAIL(h, MVHDP_ERR_INVALID_ARG, who + r);
     if (K > 64 * 32) FAIL(h, MVHDP_ERR_UNSUPPORTED, "heldout_left_to_right: more than 2048 topics");   // (mvhdp_create admits none: MVHDP_MAX_TOPICS)
     // the counts as the handle holds them: stale counts, or counts that lack a NO_APPLY sweep's pending deltas, are evaluated as they are (the header says so)
     if (!h->have_hyper || !h->st.have_counts()) FAIL(h, MVHDP_ERR_STATE, "heldout_left_to_right before set_hyper / counts (build_counts, set_counts or a sweep)");
     const int m = a->m, V = mm.V[m], R = a->particles;
     const bool resample = a->resample != 0;
-    HIPC(h, hipSetDevice(h->device));
-    HIPC(h, hipStreamSynchronize(h->stream));                  // what is pending on the handle lands first
+    if (int rc = side_begin(h)) return rc;
 
     // ---- the frozen model: alpha, 1 / (n_k + betaSum), in the order the lanes read them ----
-    int T = 1;
-    while (64 * T < K) T <<= 1;
-    const bool vec = T >= 4 && K % 4 == 0;
+    const LaneTiling lt = lane_tiling(K);
+    const int T = lt.T;
+    const bool vec = lt.vec;
     std::vector<int32_t> nk((size_t)K);
     HIPC(h, hipMemcpyAsync(nk.data(), mm.counts + mm.rowbase[mm.M] * K + (int64_t)m * K, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
     HIPC(h, hipStreamSynchronize(h->stream));
@@ -241,7 +238,7 @@ extern "C" int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_a
     const double alpha_sum = a->alpha ? a->alpha_sum : mm.gamma[m] * mm.alpha_sum[m];
     std::vector<double> tab((size_t)2 * 64 * T, 0.0);
     for (int k = 0; k < K; k++) {
-        const size_t at = (size_t)(k % T) * 64 + (size_t)(k / T);
+        const size_t at = lane_slot(k, T);
         tab[at] = alpha[k];
         tab[(size_t)64 * T + at] = 1.0 / ((double)nk[(size_t)k] + beta_sum);
     }
@@ -277,12 +274,10 @@ extern "C" int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_a
         const int64_t Dc = d1 - d0, t0 = doc_off[d0], Nc = doc_off[d1] - t0;
         if (Nc > 0) {
             c_off.resize((size_t)Dc + 1);
-            c_order.resize((size_t)Dc);
             int64_t longest = 0;
             for (int64_t d = 0; d <= Dc; d++) c_off[(size_t)d] = doc_off[d0 + d] - t0;
-            for (int64_t d = 0; d < Dc; d++) { c_order[(size_t)d] = (int32_t)d; longest = std::max(longest, c_off[(size_t)d + 1] - c_off[(size_t)d]); }
-            std::stable_sort(c_order.begin(), c_order.end(), [&](int32_t l, int32_t r) {
-                return c_off[(size_t)l + 1] - c_off[(size_t)l] > c_off[(size_t)r + 1] - c_off[(size_t)r]; });
+            for (int64_t d = 0; d < Dc; d++) longest = std::max(longest, c_off[(size_t)d + 1] - c_off[(size_t)d]);
+            order_by_length_desc(c_order, Dc, [&](int32_t d) { return c_off[(size_t)d + 1] - c_off[(size_t)d]; });
             DevArray<int64_t> d_off;
             DevArray<int32_t> d_tok, d_order;
             DevArray<uint16_t> d_zs;
@@ -308,15 +303,7 @@ extern "C" int mvhdp_heldout_left_to_right(mvhdp_handle h, const mvhdp_heldout_a
             ka.beta = beta; ka.alpha_sum = alpha_sum;
             ka.seed_lo = (uint32_t)a->seed; ka.seed_hi = (uint32_t)(a->seed >> 32);
             const unsigned blocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ka.n_items + 7) / 8, (int64_t)h->num_cus * 8));   // two items a wave at least: the tables are staged once per block
-            hipError_t e = hipErrorInvalidValue;
-            switch (T) {
-            case 1: e = launch_ltr<1>(ka, vec, blocks, h->stream); break;
-            case 2: e = launch_ltr<2>(ka, vec, blocks, h->stream); break;
-            case 4: e = launch_ltr<4>(ka, vec, blocks, h->stream); break;
-            case 8: e = launch_ltr<8>(ka, vec, blocks, h->stream); break;
-            case 16: e = launch_ltr<16>(ka, vec, blocks, h->stream); break;
-            case 32: e = launch_ltr<32>(ka, vec, blocks, h->stream); break;
-            }
+            const hipError_t e = dispatch_T(T, [&](auto t) { return launch_ltr<decltype(t)::value>(ka, vec, blocks, h->stream); });
             HIPC(h, e);
             const unsigned rblocks = (unsigned)std::max<int64_t>(1, std::min<int64_t>((Dc + 3) / 4, (int64_t)h->num_cus * 8));
             LAUNCH(h, heldout_reduce_kernel, dim3(rblocks), dim3(256), 0, h->stream, d_P, d_off, d_tok, Dc, Nc, V, R, std::log((double)R), d_S, d_ll);

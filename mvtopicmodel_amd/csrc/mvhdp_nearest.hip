@@ -21,6 +21,7 @@
 #include "mvhdp_screen.h"
 #include "mvhdp_select.h"
 #include "mvhdp_nearest.h"
+#include "mvhdp_side.h"
 
 namespace {
 
@@ -323,8 +324,6 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const double* __restrict
         if (lane == 0) counts[k] = n_eff;
     }
 }
-
-unsigned row_blocks(int64_t rows, int num_cus) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t)num_cus * 32)); }
 
 // the proportions of entities [d0, d1) into out [d1 - d0][K], chunk by chunk
 int launch_theta(mvhdp_ctx* h, const DocTopicCarry& carry, const double* d_w, int64_t d0, int64_t d1, double* out)

@@ -11,6 +11,7 @@
 // the host sorts each stripe's survivors by (i << 32) | j.
 #include "mvhdp_screen.h"
 #include "mvhdp_select.h"
+#include "mvhdp_side.h"
 
 namespace {
 
@@ -483,9 +484,7 @@ extern "C" int mvhdp_entity_topic_distributions(mvhdp_handle h, const double* vi
     const int K = mm.K;
     if (!view_weights || n_groups < 0 || !member_off || (n_groups > 0 && !out)) FAIL(h, MVHDP_ERR_INVALID_ARG, "entity_topic_distributions: null buffer or negative n_groups");
     if (threshold != threshold || round_digits < -1 || round_digits > 15) FAIL(h, MVHDP_ERR_INVALID_ARG, "entity_topic_distributions: NaN threshold or round_digits outside -1..15");
-    if (member_off[0] != 0) FAIL(h, MVHDP_ERR_INVALID_ARG, "entity_topic_distributions: member_off[0] != 0");
-    for (int64_t g = 0; g < n_groups; g++)
-        if (member_off[g + 1] < member_off[g]) FAIL(h, MVHDP_ERR_INVALID_ARG, "entity_topic_distributions: member_off decreases");
+    if (const char* r = check_offsets(member_off, n_groups, INT64_MAX)) FAIL(h, MVHDP_ERR_INVALID_ARG, std::string("entity_topic_distributions: member_off ") + r);
     const int64_t nm = member_off[n_groups];
     if (nm > 0 && !members) FAIL(h, MVHDP_ERR_INVALID_ARG, "entity_topic_distributions: null members");
     for (int64_t q = 0; q < nm; q++)

@@ -10,8 +10,8 @@
 //                         second kernel places each by the number that precede it; one wave per pair counts the entries that
 //                         precede the queried one.  Integers and exact fp64 values only.
 // Work is cut on the host: theta in ranges of entities, scores in blocks of rows, phi in stripes of types, each within XVIEW_BLOCK_BYTES.
-// Everything runs on the handle's stream.
-#include "mvhdp_ctx.h"
+// Everything runs on the handle's stream; the shared argument checks, the prologue and wave_blocks are mvhdp_side.h's.
+#include "mvhdp_side.h"
 #include "mvhdp_select.h"
 #include "mvhdp_xview.h"
 
@@ -161,9 +161,6 @@ __global__ __launch_bounds__(256) void xview_rank_kernel(const u64* __restrict__
     }
 }
 
-
-unsigned wave_blocks(int64_t waves, int num_cus) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)num_cus * 16)); }
-
 // MVHDP_XVIEW_BLOCK_BYTES (tests: forces the borders between blocks, stripes and ranges at small sizes)
 size_t block_bytes()
 {
@@ -204,21 +201,13 @@ int check_common(mvhdp_ctx* h, const mvhdp_predict_args* a, int64_t d0, int64_t 
     if (a->m < 0 || a->m >= mm.M) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": bad view");
     int rc = require_corpus(h); if (rc) return rc;
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, w + " before set_hyper");
-    if (!h->st.have_counts() || h->st.counts_stale()) FAIL(h, MVHDP_ERR_STATE, w + ": the counts are not current (build_counts / set_counts first)");
-    if (h->st.delta_pending()) FAIL(h, MVHDP_ERR_STATE, w + ": a NO_APPLY sweep's deltas are pending (mvhdp_apply_delta first)");
+    rc = require_current_counts(h, w); if (rc) return rc;
     if (d0 < 0 || d1 > mm.D || d0 > d1) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": bad entity range");
     if (a->theta) {
-        const int64_t n = (d1 - d0) * mm.K;
-        for (int64_t i = 0; i < n; i++)
-            if (!(a->theta[i] >= 0.0) || !std::isfinite(a->theta[i])) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": a theta entry is negative or not finite");
+        if (const char* r = check_nonneg_finite(a->theta, (d1 - d0) * mm.K)) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": a theta entry " + r);
     } else {
         if (!a->view_weights) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": neither view_weights nor theta");
-        double sum = 0.0;
-        for (int m = 0; m < mm.M; m++) {
-            if (!std::isfinite(a->view_weights[m]) || a->view_weights[m] < 0.0) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": a view weight is negative or not finite");
-            sum += a->view_weights[m];
-        }
-        if (!(sum > 0.0) || !std::isfinite(sum)) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": the view weights do not sum to a positive number");
+        if (const char* r = check_view_weights(a->view_weights, mm.M)) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": " + r);
     }
     return MVHDP_OK;
 }
@@ -231,8 +220,7 @@ int xview_run(mvhdp_ctx* h, const mvhdp_predict_args* a, int64_t d0, int64_t d1,
     const int64_t V = mm.V[m];
     const bool excl = a->exclude_present != 0;
     const size_t bb = block_bytes();
-    HIPC(h, hipSetDevice(h->device));
-    HIPC(h, hipStreamSynchronize(h->stream));                  // what is pending on the handle lands first
+    if (int rc = side_begin(h)) return rc;
     hipStream_t s = h->stream;
 
     DocTopicCarry carry{};

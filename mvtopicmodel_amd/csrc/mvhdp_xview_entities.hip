@@ -20,7 +20,7 @@
 //                         (score, entity); the counts add over the blocks of entities.
 // Work is cut on the host: queries in blocks, entities in blocks, the block of scores within 256 MiB.  theta is formed per block of
 // entities (mvhdp_launch_doc_topic_prop) and never leaves the device.  No floating-point atomics; everything runs on the handle's stream.
-#include "mvhdp_ctx.h"
+#include "mvhdp_side.h"
 #include "mvhdp_select.h"
 #include "mvhdp_xview.h"
 
@@ -240,14 +240,6 @@ __global__ __launch_bounds__(256) void xe_rank_kernel(const u64* __restrict__ S,
     }
 }
 
-unsigned wave_blocks(int64_t waves, int num_cus) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)num_cus * 16)); }
-unsigned row_blocks(int64_t rows, int num_cus) { return (unsigned)std::max<int64_t>(1, std::min<int64_t>(rows, (int64_t)num_cus * 32)); }
-
-struct EventPair {
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
-
 struct EntPredict {
     int32_t n = 0;
     std::vector<int64_t> ids;
@@ -272,29 +264,16 @@ int check_args(mvhdp_ctx* h, const mvhdp_entities_args* a, const char* who)
     if (a->m < 0 || a->m >= mm.M) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": bad view");
     int rc = require_corpus(h); if (rc) return rc;
     if (!h->have_hyper) FAIL(h, MVHDP_ERR_STATE, w + " before set_hyper");
-    if (!h->st.have_counts() || h->st.counts_stale()) FAIL(h, MVHDP_ERR_STATE, w + ": the counts are not current (build_counts / set_counts first)");
-    if (h->st.delta_pending()) FAIL(h, MVHDP_ERR_STATE, w + ": a NO_APPLY sweep's deltas are pending (mvhdp_apply_delta first)");
+    rc = require_current_counts(h, w); if (rc) return rc;
     if (a->c0 < 0 || a->c1 > mm.D || a->c0 > a->c1) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": bad candidate range");
     if (a->nq < 0) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": negative nq");
     if (a->block_entities < 0 || a->block_queries < 0) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": negative block_entities or block_queries");
-    if (!a->view_weights) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": null view_weights");
-    double sum = 0.0;
-    for (int m = 0; m < mm.M; m++) {
-        if (!std::isfinite(a->view_weights[m]) || a->view_weights[m] < 0.0) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": a view weight is negative or not finite");
-        sum += a->view_weights[m];
-    }
-    if (!(sum > 0.0) || !std::isfinite(sum)) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": the view weights do not sum to a positive number");
+    if (const char* r = check_view_weights(a->view_weights, mm.M)) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": " + r);
     if (a->psi) {
-        const int64_t cells = a->nq * mm.K;
-        for (int64_t i = 0; i < cells; i++)
-            if (!(a->psi[i] >= 0.0) || !std::isfinite(a->psi[i])) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": a psi entry is negative or not finite");
+        if (const char* r = check_nonneg_finite(a->psi, a->nq * mm.K)) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": a psi entry " + r);
     } else if (a->nq > 0) {
         if (!a->q_off) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": null q_off");
-        if (a->q_off[0] != 0) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": q_off does not start at 0");
-        for (int64_t j = 0; j < a->nq; j++) {
-            if (a->q_off[j + 1] < a->q_off[j]) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": q_off decreases");
-            if (a->q_off[j + 1] - a->q_off[j] > XE_MAX_QUERY_ITEMS) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": a query of more than 2^20 items");
-        }
+        if (const char* r = check_offsets(a->q_off, a->nq, XE_MAX_QUERY_ITEMS)) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": q_off (a query: at most 2^20 items) " + r);
         const int64_t total = a->q_off[a->nq];
         if (total > 0 && !a->q_items) FAIL(h, MVHDP_ERR_INVALID_ARG, w + ": null q_items");
         const int32_t V = mm.V[a->m];
@@ -314,8 +293,7 @@ int entities_run(mvhdp_ctx* h, const mvhdp_entities_args* a, EntPredict* pr, Ent
     const int K = mm.K, m = a->m;
     const int64_t V = mm.V[m], C = a->c1 - a->c0;
     const bool item_form = a->psi == nullptr, excl = item_form && a->exclude_present != 0;
-    HIPC(h, hipSetDevice(h->device));
-    HIPC(h, hipStreamSynchronize(h->stream));                  // what is pending on the handle lands first
+    if (int rc = side_begin(h)) return rc;
     hipStream_t s = h->stream;
 
     // the queries that take part: every one (predict), or those that have pairs, each once (rank)
@@ -385,10 +363,9 @@ int entities_run(mvhdp_ctx* h, const mvhdp_entities_args* a, EntPredict* pr, Ent
         std::stable_sort(order.begin(), order.end(), [&](int64_t l, int64_t r) {
             return blk[(size_t)l] != blk[(size_t)r] ? blk[(size_t)l] < blk[(size_t)r] : rk->entity[l] < rk->entity[r]; });
     }
-    EventPair ev;
-    HIPC(h, hipEventCreate(&ev.a));
-    HIPC(h, hipEventCreate(&ev.b));
-    HIPC(h, hipEventRecord(ev.a, s));
+    StreamTimer timer;
+    HIPC(h, timer.create());
+    HIPC(h, timer.start(s));
 
     std::vector<double> h_psi, c_pscore;
     std::vector<int64_t> h_invoff;
@@ -529,13 +506,11 @@ int entities_run(mvhdp_ctx* h, const mvhdp_entities_args* a, EntPredict* pr, Ent
         }
     }
     u64 marked = 0;
-    HIPC(h, hipEventRecord(ev.b, s));
+    HIPC(h, timer.stop(s));
     HIPC(h, d_marked.download(&marked, 1, s));
     HIPC(h, hipStreamSynchronize(s));
-    float ms = 0.0f;
-    HIPC(h, hipEventElapsedTime(&ms, ev.a, ev.b));
+    HIPC(h, timer.elapsed_ms(&st.kernel_ms));
     st.excluded = (int64_t)marked;
-    st.kernel_ms = (double)ms;
     return MVHDP_OK;
 }
 
