@@ -829,6 +829,53 @@ int mvhdp_cohort_top_words(mvhdp_handle h, const mvhdp_cohort_args* a, int64_t n
                            int32_t* nonzero /*[G][K] or NULL*/, int64_t* tokens /*[G][K] or NULL*/, int64_t* docs /*[G][K] or NULL*/,
                            mvhdp_cohort_stats* stats /* or NULL */);
 
+/* ---- topic surgery: merge, drop and reorder topics on the trained handle.  mvhdp_topic_gram finds near-duplicate topics, mvhdp_diagnostics
+ * junk topics, n_k the topics that have died out; this call acts on them.  It is what the reference's mergeSimilarTopics (PTM:677-843, left
+ * commented out there) does with its merge map and delete list -- every z rewritten (PTM:832-834), then a recount -- applied to the
+ * assignments, the counts, alpha and the inactive set together, on the device.  The definition is ours.
+ * One hop: z' = map[z] for z >= 0; -1 stays -1.  map[k] in [0, K) is the topic that takes topic k's tokens, MVHDP_UNASSIGNED_TOPIC drops
+ *   them (they become unassigned, and the next sampling sweep assigns them anew).  The map is NOT chased: map = [1, 2, 2] sends topic 0's
+ *   tokens to 1 and topic 1's to 2.  Any map is legal, permutations with cycles included.  The sources of t are {k : map[k] == t}.
+ * Counts: n_wk'[w][t] = the sum of n_wk[w][k] over the sources of t, n_k' likewise: after the call the counts are exactly the recount of
+ *   z' (mvhdp_build_counts would change nothing).
+ * alpha: for every view, alpha'[m][t] = the fp64 sum of alpha[m][k] over the sources of t in ascending k; a single source moves its bits, so
+ *   a permutation permutes alpha exactly.  A topic without a source gets +0.0.  alpha[m][K], alpha_sum and every other field of mvhdp_hyper
+ *   stay as they are: the mass of dropped topics is NOT redistributed (the host does that through mvhdp_set_hyper if it wants to).
+ * inactive: a topic with sources is inactive iff all its sources were.  A topic without a source keeps its state -- an active one stays
+ *   "active" with alpha 0 and is never sampled again, as PTM:751 leaves it -- unless MVHDP_REMAP_RETIRE is set: then it joins the inactive
+ *   set, and a later birth can take its index (a truncated HDP otherwise never gets a vacated index back).  first_inactive is recomputed
+ *   and MVHDP_BUF_BIRTH_KEYS is reset to MVHDP_ACT_KEY_NONE.
+ * The handle afterwards: as after mvhdp_set_assignments of every view and mvhdp_build_counts -- the counts current, the trees outdated, the
+ *   slot counts, the 16-bit and 12-bit images and the row classes rewritten by the next sweep's own preparation.  Every kind of sweep goes
+ *   on from there and equals, integer for integer, a fresh handle loaded with z', alpha', inactive' (tests/test_gpu_remap.py).
+ * Refusals, checked whole before anything changes (z, counts, alpha and inactive stay byte for byte): MVHDP_ERR_INVALID_ARG for a NULL a
+ *   or map, an entry below -1 or >= K, an unknown flag; MVHDP_ERR_STATE before mvhdp_set_corpus of every view or mvhdp_set_hyper, with
+ *   counts that are not current or a MVHDP_SWEEP_NO_APPLY sweep's deltas pending (the rule of mvhdp_top_words), inside an
+ *   mvhdp_apply_delta_begin bracket; MVHDP_ERR_UNSUPPORTED while a vectors mix is set (its [V_0][K] columns belong to topics) or embeddings
+ *   with topic rows are initialised (mvhdp_emb_release first).  -1 for a NULL handle.
+ * stats (or NULL): moved[m] = the view-m tokens whose z changed to another topic, dropped[m] = those that became unassigned; vacated = the
+ *   topics without a source that held tokens or were active before, retired = those of them that are inactive afterwards; kernel_ms = the
+ *   stream's time over both passes.
+ * On the device: one pass over every view's z (the map in LDS, 16-byte loads, a lane stores only what changed) and one over the sumV + M
+ *   rows of MVHDP_BUF_COUNTS, a wave per row, the row held in registers and folded through LDS in place: 4 bytes read per token and per
+ *   count cell, written only where something changed.  profiles/remap_topics.md has the figures.
+ * Not done: the reference's own discriminative-weight delete rule (PTM:773-809: the host builds the map, mvtopicmodel_amd/surgery.py has
+ *   merge, prune and order maps), splitting a topic, a JNI class.
+ * mvhdp_remap_args: a pointer and a uint32 (16 bytes).  mvhdp_remap_stats: int64 moved[8], dropped[8]; int32 vacated, retired; double
+ *   kernel_ms (144 bytes).  tests/test_remap_kats.py pins both. */
+#define MVHDP_REMAP_RETIRE 0x1u   /* vacated topics join the inactive set (ours); without it they stay active with alpha 0, as PTM:751 leaves them */
+typedef struct {
+    const int32_t* map;     /* [K]: map[k] in [0, K) = the topic that takes topic k's tokens; MVHDP_UNASSIGNED_TOPIC = they become unassigned */
+    uint32_t flags;
+} mvhdp_remap_args;
+typedef struct {
+    int64_t moved[MVHDP_MAX_MODALITIES];    /* tokens whose z changed to another topic */
+    int64_t dropped[MVHDP_MAX_MODALITIES];  /* tokens that became unassigned */
+    int32_t vacated, retired;               /* topics no topic maps onto that held tokens or were active before; of those, inactive afterwards */
+    double kernel_ms;
+} mvhdp_remap_stats;
+int mvhdp_remap_topics(mvhdp_handle h, const mvhdp_remap_args* a, mvhdp_remap_stats* stats /* or NULL */);
+
 /* ---- word and topic embeddings: trainTypeVectors (PTM:517-524, 1186-1206, 1495-1498) and SciTopicFlow.runWordEmbeddings (FLOW:115-136).
  * TWE = MVTopicModel/TopicWordEmbeddings.java, TWER = MVTopicModel/TopicWordEmbeddingRunnable.java.  WordEmbeddings is TWE with no
  * topics and no context columns: the same trainer with with_topics = 0 (a WordEmbeddings host makes a K = 1, M = 1 handle over its
@@ -1095,6 +1142,12 @@ int mvhdp_group_abort(mvhdp_group g);
  * member (the single handle's additions in the single handle's order: bit-identical), across processes by adding every rank's partial
  * result in rank order (equal to rounding; collective: every rank calls).  Arguments as for the single-handle functions. ---- */
 int mvhdp_group_set_hyper(mvhdp_group g, const mvhdp_hyper* hy);          /* every local member (replicated: every rank passes the same values) */
+/* mvhdp_remap_topics on every local member: each remaps its own entities' z and its replica of the counts, alpha and the inactive set.  The
+ * counts are replicated, so nothing is exchanged; every rank passes the same map, as with mvhdp_group_set_hyper.  MVHDP_ERR_STATE, nothing
+ * changed, unless the group is drained (no MVHDP_SWEEP_ASYNC_EXCHANGE in flight: mvhdp_group_drain) and not failed (no mvhdp_group_abort
+ * raised, every member's counts current: mvhdp_group_build_counts after a failed sweep); every member is asked for its own refusals
+ * before any of them remaps.  stats: moved and dropped summed over the local members; vacated and retired are those of the replicated model. */
+int mvhdp_group_remap_topics(mvhdp_group g, const mvhdp_remap_args* a, mvhdp_remap_stats* stats /* or NULL */);
 int mvhdp_group_log_likelihood(mvhdp_group g, double* log_likelihood /*[M]*/);
 int mvhdp_group_doc_topic_hist(mvhdp_group g, int32_t m, int32_t* hist /*[K][hist_len]*/, int32_t hist_len,
                                int32_t* doc_len_counts /*[len_len]*/, int32_t len_len);

@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
     "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_fold_in", "mvhdp_predict_items", "mvhdp_score_items",
     "mvhdp_nearest_entities", "mvhdp_nearest_probe", "mvhdp_topic_top_entities", "mvhdp_predict_entities", "mvhdp_rank_entities",
-    "mvhdp_topic_gram", "mvhdp_cohort_top_words",
+    "mvhdp_topic_gram", "mvhdp_cohort_top_words", "mvhdp_remap_topics",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "mvhdp_device_buffer", "mvhdp_counts_written", "mvhdp_set_stream", "mvhdp_synchronize",
     "mvhdp_group_create", "mvhdp_group_unique_id", "mvhdp_group_create_rank", "mvhdp_group_destroy", "mvhdp_group_last_error",
     "mvhdp_group_get_info", "mvhdp_group_set_exchange_chunks", "mvhdp_group_build_counts", "mvhdp_group_sweep", "mvhdp_group_abort", "mvhdp_group_drain",
-    "mvhdp_group_set_hyper", "mvhdp_group_log_likelihood", "mvhdp_group_doc_topic_hist", "mvhdp_group_count_histogram",
+    "mvhdp_group_set_hyper", "mvhdp_group_remap_topics", "mvhdp_group_log_likelihood", "mvhdp_group_doc_topic_hist", "mvhdp_group_count_histogram",
     "mvhdp_group_view_overlap_sums", "mvhdp_group_gamma_doc_statistics", "mvhdp_group_diagnostics",
 ]
 
@@ -211,6 +211,18 @@ class CohortStatsC(C.Structure):
                 ("cohorts_per_pass", C.c_int32), ("kernel_ms", C.c_double)]
 
 
+REMAP_RETIRE = 0x1                                  # MVHDP_REMAP_RETIRE
+
+
+class RemapArgsC(C.Structure):
+    _fields_ = [("map", C.c_void_p), ("flags", C.c_uint32)]
+
+
+class RemapStatsC(C.Structure):
+    _fields_ = [("moved", C.c_int64 * MAX_M), ("dropped", C.c_int64 * MAX_M), ("vacated", C.c_int32), ("retired", C.c_int32),
+                ("kernel_ms", C.c_double)]
+
+
 class NearestArgsC(C.Structure):
     _fields_ = [("view_weights", C.c_void_p), ("c0", C.c_int64), ("c1", C.c_int64), ("queries", C.c_void_p), ("nq", C.c_int64),
                 ("q0", C.c_int64), ("q1", C.c_int64), ("exclude_self", C.c_int32), ("n", C.c_int32), ("min_weight", C.c_double),
@@ -343,6 +355,8 @@ def load_library():
     L.mvhdp_rank_entities.argtypes = [vp, C.POINTER(EntitiesArgsC), i64, vp, vp, vp, vp]
     L.mvhdp_topic_gram.argtypes = [vp, C.POINTER(TopicGramArgsC), vp, vp, vp, vp, C.POINTER(TopicGramStatsC)]
     L.mvhdp_cohort_top_words.argtypes = [vp, C.POINTER(CohortArgsC), i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CohortStatsC)]
+    L.mvhdp_remap_topics.argtypes = [vp, C.POINTER(RemapArgsC), C.POINTER(RemapStatsC)]
+    L.mvhdp_group_remap_topics.argtypes = [vp, C.POINTER(RemapArgsC), C.POINTER(RemapStatsC)]
     L.mvhdp_nearest_entities.argtypes = [vp, C.POINTER(NearestArgsC), vp, vp, vp, C.POINTER(NearestStatsC)]
     L.mvhdp_nearest_probe.argtypes = [i64, i64, i32, i32, i32, C.POINTER(NearestStatsC)]
     L.mvhdp_topic_top_entities.argtypes = [vp, vp, i64, i64, i32, C.c_double, i64, i64, vp, vp, vp]

@@ -209,5 +209,9 @@ int mvhdp_doc_topic_prepare(mvhdp_ctx* h, DocTopicCarry& carry);
 
 // frees h->emb and its device buffers (mvhdp_emb.hip; release_device_resources calls it)
 void mvhdp_emb_free(mvhdp_ctx* h);
+// embeddings are initialised and hold a row per topic (with_topics)
+bool mvhdp_emb_has_topic_rows(const mvhdp_ctx* h);
+// every refusal of mvhdp_remap_topics (mvhdp_remap.hip), touching nothing: a group asks all its members before any of them remaps
+int mvhdp_remap_check(mvhdp_ctx* h, const mvhdp_remap_args* a);
 // the walk-threshold search the coming sweep belongs to: the mix flavours keep their own
 static inline WalkTuner& walk_tuner_of(mvhdp_ctx* h, uint32_t flags) { return (h->mm.mix && !(flags & MVHDP_SWEEP_FROZEN)) ? h->wt_mix : h->wt; }

@@ -404,6 +404,8 @@ void mvhdp_emb_free(mvhdp_ctx* h)
     h->emb = nullptr;
 }
 
+bool mvhdp_emb_has_topic_rows(const mvhdp_ctx* h) { return h->emb && h->emb->K > 0; }
+
 static int emb_ready(mvhdp_ctx* h)
 {
     if (!h->emb) FAIL(h, MVHDP_ERR_STATE, "embeddings: mvhdp_emb_init has not been called");

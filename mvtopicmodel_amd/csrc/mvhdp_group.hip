@@ -1137,6 +1137,28 @@ extern "C" int mvhdp_group_set_hyper(mvhdp_group g, const mvhdp_hyper* hy)
     return MVHDP_OK;
 }
 
+// mvhdp_remap_topics on every local member.  The counts are replicated and every member folds its own replica, so nothing goes on the wire;
+// every member is asked for its refusals before the first one changes anything.
+extern "C" int mvhdp_group_remap_topics(mvhdp_group g, const mvhdp_remap_args* a, mvhdp_remap_stats* stats)
+{
+    CHECK_G(g);
+    if (g->async_pending) GFAIL(g, MVHDP_ERR_STATE, "group_remap_topics: an asynchronous exchange is in flight (mvhdp_group_drain first)");
+    if (g->abort_raised) GFAIL(g, MVHDP_ERR_STATE, "group_remap_topics: mvhdp_group_abort was raised on this rank");
+    DeviceGuard dg;
+    for (size_t i = 0; i < g->members.size(); i++) GMEM(g, i, mvhdp_remap_check(g->members[i], a));
+    mvhdp_remap_stats sum{};
+    pack_reset(g);                                        // (new counts: the rows' classes are decided again)
+    for (size_t i = 0; i < g->members.size(); i++) {
+        mvhdp_remap_stats st{};
+        GMEM(g, i, mvhdp_remap_topics(g->members[i], a, &st));
+        for (int m = 0; m < MVHDP_MAX_MODALITIES; m++) { sum.moved[m] += st.moved[m]; sum.dropped[m] += st.dropped[m]; }
+        sum.vacated = st.vacated; sum.retired = st.retired;                 // (of the replicated model: the same on every member)
+        sum.kernel_ms += st.kernel_ms;
+    }
+    if (stats) *stats = sum;
+    return MVHDP_OK;
+}
+
 // modelLogLikelihood PTM:3322-3452 of the whole model: the document part summed over every entity of every member in entity order,
 // the model part (modalityCnt term, topic-word term, tokensPerTopic terms) once, from the replicated counts.
 extern "C" int mvhdp_group_log_likelihood(mvhdp_group g, double* out)

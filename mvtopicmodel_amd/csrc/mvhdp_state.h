@@ -1,6 +1,6 @@
 // mvhdp_state.h — what the device buffers of one handle currently hold (mvhdp_ctx::st), kept in one place: the fields are private, they
 // are read through the accessors and written ONLY by the transitions below, each of which records one event that happened to the
-// buffers.  The host-side sources (mvhdp_api.hip, mvhdp_enqueue.hip, mvhdp_group.hip, mvhdp_emb.hip, mvhdp_diag.hip) call these and
+// buffers.  The host-side sources (mvhdp_api.hip, mvhdp_enqueue.hip, mvhdp_group.hip, mvhdp_emb.hip, mvhdp_diag.hip, mvhdp_remap.hip) call these and
 // nothing else; tests/test_handle_state.py compiles this file with the host compiler: no HIP type in here.
 //
 // The rules the callers keep with it:
@@ -82,6 +82,7 @@ public:
     // A live sweep on the 16-bit mirror needs every row's total to be constant; a first visit of an unassigned token only adds to its
     // row, so while this holds live sweeps stay on the 32-bit table.
     bool any_unassigned() const { return unassigned_ != 0; }
+    bool view_unassigned(int m) const { return (unassigned_ >> m & 1u) != 0; }   // the same of view m alone
 
     // mvhdp_set_corpus: view m has new tokens, all unassigned (if it has any); the counts and trees of the old corpus mean nothing
     void corpus_replaced(int m, bool any_tokens) { set_unassigned(m, any_tokens); nslots_valid_ = false; have_counts_ = false; have_trees_ = false; }

@@ -13,6 +13,7 @@ import numpy as np
 
 from ._lib import (COHORT_BY_COUNT, COHORT_BY_SHARE, CohortArgsC, CohortStatsC, DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
                    EmbConfigC, EmbStatsC, EntitiesArgsC, EntitiesStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TopicGramArgsC, TopicGramStatsC, TuningC,
+                   REMAP_RETIRE, RemapArgsC, RemapStatsC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
@@ -416,6 +417,29 @@ class CohortWords:
         if self.types is None:
             raise ValueError("words needs a call that was not trends-only")
         return [(int(t) if vocabulary is None else vocabulary[int(t)], int(c)) for t, c in zip(self.types[g, k], self.counts[g, k]) if t >= 0]
+
+
+@dataclass
+class RemapStats:
+    """mvhdp_remap_stats: per view the tokens whose topic changed to another topic (moved [M]) and those that became unassigned (dropped
+    [M]); vacated = the topics no topic maps onto that held tokens or were active before, retired = those of them that are inactive
+    afterwards; kernel_ms = the stream's time over both passes."""
+    moved: np.ndarray = None
+    dropped: np.ndarray = None
+    vacated: int = 0
+    retired: int = 0
+    kernel_ms: float = 0.0
+
+
+def _remap_call(fn, handle, K, M, topic_map, retire):
+    """the arguments and the statistics of mvhdp_remap_topics / mvhdp_group_remap_topics; returns (rc, RemapStats)"""
+    tm = np.ascontiguousarray(topic_map, dtype=np.int32)
+    if tm.shape != (K,):
+        raise ValueError(f"remap_topics: the map must hold one entry per topic ({K}), got shape {tm.shape}")
+    a = RemapArgsC(tm.ctypes.data, REMAP_RETIRE if retire else 0)
+    st = RemapStatsC()
+    rc = fn(handle, C.byref(a), C.byref(st))
+    return rc, RemapStats(np.array(st.moved[:M], dtype=np.int64), np.array(st.dropped[:M], dtype=np.int64), st.vacated, st.retired, st.kernel_ms)
 
 
 def merge_topic_top_entities(parts, n):
@@ -1207,6 +1231,15 @@ class NativeSampler:
         return CohortWords(types, counts, nonzero, tokens, docs, CohortStats(**{f: getattr(st, f) for f, _ in CohortStatsC._fields_}))
 
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
+    # -- topic surgery (include/mvhdp.h mvhdp_remap_topics; mvtopicmodel_amd/surgery.py builds the maps) --
+    def remap_topics(self, topic_map, retire=False) -> RemapStats:
+        """Merge, drop and reorder topics in place: topic_map [K], map[k] = the topic that takes topic k's tokens, -1 = they become
+        unassigned; one hop, never chased.  The assignments, the counts, alpha and the inactive set move together and every kind of sweep
+        goes on afterwards.  retire: the topics nothing maps onto join the inactive set, so that a later birth can take their index."""
+        rc, st = _remap_call(self.L.mvhdp_remap_topics, self.h, self.K, self.M, topic_map, retire)
+        self._ck(rc)
+        return st
+
     def top_words(self, m, n):
         """getSortedWords(m) PTM:1792-1811 cut at n: (types [K][n] (-1 unfilled), counts [K][n], nonzero [K])."""
         n = int(n)
@@ -1551,6 +1584,14 @@ class NativeGroup:
     def set_vectors_mix(self, lam, exp_dot=None, sum_exp=None):
         for s in self.members:                  # (every member carries its own copy of the table; the group checks that they agree)
             s.set_vectors_mix(lam, exp_dot, sum_exp)
+
+    def remap_topics(self, topic_map, retire=False) -> RemapStats:
+        """NativeSampler.remap_topics on every local member (every rank passes the same map); moved and dropped are summed over them.
+        Refused unless the group is drained and not failed."""
+        s0 = self.members[0]
+        rc, st = _remap_call(self.L.mvhdp_group_remap_topics, self.g, s0.K, s0.M, topic_map, retire)
+        self._ck(rc)
+        return st
 
     def model_log_likelihood(self):
         M = self.members[0].M
