@@ -1073,6 +1073,19 @@ int mvhdp_plan_probe(const mvhdp_plan_input* in, const mvhdp_tuning* tuning /* o
 int mvhdp_tuner_probe(int32_t num_modalities, const double* tree_branch_share /*[M]*/, const double* u1_hist /*[20] or NULL*/,
                       const double* ns_by_step /*[21]*/, int32_t n_sweeps, int32_t group, int32_t* steps_out /*[n_sweeps]*/);
 
+/* ---- the launch census: which compiled sweep kernel ran, over how many tokens (diagnostics; off by default, per handle) ----
+ * The sweep is compiled 60 times -- the 56 instantiations of the register-resident kernel (rmax, debug, walk, narrow, roomy, liverows, mix:
+ * its template arguments) and the four builds of the generic kernel (rmax = 0: debug, mix) -- and which of them a class launch gets is
+ * decided by the planner, the tuning block and the environment.  With the census on, every class launch is counted where its kernel is looked
+ * up (launches) and counts its statistics into a block of its own, which a small kernel behind the segment adds into the sweep's counters and,
+ * by its tokens, into the row of that kernel (tokens: a launch over an empty queue counts as a launch and adds none).  Nothing a sweep
+ * returns or leaves behind changes; with the census off nothing is allocated or enqueued for it.
+ * enable: 1 on, 0 off, -1 leave as is; reset != 0 zeroes the tallies; rows: [cap] or NULL; *n_rows (may be NULL) = the rows that exist (60),
+ * always in the same order. */
+typedef struct { int32_t rmax /* 0: the generic kernel */, debug, walk, narrow, roomy, liverows, mix, reserved;
+                 int64_t launches, tokens; } mvhdp_census_row;
+int mvhdp_sweep_census(mvhdp_handle h, int32_t enable, int32_t reset, mvhdp_census_row* rows, int32_t cap, int32_t* n_rows);
+
 /* ---- document shards on several GPUs: the exchange step inside the library ----
  * What the reference keeps inside its own process -- the nst x nut queue mesh between sampler and updater threads and the
  * barrier that ends an iteration (PTM:1042-1049, PTM:1232) -- for samplers that are GPUs: every member handle holds a

@@ -25,6 +25,7 @@ ABI_SYMBOLS = [
     "mvhdp_emb_word_stats", "mvhdp_emb_sampling_table", "mvhdp_emb_softmax", "mvhdp_emb_nearest", "mvhdp_emb_release",
     "mvhdp_set_vectors_mix", "mvhdp_get_vectors_mix",
     "mvhdp_sweep", "mvhdp_sweep_many", "mvhdp_get_tuning", "mvhdp_set_tuning", "mvhdp_plan_probe", "mvhdp_tuner_probe",
+    "mvhdp_sweep_census",
     "mvhdp_apply_delta", "mvhdp_apply_delta_begin", "mvhdp_apply_delta_rows", "mvhdp_apply_delta_end",
     "mvhdp_get_birth_keys", "mvhdp_activate_births",
     "mvhdp_trees_current", "mvhdp_get_view_weights",
@@ -79,6 +80,11 @@ class TuningC(C.Structure):
                 ("walk_theta", C.c_double * MAX_M), ("primary_min_share", C.c_double),
                 ("learnt_walk_step", C.c_int32 * 4), ("tree_branch_share", C.c_double * MAX_M),
                 ("live_overlap", C.c_int32), ("live_rows", C.c_int32)]
+
+
+class CensusRowC(C.Structure):
+    _fields_ = [("rmax", C.c_int32), ("debug", C.c_int32), ("walk", C.c_int32), ("narrow", C.c_int32), ("roomy", C.c_int32),
+                ("liverows", C.c_int32), ("mix", C.c_int32), ("reserved", C.c_int32), ("launches", C.c_int64), ("tokens", C.c_int64)]
 
 
 class GroupInfoC(C.Structure):
@@ -384,6 +390,7 @@ def load_library():
     L.mvhdp_set_tuning.argtypes = [vp, C.POINTER(TuningC)]
     L.mvhdp_plan_probe.argtypes = [C.POINTER(PlanInputC), C.POINTER(TuningC), C.POINTER(PlanOutputC)]
     L.mvhdp_tuner_probe.argtypes = [i32, vp, vp, vp, i32, i32, vp]
+    L.mvhdp_sweep_census.argtypes = [vp, i32, i32, C.POINTER(CensusRowC), i32, C.POINTER(i32)]
     L.mvhdp_apply_delta.argtypes = [vp, i32, i32]
     L.mvhdp_apply_delta_begin.argtypes = [vp]
     L.mvhdp_apply_delta_rows.argtypes = [vp, i64, i64]

@@ -226,6 +226,7 @@ static void release_device_resources(mvhdp_ctx* h)
     if (h->h_ctl) { hipHostFree(h->h_ctl); h->h_ctl = nullptr; }
     h->d_stats = nullptr; h->d_act_key = nullptr; h->d_doc_counter = nullptr; h->d_ovf_meta = nullptr;
     fr(h->d_doc_order); fr(h->d_lists); fr(h->d_nslots); fr(h->d_stats_many); fr(h->d_heavy_list); fr(h->d_heavy_ctl);
+    fr(h->census.d_blocks); fr(h->census.d_tally); h->census.on = false;
     if (h->ev_rf_go) { hipEventDestroy(h->ev_rf_go); h->ev_rf_go = nullptr; }
     if (h->ev_rf_done) { hipEventDestroy(h->ev_rf_done); h->ev_rf_done = nullptr; }
     if (h->rf_stream) { hipStreamDestroy(h->rf_stream); h->rf_stream = nullptr; }

@@ -6,6 +6,7 @@
 #include "mvhdp_plan.h"
 #include "mvhdp_state.h"
 #include "mvhdp_scratch.h"
+#include "mvhdp_census.h"
 
 #include <algorithm>
 #include <functional>
@@ -111,6 +112,15 @@ struct mvhdp_ctx {
     float* d_mix32 = nullptr;                // its fp32 rounding (MvModel::mix32)
     double mix_lambda = 0.0;
     WalkTuner wt_mix;
+    // The launch census (mvhdp_sweep_census, mvhdp_census.h), off by default: with it on, every class launch of a segment counts into a
+    // statistics block of its own, which a fold kernel behind the segment adds into the sweep's counters and, by its tokens, into the tally
+    // of the kernel the launch took.  Two sets of blocks: two segments may be in flight (enqueue_overlapped), each on its own set.
+    struct Census {
+        bool on = false;
+        unsigned long long* d_blocks = nullptr;  // [2][MVHDP_N_CLASSES][ST_COUNT]
+        unsigned long long* d_tally = nullptr;   // [MVHDP_CENSUS_ROWS] tokens
+        long long launches[MVHDP_CENSUS_ROWS] = {0};
+    } census;
 };
 
 

@@ -161,6 +161,7 @@ struct SegCtl {
     unsigned int* class_counts;        // [MVHDP_N_CLASSES] lengths of the route pass's lists
     unsigned long long* qheads;        // [8] one work-queue head per kernel class
     int32_t* lists;                    // [MVHDP_N_CLASSES][D] entity lists (nullptr: the handle's own, allocated on first use)
+    int census_set = 0;                // the launch census' set of statistics blocks (mvhdp_ctx::Census): the second one for the second segment in flight
 };
 
 // Route pass + every class kernel of segment `seg` on stream s (the wider classes on the side streams behind a fork event, joined
@@ -190,6 +191,15 @@ static hipError_t launch_segment_kernels(mvhdp_ctx* h, const SweepPlan& p, const
         ClassifyArgs ca{};
         int32_t* lists = ctl.lists ? ctl.lists : h->d_lists;
         bool used_stream[PLAN_N_STREAMS] = {};
+        // the launch census: a zeroed block per class launch instead of the sweep's counters, folded into them behind the join events below.
+        // This set's last fold sits in front of this on the same stream.
+        CensusFold cf{};
+        unsigned long long* census_blocks = nullptr;
+        if (h->census.on) {
+            census_blocks = h->census.d_blocks + (size_t)ctl.census_set * MVHDP_N_CLASSES * ST_COUNT;
+            step(hipMemsetAsync(census_blocks, 0, (size_t)MVHDP_N_CLASSES * ST_COUNT * sizeof(unsigned long long), s));
+            cf.blocks = census_blocks; cf.stats = d_stats; cf.tally = h->census.d_tally;
+        }
         if (p.route && H_seg > 0) {
             if (!ctl.lists && !h->d_lists) step(hipMalloc(&h->d_lists, (size_t)MVHDP_N_CLASSES * mm.D * sizeof(int32_t)));
             lists = ctl.lists ? ctl.lists : h->d_lists;
@@ -251,11 +261,18 @@ static hipError_t launch_segment_kernels(mvhdp_ctx* h, const SweepPlan& p, const
                     n_c = std::min<int64_t>(H_seg, (int64_t)(2 * cnt / (unsigned)nseg) + 64);
                 }
             }
-            if (g.fast) step(mvhdp_launch_sweep_fast(mk, sc, g.r, blocks_for(n_c, g), p.debug, st));
-            else step(mvhdp_launch_sweep(mk, sc, blocks_for(n_c, g), p.debug, st));
+            int row = -1;
+            if (census_blocks) sc.stats = census_blocks + (size_t)cf.n * ST_COUNT;
+            if (g.fast) step(mvhdp_launch_sweep_fast_row(mk, sc, g.r, blocks_for(n_c, g), p.debug, st, &row));
+            else step(mvhdp_launch_sweep_row(mk, sc, blocks_for(n_c, g), p.debug, st, &row));
+            if (census_blocks) {
+                cf.row[cf.n++] = row;
+                if (row >= 0) h->census.launches[row]++;
+            }
         }
         for (int si = 1; si < PLAN_N_STREAMS; si++) if (used_stream[si]) step(hipEventRecord(h->ev_join[si], h->side[si]));
         for (int si = 1; si < PLAN_N_STREAMS; si++) if (used_stream[si]) step(hipStreamWaitEvent(s, h->ev_join[si], 0));
+        if (census_blocks) { const hipError_t ef = mvhdp_launch_census_fold(cf, s); step(ef); }   // (whatever failed above: what did run is counted)
     }
     return e;
 }
@@ -451,7 +468,7 @@ static int enqueue_overlapped(mvhdp_ctx* h, const SweepPlan& p, uint32_t sweep_i
     } else if (flags & MVHDP_SWEEP_NO_APPLY) {                     // (live, document shards: the caller wants after - before)
         step(mvhdp_launch_live_helper(mm, 0, d_stats, X[0])); h->st.delta_written(false);
     }
-    SegCtl ctl[2] = {{h->d_ovf_meta + META_CLASS_COUNTS, h->d_doc_counter, nullptr}, {(unsigned int*)(ov.ctl2 + 8), ov.ctl2, ov.lists2}};
+    SegCtl ctl[2] = {{h->d_ovf_meta + META_CLASS_COUNTS, h->d_doc_counter, nullptr}, {(unsigned int*)(ov.ctl2 + 8), ov.ctl2, ov.lists2, 1}};
     step(mvhdp_launch_ctl_reset(d_stats, ST_COUNT, h->d_act_key, (unsigned long long*)h->d_ovf_meta, META_WORDS64, nullptr, nullptr, X[0]));
     step(hipEventRecord(ev_k0, X[0]));
     step(hipEventRecord(ov.ev_start, X[0]));
@@ -920,4 +937,42 @@ extern "C" int mvhdp_sweep_many(mvhdp_handle h, uint32_t first_idx, int32_t n, u
     learn_from_sweep(h, p, acc.data(), meta + META_HIST, ms_sum, comparable);
     if (!p.frozen && acc[ST_ABORT] == 0) h->st.every_token_assigned();
     return ret;
+}
+
+// The launch census (include/mvhdp.h).  Switching it on allocates the blocks and the tally; they stay until the handle goes.
+extern "C" int mvhdp_sweep_census(mvhdp_handle h, int32_t enable, int32_t reset, mvhdp_census_row* rows, int32_t cap, int32_t* n_rows)
+{
+    CHECK_H(h);
+    static_assert(MVHDP_CENSUS_ROWS == 60, "include/mvhdp.h says 60 rows");
+    if (enable < -1 || enable > 1 || cap < 0 || (rows == nullptr && cap > 0)) FAIL(h, MVHDP_ERR_INVALID_ARG, "sweep_census: enable is -1, 0 or 1; rows with a capacity");
+    auto& cs = h->census;
+    HIPC(h, hipSetDevice(h->device));
+    HIPC(h, hipStreamSynchronize(h->stream));
+    if (enable == 1 && !cs.d_blocks) HIPC(h, hipMalloc(&cs.d_blocks, (size_t)2 * MVHDP_N_CLASSES * ST_COUNT * sizeof(unsigned long long)));
+    if (enable == 1 && !cs.d_tally) {
+        HIPC(h, hipMalloc(&cs.d_tally, MVHDP_CENSUS_ROWS * sizeof(unsigned long long)));
+        HIPC(h, hipMemset(cs.d_tally, 0, MVHDP_CENSUS_ROWS * sizeof(unsigned long long)));
+    }
+    if (enable >= 0) cs.on = enable == 1;
+    if (reset) {
+        std::fill(cs.launches, cs.launches + MVHDP_CENSUS_ROWS, 0LL);
+        if (cs.d_tally) HIPC(h, hipMemset(cs.d_tally, 0, MVHDP_CENSUS_ROWS * sizeof(unsigned long long)));
+    }
+    if (n_rows) *n_rows = MVHDP_CENSUS_ROWS;
+    if (!rows) return MVHDP_OK;
+    unsigned long long tally[MVHDP_CENSUS_ROWS] = {0};
+    if (cs.d_tally) HIPC(h, hipMemcpy(tally, cs.d_tally, sizeof tally, hipMemcpyDeviceToHost));
+    for (int i = 0; i < std::min<int>(cap, MVHDP_CENSUS_ROWS); i++) {
+        mvhdp_census_row& r = rows[i];
+        r = mvhdp_census_row{};
+        if (i < MVHDP_N_FAST_FLAVOURS) {
+            const FastFlavour& f = mvhdp_fast_flavours[i];
+            r.rmax = f.rmax; r.debug = f.debug; r.walk = f.walk; r.narrow = f.narrow; r.roomy = f.roomy; r.liverows = f.liverows; r.mix = f.mix;
+        } else {
+            const int g = i - MVHDP_N_FAST_FLAVOURS;             // (mvhdp_census_generic_row: debug + 2 * mix)
+            r.debug = g & 1; r.mix = g >> 1;
+        }
+        r.launches = cs.launches[i]; r.tokens = (int64_t)tally[i];
+    }
+    return MVHDP_OK;
 }

@@ -1122,11 +1122,41 @@ int mvhdp_sweep_generic_regs(bool debug, bool mix)
     return a.numRegs;
 }
 
-hipError_t mvhdp_launch_sweep(const MvModel& mm, const SweepLaunch& sl, int grid_blocks, bool debug, hipStream_t s)
+#include "mvhdp_census.h"
+// (row: the launch census, mvhdp_census.h -- which of the four builds this launch took)
+hipError_t mvhdp_launch_sweep_row(const MvModel& mm, const SweepLaunch& sl, int grid_blocks, bool debug, hipStream_t s, int* row)
 {
     const size_t lds = sl.block_shared_bytes + (size_t)sl.waves_per_block * sl.wave_bytes;
     void* args[] = {(void*)&mm, (void*)&sl};
+    if (row) *row = mvhdp_census_generic_row(debug, mm.mix != nullptr);
     (void)hipLaunchKernel(generic_sweep_kernel(debug, mm.mix != nullptr), dim3(grid_blocks), dim3(64 * sl.waves_per_block), args, lds, s);
+    return hipGetLastError();
+}
+
+hipError_t mvhdp_launch_sweep(const MvModel& mm, const SweepLaunch& sl, int grid_blocks, bool debug, hipStream_t s)
+{
+    return mvhdp_launch_sweep_row(mm, sl, grid_blocks, debug, s, nullptr);
+}
+
+// The launch census (mvhdp_census.h): a segment's class launches each counted into a block of their own; this adds the blocks into the
+// sweep's counters -- atomically: the folds of two segments in flight meet there -- and every block's tokens into its kernel's tally.
+__global__ __launch_bounds__(256) void census_fold_kernel(CensusFold cf)
+{
+    for (int i = threadIdx.x; i < ST_COUNT; i += blockDim.x) {
+        unsigned long long v = 0;
+        for (int b = 0; b < cf.n; b++) v += cf.blocks[(size_t)b * ST_COUNT + i];
+        if (v) atomicAdd(&cf.stats[i], v);
+    }
+    if ((int)threadIdx.x < cf.n && cf.row[threadIdx.x] >= 0) {
+        const unsigned long long t = cf.blocks[(size_t)threadIdx.x * ST_COUNT + ST_TOKENS];
+        if (t) atomicAdd(&cf.tally[cf.row[threadIdx.x]], t);
+    }
+}
+
+hipError_t mvhdp_launch_census_fold(const CensusFold& cf, hipStream_t s)
+{
+    if (cf.n <= 0) return hipSuccess;
+    hipLaunchKernelGGL(census_fold_kernel, dim3(1), dim3(256), 0, s, cf);
     return hipGetLastError();
 }
 

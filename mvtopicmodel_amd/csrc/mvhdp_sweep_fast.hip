@@ -945,24 +945,34 @@ __global__ __launch_bounds__(256, fast_launch_bound(RMAX, WALK, ROOMY, LIVEROWS,
 #undef sn_set
 
 // The instantiations that exist -- mvhdp_flavour.h lists them, once -- each with its key; what a launch and a register query look up
+#include "mvhdp_census.h"
 struct FastKernel { FastFlavour key; const void* fn; };
 #define FAST_KERNEL_ROW(R, D, W, N, RO, L, MX) {{R, D, W, N, RO, L, MX}, (const void*)sweep_fast_kernel<R, D, W, N, RO, L, MX>},
 static const FastKernel fast_kernels[] = { MVHDP_FAST_FLAVOURS(FAST_KERNEL_ROW) };
 #undef FAST_KERNEL_ROW
 
-// the kernel of a request; null: a request no plan makes, or (an internal error) a flavour the rule names and the list does not hold
-static const void* fast_kernel(const FastRequest& q)
+// the kernel of a request, as its place in the list; -1: a request no plan makes, or (an internal error) a flavour the rule names and
+// the list does not hold
+static int fast_kernel_index(const FastRequest& q)
 {
     FastFlavour f;
-    if (!mvhdp_fast_resolve(q, &f)) return nullptr;
-    for (const FastKernel& k : fast_kernels) if (k.key == f) return k.fn;
-    return nullptr;
+    if (!mvhdp_fast_resolve(q, &f)) return -1;
+    for (int i = 0; i < MVHDP_N_FAST_FLAVOURS; i++) if (fast_kernels[i].key == f) return i;
+    return -1;
+}
+static const void* fast_kernel(const FastRequest& q)
+{
+    const int i = fast_kernel_index(q);
+    return i < 0 ? nullptr : fast_kernels[i].fn;
 }
 
-hipError_t mvhdp_launch_sweep_fast(const MvModel& mm, const SweepLaunch& sl, int rmax, int grid_blocks, bool debug, hipStream_t s)
+// (row: the launch census, mvhdp_census.h -- the place in the list of the kernel this launch took)
+hipError_t mvhdp_launch_sweep_fast_row(const MvModel& mm, const SweepLaunch& sl, int rmax, int grid_blocks, bool debug, hipStream_t s, int* row)
 {
-    const void* f = fast_kernel({rmax, mm.K, debug, sl.walk != 0, sl.narrow, sl.live_rows != 0, sl.live16 != 0, mm.mix != nullptr, mm.counts12 != nullptr});
-    if (!f) return hipErrorInvalidValue;
+    const int i = fast_kernel_index({rmax, mm.K, debug, sl.walk != 0, sl.narrow, sl.live_rows != 0, sl.live16 != 0, mm.mix != nullptr, mm.counts12 != nullptr});
+    if (row) *row = i;
+    if (i < 0) return hipErrorInvalidValue;
+    const void* f = fast_kernels[i].fn;
     const size_t lds = sl.block_shared_bytes + (size_t)sl.waves_per_block * sl.wave_bytes;
     if (lds > 65536) {
         hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -972,6 +982,11 @@ hipError_t mvhdp_launch_sweep_fast(const MvModel& mm, const SweepLaunch& sl, int
     void* args[] = {(void*)&mm, (void*)&sl};
     (void)hipLaunchKernel(f, dim3(grid_blocks), dim3(64 * sl.waves_per_block), args, lds, s);
     return hipGetLastError();
+}
+
+hipError_t mvhdp_launch_sweep_fast(const MvModel& mm, const SweepLaunch& sl, int rmax, int grid_blocks, bool debug, hipStream_t s)
+{
+    return mvhdp_launch_sweep_fast_row(mm, sl, rmax, grid_blocks, debug, s, nullptr);
 }
 
 int mvhdp_sweep_kernel_regs(int cls, int flavour, bool mix)

@@ -7,11 +7,12 @@ import atexit
 import ctypes as C
 import sys
 import weakref
+from collections import namedtuple
 from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (COHORT_BY_COUNT, COHORT_BY_SHARE, CohortArgsC, CohortStatsC, DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
+from ._lib import (CensusRowC, COHORT_BY_COUNT, COHORT_BY_SHARE, CohortArgsC, CohortStatsC, DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
                    EmbConfigC, EmbStatsC, EntitiesArgsC, EntitiesStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TopicGramArgsC, TopicGramStatsC, TuningC,
                    REMAP_RETIRE, RemapArgsC, RemapStatsC,
                    load_library,
@@ -44,6 +45,9 @@ BUF_BIRTH_KEYS = 2
 BUF_COUNTS12 = 3        # read-only views for tests and diagnostics: the 12-bit image of n_wk and the row classes
 BUF_ROW_CLASS = 4
 ACT_KEY_NONE = (1 << 63) - 1
+
+# a row of the launch census (NativeSampler.sweep_census): key = (rmax, debug, walk, narrow, roomy, liverows, mix)
+CensusRow = namedtuple("CensusRow", "key launches tokens")
 
 
 def _ptr(a):
@@ -1406,6 +1410,16 @@ class NativeSampler:
         arr = (SweepStatsC * max(int(n), 1))()
         self._ck(self.L.mvhdp_sweep_many(self.h, int(first_idx), int(n), int(seed), int(flags), C.cast(arr, C.c_void_p)))
         return [SweepStats(**{f: getattr(arr[i], f) for f, _ in SweepStatsC._fields_}) for i in range(int(n))]
+
+    def sweep_census(self, enable=None, reset=False):
+        """The launch census (mvhdp_sweep_census): one CensusRow per compiled sweep kernel -- its key (rmax, debug, walk, narrow, roomy,
+        liverows, mix; rmax 0: the generic kernel), the launches it got and the tokens they sampled since the last reset.
+        enable True / False switches the census of this handle on / off, None leaves it; the rows are read after the reset."""
+        n = C.c_int32(0)
+        self._ck(self.L.mvhdp_sweep_census(self.h, -1, 0, None, 0, C.byref(n)))
+        arr = (CensusRowC * n.value)()
+        self._ck(self.L.mvhdp_sweep_census(self.h, -1 if enable is None else int(bool(enable)), int(bool(reset)), arr, n.value, None))
+        return [CensusRow((r.rmax, r.debug, r.walk, r.narrow, r.roomy, r.liverows, r.mix), r.launches, r.tokens) for r in arr]
 
     # -- tuning (never changes a result) --------------------------------------------
     def get_tuning(self):

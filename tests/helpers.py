@@ -138,10 +138,12 @@ def run_deferred_ladders(ev, flips, forced, js=near_ties.THIN_JS, runs=every_run
         assert served_class(case, R) == R.bit_length() - 1, f"force_primary {R} would not be what serves the entities of {case.name}"
         s = make_native(case, case.hy, case.z0)
         s.set_tuning(force_primary=R)
+        s.sweep_census(enable=True, reset=True)
         flav["rmax%d" % R] = (s, 0)
     for name in others:
         flav[name] = (make_native(case, case.hy, case.z0), flags_of[name])
     fb = {name: {} for name in flav}
+    sampled = {name: 0 for name in flav}
     dropped, kept = [0], 0
     for fi, f in enumerate(flips):
         for rung in near_ties.ladder(ev, f, js, dropped):
@@ -160,6 +162,15 @@ def run_deferred_ladders(ev, flips, forced, js=near_ties.THIN_JS, runs=every_run
                 except AssertionError as e:
                     raise AssertionError(f"{where}: {e}") from None
                 fb[name][(fi, rung.j, rung.side)] = rs.exact_fallbacks
+                sampled[name] += rs.tokens
+    # the launch census of every forced variant: it was the R-round kernel that sampled every token of every comparison above
+    for R in forced:
+        rows = flav["rmax%d" % R][0].sweep_census()
+        by_rounds = {}
+        for r in rows:
+            by_rounds[r.key[0]] = by_rounds.get(r.key[0], 0) + r.tokens
+        assert by_rounds.get(R, 0) == sampled["rmax%d" % R] == sum(by_rounds.values()), \
+            f"force_primary {R} on {case.name}: {sampled['rmax%d' % R]} tokens sampled, by kernel rounds {by_rounds}"
     for s, _ in flav.values():
         s.close()
     assert dropped[0] * 20 <= kept + dropped[0], f"{dropped[0]} rungs of {kept + dropped[0]} abandoned by the oracle"

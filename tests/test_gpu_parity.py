@@ -445,18 +445,27 @@ def test_wide_variants_on_the_32_bit_table(force, what, monkeypatch):
     """Rows of K >= 256 are gathered from the 16-bit mirror, so the flavours of the 8- and 16-round variants that read the 32-bit table run
     only with the mirror switched off (set_tuning(narrow=0)): the plain one (no view gets a walk threshold -- alpha = 5 sends three
     tokens in four to the tree branch, and a view is steered only below 0.35 -- so every sweep after the first, which measures, runs it),
-    the walk flavour under a fixed threshold, the debug one.  Deferred sweeps: every integer is the oracle's."""
+    the walk flavour under a fixed threshold, the debug one.  Deferred sweeps: every integer is the oracle's, and the launch census
+    (NativeSampler.sweep_census) says that the named flavour is the kernel of the forced variant that sampled them."""
     monkeypatch.setenv("MVHDP_FORCE_RMAX", force)
     c = wide_corpus()
     hy = Hyper.defaults(c.K, c.V, alpha=5.0 if what == "plain" else 0.1)
     o = make_oracle(c, hy)
     s = make_native(c, hy, [o.get_assignments(m) for m in range(c.M)])
     s.set_tuning(narrow=0, **(dict(walk_fixed=1, walk_theta=[0.3, 0.3]) if what == "walk" else {}))
+    s.sweep_census(enable=True, reset=True)
     for it in range(3):
         ro = o.sweep(it, 17)
         rs = s.sweep(it, 17, want_dbg=(what == "debug"))
         assert (rs.tokens, rs.changed) == (ro["stats"]["tokens"], ro["stats"]["changed"])
         assert_same_state(o, s, c.M)
+        if what == "plain" and it == 0:                      # (the sweep that measures runs the walk flavour: counted apart)
+            s.sweep_census(reset=True)
+    # the launch census: of the forced variant's kernels, the named flavour on the 32-bit table is the one that sampled tokens
+    R = int(force)
+    named = (R, int(what == "debug"), int(what != "plain"), 0, 0, 0, 0)
+    sampled = {r.key: r.tokens for r in s.sweep_census() if r.tokens}
+    assert sampled.get(named, 0) > 0 and [k for k in sampled if k[0] == R] == [named], sampled
     s.close()
 
 
