@@ -860,7 +860,7 @@ int mvhdp_cohort_top_words(mvhdp_handle h, const mvhdp_cohort_args* a, int64_t n
  *   rows of MVHDP_BUF_COUNTS, a wave per row, the row held in registers and folded through LDS in place: 4 bytes read per token and per
  *   count cell, written only where something changed.  profiles/remap_topics.md has the figures.
  * Not done: the reference's own discriminative-weight delete rule (PTM:773-809: the host builds the map, mvtopicmodel_amd/surgery.py has
- *   merge, prune and order maps), splitting a topic, a JNI class.
+ *   merge, prune and order maps), a JNI class.  Splitting a topic is mvhdp_split_topic below.
  * mvhdp_remap_args: a pointer and a uint32 (16 bytes).  mvhdp_remap_stats: int64 moved[8], dropped[8]; int32 vacated, retired; double
  *   kernel_ms (144 bytes).  tests/test_remap_kats.py pins both. */
 #define MVHDP_REMAP_RETIRE 0x1u   /* vacated topics join the inactive set (ours); without it they stay active with alpha 0, as PTM:751 leaves them */
@@ -875,6 +875,84 @@ typedef struct {
     double kernel_ms;
 } mvhdp_remap_stats;
 int mvhdp_remap_topics(mvhdp_handle h, const mvhdp_remap_args* a, mvhdp_remap_stats* stats /* or NULL */);
+
+/* ---- topic surgery, the opposite move: cut one topic in two on the trained handle, with a Gibbs sampler restricted to the tokens of that
+ * topic and to two outcomes.  The reference has no counterpart (its unfinished mergeSimilarTopics only merges): THIS definition is ours;
+ * tests/native/split_ref.c restates this paragraph sequentially and the device equals it integer for integer and bit for bit.  For a
+ * truncated HDP a split is also the deliberate form of a birth: the target is a free index, usually one of the inactive set.
+ * The split set: every position n of every view m with z[m][n] == source.  Every other position and every other topic's counts stay byte
+ *   for byte as they were.  During the call a token of the set carries a side, a (it stays in source) or b (it goes to target).
+ * The target: a topic index != source that holds no token in any view (n_k[m][target] == 0) and whose alpha[m][target] is exactly 0.0 in
+ *   every view, else MVHDP_ERR_INVALID_ARG.  target == -1: the library picks the lowest index of the inactive set that meets these
+ *   conditions; MVHDP_ERR_INVALID_ARG ("no free topic") if there is none.
+ * Constants of the call, per view, fp64, every operation rounded on its own (no fused multiply-add):
+ *   ah_m = 0.5 * alpha[m][source];  A_m = gamma[m] * ah_m, the same for both sides;  Lp_m = (double)len_m + gamma[m] * alphaSum[m] per
+ *   entity, len_m the entity's WHOLE view-m span, as in mvhdp_fold_in;  P = args.coupling: exactly the fold-in's matrix, its default for
+ *   NULL and its validation.
+ * Iteration 0, the initial sides: a token of type w with type_hint[m][w] == 0 or 1 takes that side; every other token (hint -1, a NULL
+ *   row, a NULL array) takes b iff u >= 0.5, else a.  u = bits_to_unit(x0, x1) of Philox4x32-10 with key = seed (low word, high word) and
+ *   counter (low 32 bits of g,  high 32 bits of g,  it + m * 2^16,  pos), g = doc_id_base + d, it = 0, pos = the position inside the
+ *   entity's view-m span: the fold-in's counter.  A hint value outside {-1, 0, 1}: MVHDP_ERR_INVALID_ARG.
+ * Iteration it = 1 .. iterations: the word counts are FROZEN for the whole iteration (the library's deferred discipline):
+ *   c_w[m][w][x] and c[m][x], x in {a, b}, are the counts of the sides as the previous iteration left them; per view and side two
+ *   reciprocals per iteration, r0 = 1.0 / ((double)c[m][x] + betaSum[m]) and r1 = 1.0 / ((double)(c[m][x] - 1) + betaSum[m]).  Entities
+ *   are independent of each other within an iteration.  Inside an entity the views go in ascending m and within a view the positions of the
+ *   split set in ascending order; the entity's own side counts e[m][x] are LIVE.  At the start of view m's pass, for x in {a, b}, in the
+ *   fold-in's operation order:
+ *     s = 0.0;  for i ascending, i != m, len_i != 0:  s = s + P[m][i] * ((double)e[i][x] + A_i) / Lp_i   (product, then quotient);
+ *     base[x] = A_m + s * Lp_m.
+ *   A view in which the entity has no token of the set has no pass.  A visit of a token of type w currently on side y: take it out of
+ *   e[m][y];  for each x with own = (x == y):  phi[x] = ((double)(c_w[m][w][x] - own) + beta[m]) * (own ? r1 : r0)[x];
+ *   wt[x] = (P[m][m] * (double)e[m][x] + base[x]) * phi[x];  total = wt[a] + wt[b];  the token goes to a iff u * total < wt[a], else to
+ *   b, u as above with this it;  total == 0.0 or not finite: the token keeps y;  add it to e[m] of its new side.  A visit has no divide.
+ *   flips[it - 1] = the tokens whose side changed in iteration it.
+ * Afterwards: z holds source or target for the set; the counts are exactly the recount of the new z (mvhdp_build_counts would change
+ *   nothing); alpha'[m][source] = alpha'[m][target] = ah_m (0.5 a + 0.5 a == a bitwise unless ah_m is subnormal) -- with
+ *   MVHDP_SPLIT_KEEP_ALPHA the source keeps its alpha and the target gets ah_m, and alpha_sum is the host's business, as after
+ *   mvhdp_remap_topics.  alpha[m][K], alpha_sum and every other field of mvhdp_hyper are untouched.  The target leaves the inactive set
+ *   (stats.activated), first_inactive is recomputed and MVHDP_BUF_BIRTH_KEYS is reset to MVHDP_ACT_KEY_NONE.  The handle is in the state
+ *   mvhdp_remap_topics leaves: the counts current, the trees outdated, the slot counts, the 16-bit and 12-bit images and the row classes
+ *   rewritten by the next sweep's own preparation; every kind of sweep goes on from there and equals, integer for integer, a fresh
+ *   handle loaded with z', alpha', inactive' (tests/test_gpu_split.py).
+ * Refusals, checked whole before anything changes (z, counts, alpha and inactive stay byte for byte): those of mvhdp_remap_topics --
+ *   MVHDP_ERR_STATE before mvhdp_set_corpus of every view or mvhdp_set_hyper, with counts that are not current or a MVHDP_SWEEP_NO_APPLY
+ *   sweep's deltas pending, inside an mvhdp_apply_delta_begin bracket; MVHDP_ERR_UNSUPPORTED while a vectors mix is set, embeddings with
+ *   topic rows are initialised, or K > 2048 -- and MVHDP_ERR_INVALID_ARG for a NULL a, source or target out of range (target below -1 or
+ *   >= K), source == target, a source in the inactive set, an unknown flag, iterations outside 0 .. 65535 (the counter's 16 bits), a bad
+ *   coupling or hint, the target's conditions above.  -1 for a NULL handle.  A source without tokens is MVHDP_OK with zeros: the target
+ *   is still activated and alpha still halved.
+ * stats (or NULL): split[m] = the view-m tokens of the set, moved[m] = of those, in the target at the end; flips_last = flips of the last
+ *   iteration (0 with iterations == 0); target = the index used, activated = 1 if it left the inactive set; kernel_ms = the stream's time
+ *   over the kernels of the call.
+ * Guarantees: two calls with the same arguments on the same state give the same bytes (kernel_ms aside); an entity's draws depend on
+ *   nothing but its global id, the seed, its own tokens and the frozen counts, so a later group form (the counts of the sides summed
+ *   over the shards between iterations) can equal one handle.
+ * On the device (mvhdp_split.hip): one pass over every view's z with 16-byte loads lists the set in entity order (position, type, side
+ *   byte) with a CSR by entity; the word counts of the two sides live in a table [sumV + M][2] of int32 filled from the source column;
+ *   per iteration one sampling launch (a wave per entity that owns tokens of the set, chunks of 64 records, the chain resolved from LDS)
+ *   and one launch of integer atomics on the table; at the end z of the set and the two columns of the count rows are written.
+ *   profiles/split_topic.md has the figures.
+ * Not done: mvhdp_group_split_topic / NativeGroup.split_topic, a JNI class.
+ * mvhdp_split_args, in this order: int32 source, target, iterations; uint32 flags; uint64 seed; two host pointers (40 bytes).
+ *   mvhdp_split_stats: int64 split[8], moved[8], flips_last; int32 target, activated; double kernel_ms (152 bytes).
+ *   tests/test_split_kats.py pins both. */
+#define MVHDP_SPLIT_KEEP_ALPHA 0x1u   /* the source keeps its alpha; the target still gets 0.5 * alpha[m][source] */
+typedef struct {
+    int32_t source, target;              /* target: a topic index, or -1 = the library picks the lowest free index of the inactive set */
+    int32_t iterations;                  /* 0 .. 65535 restricted sweeps after the initial assignment */
+    uint32_t flags;
+    uint64_t seed;
+    const double* coupling;              /* [M][M] host or NULL: exactly mvhdp_fold_in's P and its default */
+    const int8_t* const* type_hint;      /* NULL, or [M] -> NULL or [V_m]: -1 none, 0 stays in source, 1 starts in target */
+} mvhdp_split_args;
+typedef struct {
+    int64_t split[MVHDP_MAX_MODALITIES]; /* tokens of view m that carried the source topic */
+    int64_t moved[MVHDP_MAX_MODALITIES]; /* of those, in the target at the end */
+    int64_t flips_last;                  /* tokens that changed side in the last iteration (0 with iterations == 0) */
+    int32_t target, activated;           /* the target used; 1 if it left the inactive set */
+    double kernel_ms;
+} mvhdp_split_stats;
+int mvhdp_split_topic(mvhdp_handle h, const mvhdp_split_args* a, int64_t* flips /*[iterations] or NULL*/, mvhdp_split_stats* stats /* or NULL */);
 
 /* ---- word and topic embeddings: trainTypeVectors (PTM:517-524, 1186-1206, 1495-1498) and SciTopicFlow.runWordEmbeddings (FLOW:115-136).
  * TWE = MVTopicModel/TopicWordEmbeddings.java, TWER = MVTopicModel/TopicWordEmbeddingRunnable.java.  WordEmbeddings is TWE with no

@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
     "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_fold_in", "mvhdp_predict_items", "mvhdp_score_items",
     "mvhdp_nearest_entities", "mvhdp_nearest_probe", "mvhdp_topic_top_entities", "mvhdp_predict_entities", "mvhdp_rank_entities",
-    "mvhdp_topic_gram", "mvhdp_cohort_top_words", "mvhdp_remap_topics",
+    "mvhdp_topic_gram", "mvhdp_cohort_top_words", "mvhdp_remap_topics", "mvhdp_split_topic",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
@@ -229,6 +229,19 @@ class RemapStatsC(C.Structure):
                 ("kernel_ms", C.c_double)]
 
 
+SPLIT_KEEP_ALPHA = 0x1                              # MVHDP_SPLIT_KEEP_ALPHA
+
+
+class SplitArgsC(C.Structure):
+    _fields_ = [("source", C.c_int32), ("target", C.c_int32), ("iterations", C.c_int32), ("flags", C.c_uint32), ("seed", C.c_uint64),
+                ("coupling", C.c_void_p), ("type_hint", C.c_void_p)]
+
+
+class SplitStatsC(C.Structure):
+    _fields_ = [("split", C.c_int64 * MAX_M), ("moved", C.c_int64 * MAX_M), ("flips_last", C.c_int64), ("target", C.c_int32),
+                ("activated", C.c_int32), ("kernel_ms", C.c_double)]
+
+
 class NearestArgsC(C.Structure):
     _fields_ = [("view_weights", C.c_void_p), ("c0", C.c_int64), ("c1", C.c_int64), ("queries", C.c_void_p), ("nq", C.c_int64),
                 ("q0", C.c_int64), ("q1", C.c_int64), ("exclude_self", C.c_int32), ("n", C.c_int32), ("min_weight", C.c_double),
@@ -363,6 +376,7 @@ def load_library():
     L.mvhdp_cohort_top_words.argtypes = [vp, C.POINTER(CohortArgsC), i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CohortStatsC)]
     L.mvhdp_remap_topics.argtypes = [vp, C.POINTER(RemapArgsC), C.POINTER(RemapStatsC)]
     L.mvhdp_group_remap_topics.argtypes = [vp, C.POINTER(RemapArgsC), C.POINTER(RemapStatsC)]
+    L.mvhdp_split_topic.argtypes = [vp, C.POINTER(SplitArgsC), vp, C.POINTER(SplitStatsC)]
     L.mvhdp_nearest_entities.argtypes = [vp, C.POINTER(NearestArgsC), vp, vp, vp, C.POINTER(NearestStatsC)]
     L.mvhdp_nearest_probe.argtypes = [i64, i64, i32, i32, i32, C.POINTER(NearestStatsC)]
     L.mvhdp_topic_top_entities.argtypes = [vp, vp, i64, i64, i32, C.c_double, i64, i64, vp, vp, vp]

@@ -1,6 +1,6 @@
 // mvhdp_state.h — what the device buffers of one handle currently hold (mvhdp_ctx::st), kept in one place: the fields are private, they
 // are read through the accessors and written ONLY by the transitions below, each of which records one event that happened to the
-// buffers.  The host-side sources (mvhdp_api.hip, mvhdp_enqueue.hip, mvhdp_group.hip, mvhdp_emb.hip, mvhdp_diag.hip, mvhdp_remap.hip) call these and
+// buffers.  The host-side sources (mvhdp_api.hip, mvhdp_enqueue.hip, mvhdp_group.hip, mvhdp_emb.hip, mvhdp_diag.hip, mvhdp_remap.hip, mvhdp_split.hip) call these and
 // nothing else; tests/test_handle_state.py compiles this file with the host compiler: no HIP type in here.
 //
 // The rules the callers keep with it:

@@ -14,7 +14,7 @@ import numpy as np
 
 from ._lib import (CensusRowC, COHORT_BY_COUNT, COHORT_BY_SHARE, CohortArgsC, CohortStatsC, DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
                    EmbConfigC, EmbStatsC, EntitiesArgsC, EntitiesStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TopicGramArgsC, TopicGramStatsC, TuningC,
-                   REMAP_RETIRE, RemapArgsC, RemapStatsC,
+                   REMAP_RETIRE, RemapArgsC, RemapStatsC, SPLIT_KEEP_ALPHA, SplitArgsC, SplitStatsC,
                    load_library,
                    SIM_COS, SIM_COS_FOLDED, SIM_JSD)
 
@@ -444,6 +444,20 @@ def _remap_call(fn, handle, K, M, topic_map, retire):
     st = RemapStatsC()
     rc = fn(handle, C.byref(a), C.byref(st))
     return rc, RemapStats(np.array(st.moved[:M], dtype=np.int64), np.array(st.dropped[:M], dtype=np.int64), st.vacated, st.retired, st.kernel_ms)
+
+
+@dataclass
+class SplitStats:
+    """mvhdp_split_stats: per view the tokens that carried the source topic (split [M]) and those of them in the target at the end (moved
+    [M]); flips [iterations] = the tokens that changed side per iteration, flips_last its last entry (0 without iterations); target = the
+    index used, activated = whether it left the inactive set; kernel_ms = the stream's time over the kernels of the call."""
+    split: np.ndarray = None
+    moved: np.ndarray = None
+    flips_last: int = 0
+    target: int = -1
+    activated: bool = False
+    kernel_ms: float = 0.0
+    flips: np.ndarray = None
 
 
 def merge_topic_top_entities(parts, n):
@@ -1243,6 +1257,33 @@ class NativeSampler:
         rc, st = _remap_call(self.L.mvhdp_remap_topics, self.h, self.K, self.M, topic_map, retire)
         self._ck(rc)
         return st
+
+    def split_topic(self, source, target=None, iterations=20, seed=0, coupling=None, type_hint=None, keep_alpha=False) -> SplitStats:
+        """Cut topic `source` in two in place (include/mvhdp.h mvhdp_split_topic): a Gibbs sampler restricted to the tokens of the source
+        and to the two outcomes "stays" and "goes to target".  target: a free topic index (no token, alpha 0.0 in every view), None = the
+        lowest free index of the inactive set (surgery.free_topics lists them).  type_hint: None, or per view None or an int8 row [V_m]
+        (-1 none, 0 stays in source, 1 starts in target; surgery.hint_from_words builds one).  coupling: [M][M] as for fold_in.  alpha of
+        the source is halved between the two unless keep_alpha.  Every kind of sweep goes on afterwards."""
+        iterations = int(iterations)
+        P = None if coupling is None else np.ascontiguousarray(coupling, dtype=np.float64)
+        if P is not None and P.shape != (self.M, self.M):
+            raise ValueError(f"split_topic: coupling must be [{self.M}][{self.M}], got {P.shape}")
+        rows, hp = None, None
+        if type_hint is not None:
+            if len(type_hint) != self.M:
+                raise ValueError(f"split_topic: type_hint must hold one entry per view ({self.M})")
+            rows = [None if r is None else np.ascontiguousarray(r, dtype=np.int8) for r in type_hint]
+            for m, r in enumerate(rows):
+                if r is not None and r.shape != (self.V[m],):
+                    raise ValueError(f"split_topic: type_hint[{m}] must hold one entry per type ({self.V[m]}), got shape {r.shape}")
+            hp = (C.c_void_p * self.M)(*[None if r is None else r.ctypes.data for r in rows])
+        a = SplitArgsC(int(source), -1 if target is None else int(target), iterations, SPLIT_KEEP_ALPHA if keep_alpha else 0, int(seed),
+                       None if P is None else P.ctypes.data, None if hp is None else C.cast(hp, C.c_void_p))
+        flips = np.zeros(max(iterations, 1), dtype=np.int64)
+        st = SplitStatsC()
+        self._ck(self.L.mvhdp_split_topic(self.h, C.byref(a), _ptr(flips), C.byref(st)))
+        return SplitStats(np.array(st.split[:self.M], dtype=np.int64), np.array(st.moved[:self.M], dtype=np.int64), st.flips_last, st.target,
+                          bool(st.activated), st.kernel_ms, flips[:max(iterations, 0)].copy())
 
     def top_words(self, m, n):
         """getSortedWords(m) PTM:1792-1811 cut at n: (types [K][n] (-1 unfilled), counts [K][n], nonzero [K])."""

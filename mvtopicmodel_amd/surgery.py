@@ -2,8 +2,10 @@
 return: a similarity from topic_gram, token counts from get_counts, the inactive set from get_alpha.  Pure numpy, K-sized.
 
 A map is an int32 array [K]: map[k] = the topic that takes topic k's tokens, -1 = they become unassigned.  It is applied in one hop and
-never chased; compose() makes one map of two.  Not here: the reference's own discriminative-weight delete rule (PTM:773-809) and
-splitting a topic."""
+never chased; compose() makes one map of two.  Not here: the reference's own discriminative-weight delete rule (PTM:773-809).
+
+For NativeSampler.split_topic (mvhdp_split_topic): free_topics() lists the indices a split may take, hint_from_words() builds one view's
+hint row."""
 import numpy as np
 
 DROP = -1                                                   # MVHDP_UNASSIGNED_TOPIC
@@ -68,3 +70,33 @@ def compose(first, then):
     if first.shape != then.shape:
         raise ValueError("compose: the maps differ in length")
     return np.where(first < 0, DROP, then[np.maximum(first, 0)]).astype(np.int32)
+
+
+def free_topics(n_k_total, inactive, alpha):
+    """The indices a split may take as its target when it picks one itself, ascending: topics of the inactive set that hold no token in any
+    view (n_k_total [K], summed over the views) and whose alpha (alpha [M][K] or [M][K + 1]) is exactly 0.0 in every view.  split_topic
+    with target=None takes the first."""
+    n = np.asarray(n_k_total)
+    K = len(n)
+    off = np.asarray(inactive).astype(bool)
+    a = np.asarray(alpha, dtype=np.float64)
+    a = a.reshape(-1, a.shape[-1])[:, :K]
+    if off.shape != (K,) or a.shape[1] != K:
+        raise ValueError("free_topics: n_k_total, inactive and alpha disagree about K")
+    return np.flatnonzero(off & (n == 0) & (a == 0.0).all(axis=0)).astype(np.int32)
+
+
+def hint_from_words(V, stay=(), go=()):
+    """One view's type_hint row [V] int8 for split_topic: -1 everywhere, 0 for the types in `stay` (they stay in the source), 1 for those
+    in `go` (they start in the target).  A type in both lists is an error."""
+    stay = np.asarray(list(stay), dtype=np.int64)
+    go = np.asarray(list(go), dtype=np.int64)
+    for name, x in (("stay", stay), ("go", go)):
+        if len(x) and (x.min() < 0 or x.max() >= V):
+            raise ValueError(f"hint_from_words: a type of `{name}` is outside [0, {V})")
+    if len(np.intersect1d(stay, go)):
+        raise ValueError("hint_from_words: a type is in both lists")
+    row = np.full(V, -1, dtype=np.int8)
+    row[stay] = 0
+    row[go] = 1
+    return row
