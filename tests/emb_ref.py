@@ -2,14 +2,11 @@
 device's draws and dot-product order (built once per process with gcc -O2 -ffp-contract=off into a temporary directory).  Test
 infrastructure."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "emb_ref.c")
+from tests.native_build import ptr, ref_lib
+
 _lib = None
 
 
@@ -31,9 +28,7 @@ class ErStats(C.Structure):
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="emb_ref_"), "libemb_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11", SRC, "-o", so, "-lm"])
-        L = C.CDLL(so)
+        L = ref_lib("emb_ref")
         vp, i32, i64, u32, u64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
         L.er_philox.argtypes = [vp, vp, vp]
         L.er_draw64.argtypes = [u32, u32, u32, u32, u32, u32]; L.er_draw64.restype = u64
@@ -49,19 +44,15 @@ def lib():
     return _lib
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def philox(ctr, key):
     c = np.array(ctr, dtype=np.uint32); k = np.array(key, dtype=np.uint32); o = np.zeros(4, dtype=np.uint32)
-    lib().er_philox(_p(c), _p(k), _p(o))
+    lib().er_philox(ptr(c), ptr(k), ptr(o))
     return [int(x) for x in o]
 
 
 def cache(size=1000, min_exp=-6.0, max_exp=6.0):
     out = np.zeros(size + 1)
-    lib().er_cache(size, min_exp, max_exp, _p(out))
+    lib().er_cache(size, min_exp, max_exp, ptr(out))
     return out
 
 
@@ -75,7 +66,7 @@ class EmbRef:
         self.R, self.C = self.V0 + self.K, int(cfg.num_columns)
         self.w = np.zeros((self.R, self.C)); self.neg = np.zeros((self.R, self.C))
         if weights is None:
-            lib().er_init(self.R, self.C, int(seed), _p(self.w), _p(self.neg))
+            lib().er_init(self.R, self.C, int(seed), ptr(self.w), ptr(self.neg))
         else:
             self.w[:] = weights
         self.cache = cache(cfg.sigmoid_cache_size, cfg.min_exp, cfg.max_exp)
@@ -87,15 +78,15 @@ class EmbRef:
         tok = np.ascontiguousarray(tok, dtype=np.int32)
         t = C.c_int64(self.total)
         self.retention = np.zeros(self.V0); self.sorted = np.zeros(self.V0, np.int32); self.dist = np.zeros(self.V0)
-        lib().er_count(self.V0, len(tok), _p(tok), float(self.cfg.sampling_factor), _p(self.counts), C.byref(t),
-                       _p(self.retention), _p(self.sorted), _p(self.dist))
+        lib().er_count(self.V0, len(tok), ptr(tok), float(self.cfg.sampling_factor), ptr(self.counts), C.byref(t),
+                       ptr(self.retention), ptr(self.sorted), ptr(self.dist))
         self.total = t.value
         if table:
             self.table = self.table_range(0, self.cfg.sampling_table_size)
 
     def table_range(self, first, n):
         out = np.zeros(int(n), dtype=np.int32)
-        lib().er_table(self.V0, _p(self.sorted), _p(self.dist), int(self.cfg.sampling_table_size), int(first), int(n), _p(out))
+        lib().er_table(self.V0, ptr(self.sorted), ptr(self.dist), int(self.cfg.sampling_table_size), int(first), int(n), ptr(out))
         return out
 
     def table_at(self, idx):
@@ -103,24 +94,24 @@ class EmbRef:
 
     def table_literal(self):
         out = np.zeros(int(self.cfg.sampling_table_size), dtype=np.int32)
-        lib().er_table_literal(self.V0, _p(self.sorted), _p(self.dist), int(self.cfg.sampling_table_size), _p(out))
+        lib().er_table_literal(self.V0, ptr(self.sorted), ptr(self.dist), int(self.cfg.sampling_table_size), ptr(out))
         return out
 
     def train(self, doc_off, tok, z, epochs, seed, round_idx=0, ent_base=0):
         doc_off = np.ascontiguousarray(doc_off, dtype=np.int64); tok = np.ascontiguousarray(tok, dtype=np.int32)
         z = None if (z is None or not self.K) else np.ascontiguousarray(z, dtype=np.int32)
         cfg = self.cfg
-        a = ErTrain(_p(doc_off), _p(tok), _p(z), len(doc_off) - 1, int(doc_off[-1]), int(self.total), int(ent_base),
+        a = ErTrain(ptr(doc_off), ptr(tok), ptr(z), len(doc_off) - 1, int(doc_off[-1]), int(self.total), int(ent_base),
                     self.V0, self.C, self.Cc, int(cfg.window), int(cfg.num_samples), int(cfg.min_doc_length), int(epochs),
-                    int(cfg.sigmoid_cache_size), int(cfg.sampling_table_size), _p(self.table), _p(self.retention), _p(self.cache),
+                    int(cfg.sigmoid_cache_size), int(cfg.sampling_table_size), ptr(self.table), ptr(self.retention), ptr(self.cache),
                     float(cfg.min_exp), float(cfg.max_exp), int(seed), int(round_idx), 0)
         st = ErStats()
-        assert lib().er_train(C.byref(a), _p(self.w), _p(self.neg), C.byref(st)) == 0
+        assert lib().er_train(C.byref(a), ptr(self.w), ptr(self.neg), C.byref(st)) == 0
         return {f: getattr(st, f) for f, _ in ErStats._fields_}
 
     def softmax(self, reset_sums=False):
         if reset_sums:
             self.sum_exp[:] = 0.0
         e = np.zeros((self.K, self.V0))
-        lib().er_softmax(self.V0, self.K, self.C, _p(self.w), _p(e), _p(self.sum_exp))
+        lib().er_softmax(self.V0, self.K, self.C, ptr(self.w), ptr(e), ptr(self.sum_exp))
         return e, self.sum_exp.copy()

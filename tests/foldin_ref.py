@@ -1,24 +1,19 @@
 """ctypes wrapper of tests/native/foldin_ref.c, the sequential restatement of mvhdp_fold_in as include/mvhdp.h defines it (built once per
 process with gcc -O2 -ffp-contract=off into a temporary directory).  Test infrastructure: no GPU, no product code."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 from dataclasses import dataclass
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "foldin_ref.c")
+from tests.native_build import ptr, ptr_array, ref_lib
+
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="foldin_ref_"), "libfoldin_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11", SRC, "-o", so, "-lm"])
-        L = C.CDLL(so)
+        L = ref_lib("foldin_ref")
         vp, i32, i64, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64
         L.foldin_run.argtypes = [i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u64, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
         L.foldin_run.restype = i32
@@ -27,14 +22,6 @@ def lib():
         L.foldin_unit.restype = C.c_double
         _lib = L
     return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _pp(arrays):
-    return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
 
 
 @dataclass
@@ -108,17 +95,17 @@ def run(model, doc_off, tokens, view_weights=None, iterations=10, samples=1, thi
     n_in = sum(int((t < v).sum()) for t, v in zip(toks, V) if t is not None)
     tw = np.zeros((n_in * iterations, K + 2)) if trace else None
     tb = np.zeros((iterations, M, K)) if trace else None
-    keep = (_pp(nwk), _pp(offs), _pp(toks), _pp(z))
-    rc = lib().foldin_run(K, M, _p(V), keep[0], _p(nk), _p(beta), _p(beta_sum), _p(gamma), _p(alpha), _p(alpha_sum), _p(inactive), _p(P),
-                          int(iterations), int(samples), int(thin), int(seed), int(doc_base), D, keep[1], keep[2], _p(w), _p(theta), keep[3], _p(cs),
-                          _p(totals), _p(tw), _p(tb))
+    keep = (ptr_array(nwk), ptr_array(offs), ptr_array(toks), ptr_array(z))
+    rc = lib().foldin_run(K, M, ptr(V), keep[0], ptr(nk), ptr(beta), ptr(beta_sum), ptr(gamma), ptr(alpha), ptr(alpha_sum), ptr(inactive), ptr(P),
+                          int(iterations), int(samples), int(thin), int(seed), int(doc_base), D, keep[1], keep[2], ptr(w), ptr(theta), keep[3], ptr(cs),
+                          ptr(totals), ptr(tw), ptr(tb))
     assert rc == 0, rc
     return Ref(theta, z, cs, int(totals[0]), int(totals[1]), int(totals[2]), tw, tb)
 
 
 def philox(ctr, key):
     c = np.array(ctr, dtype=np.uint32); k = np.array(key, dtype=np.uint32); o = np.zeros(4, dtype=np.uint32)
-    lib().foldin_philox(_p(c), _p(k), _p(o))
+    lib().foldin_philox(ptr(c), ptr(k), ptr(o))
     return [int(x) for x in o]
 
 

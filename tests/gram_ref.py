@@ -3,14 +3,11 @@ built once per process with gcc -O2 -ffp-contract=off into a temporary directory
 xview_ref.phi_table, theta is what mvhdp_doc_topic_proportions returns for the handle under test.  Test infrastructure: no GPU, no product
 code."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "gram_ref.c")
+from tests.native_build import ptr, ref_lib
+
 BLOCK_ROWS = 1024
 CONTRACT, DESCENDING, UNFUSED, OTHER_BLOCK, ONE_CHAIN = 0, 1, 2, 3, 4     # gram_ref's variants: the contract, and four the sensitivity tests run
 TRANSFORMS = {"identity": 0, "sqrt": 1}
@@ -20,9 +17,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="gram_ref_"), "libgram_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11", SRC, "-o", so, "-lm"])
-        L = C.CDLL(so)
+        L = ref_lib("gram_ref")
         vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
         L.gram_ref.argtypes = [i32, i64, vp, i32, i32, i64, vp, vp]
         L.gram_ref.restype = i32
@@ -32,17 +27,13 @@ def lib():
     return _lib
 
 
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
 def gram(x, transform="identity", variant=CONTRACT, block=BLOCK_ROWS):
     """(gram [K][K], sums [K]) of the rows x [n][K]"""
     x = np.ascontiguousarray(x, dtype=np.float64)
     n, K = x.shape
     g, s = np.zeros((K, K)), np.zeros(K)
     src = x if n else np.zeros((1, K))
-    assert lib().gram_ref(K, n, _p(src), TRANSFORMS[transform], int(variant), int(block), _p(g), _p(s)) == 0
+    assert lib().gram_ref(K, n, ptr(src), TRANSFORMS[transform], int(variant), int(block), ptr(g), ptr(s)) == 0
     return g, s
 
 
@@ -52,7 +43,7 @@ def counts(x, threshold):
     n, K = x.shape
     na, co = np.zeros(K, dtype=np.int64), np.zeros((K, K), dtype=np.int64)
     src = x if n else np.zeros((1, K))
-    lib().gram_counts(K, n, _p(src), float(threshold), _p(na), _p(co))
+    lib().gram_counts(K, n, ptr(src), float(threshold), ptr(na), ptr(co))
     return na, co
 
 

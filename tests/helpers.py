@@ -1,5 +1,6 @@
 """Shared test helpers: build the same small model in the oracle and in the product."""
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -24,15 +25,117 @@ def make_oracle(corpus, hyper, init_seed=1):
     return o
 
 
-def make_native(corpus, hyper, z_init, doc_id_base=0):
+INV, STATE, UNSUPPORTED = -1, -2, -6                                         # MVHDP_ERR_INVALID_ARG, _STATE, _UNSUPPORTED
+
+
+def load(c, lo=0, hi=None, counts=True, z=None, hy=None, doc_id_base=0):
+    """A sampler holding entities [lo, hi) of the case c (hi None: to the last one) with c's own assignments and hyperparameters, or
+    with z (per view, of all of c's tokens) and hy.  counts True: built from the assignments; False: left unbuilt; a table [(n_wk, n_k)
+    per view]: set as given (a group's replicated counts)."""
     from mvtopicmodel_amd import NativeSampler
-    s = NativeSampler(corpus.K, corpus.V, device=0, doc_id_base=doc_id_base)
-    for m in range(corpus.M):
-        s.set_corpus(m, corpus.doc_off[m], corpus.tokens[m])
-        s.set_assignments(m, z_init[m])
-    s.set_hyper(hyper)
-    s.build_counts()
+    z = c.z if z is None else z
+    s = NativeSampler(c.K, c.V, device=0, doc_id_base=doc_id_base)
+    for m in range(c.M):
+        off = np.asarray(c.doc_off[m])
+        b, e = off[lo], off[-1 if hi is None else hi]
+        s.set_corpus(m, off[lo:None if hi is None else hi + 1] - b, c.tokens[m][b:e])
+        s.set_assignments(m, z[m][b:e])
+    s.set_hyper(c.hy if hy is None else hy)
+    if counts is True:
+        s.build_counts()
+    elif counts is not False:
+        for m in range(c.M):
+            s.set_counts(m, *counts[m])
     return s
+
+
+def make_native(corpus, hyper, z_init, doc_id_base=0):
+    return load(corpus, z=z_init, hy=hyper, doc_id_base=doc_id_base)
+
+
+def golden_sampler(name):
+    """(the sampler of tests/golden/<name>.npz after its two sweeps, the file's arrays, its hyperparameters)"""
+    from mvtopicmodel_amd import NativeSampler
+    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", name + ".npz"))
+    K, V = int(g["K"]), [int(v) for v in g["V"]]
+    hy = Hyper(alpha=g["alpha"], alpha_sum=g["alpha_sum"], beta=g["beta"], beta_sum=g["beta_sum"], gamma=g["gamma"],
+               p_a=g["p_a"], p_b=g["p_b"], inactive=g["inactive"])
+    smp = NativeSampler(K, V)
+    for m in range(len(V)):
+        smp.set_corpus(m, g[f"doc_off{m}"], g[f"tokens{m}"])
+        smp.set_assignments(m, g[f"z0_{m}"])
+    smp.set_hyper(hy)
+    smp.build_counts()
+    for it in range(2):
+        smp.sweep(it, int(g["sweep_seed"]))
+    return smp, g, hy
+
+
+def uneven_hyper(K, V, seed):
+    """alpha_k uneven, gamma != 1 and alphaSum != sum(alpha_k): alphaSum' = gamma * alphaSum is a number of its own"""
+    rng = np.random.default_rng(seed)
+    hy = Hyper.defaults(K, V)
+    hy.alpha[:, :K] = rng.uniform(0.05, 0.15, (len(V), K))
+    hy.alpha_sum = hy.alpha[:, :K].sum(1) * 1.25
+    hy.gamma = np.linspace(0.8, 0.9, len(V))
+    return hy
+
+
+def hyper_with(c, alpha, inactive):
+    hy = type(c.hy)(**{k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in vars(c.hy).items()})
+    hy.alpha, hy.inactive = alpha.copy(), inactive.copy()
+    return hy
+
+
+def shards_of(c, z, n):
+    """[(first entity, the entities' corpus, their assignments)] of n contiguous entity ranges balanced by token count (synth.shard_bounds)"""
+    tot = sum(np.diff(c.doc_off[m]) for m in range(c.M))
+    return [(lo, c.slice_docs(lo, hi), [z[m][c.doc_off[m][lo]:c.doc_off[m][hi]] for m in range(c.M)]) for lo, hi in synth.shard_bounds(tot, n)]
+
+
+def recount(tokens, z, V, K):
+    """n_wk [V][K] of one view's assignments"""
+    return np.bincount(np.asarray(tokens, dtype=np.int64) * K + z, minlength=V * K).reshape(V, K)
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
+
+
+def untouched(arrays, sentinel=-7):
+    """every cell of the outputs a raw call was handed still holds what they were filled with"""
+    return all((a == sentinel).all() for a in arrays.values())
+
+
+def state_of(s):
+    """everything a topic-surgery call may move, as bytes"""
+    parts = [s.get_assignments(m).tobytes() for m in range(s.M)]
+    for m in range(s.M):
+        nwk, nk = s.get_counts(m)
+        parts += [nwk.tobytes(), nk.tobytes()]
+    a, off = s.get_alpha()
+    return b"".join(parts + [a.tobytes(), off.tobytes()])
+
+
+def assert_holds(s, c, want, counts_of, what):
+    """the handle holds the restatement's z', the recount of it (counts_of: the restatement's own), alpha' bit for bit and inactive'"""
+    for m in range(c.M):
+        got = s.get_assignments(m)
+        assert np.array_equal(got, want.z[m]), (what, "z", m, np.flatnonzero(got != want.z[m])[:6])
+        nwk, nk = s.get_counts(m)
+        ref_nwk, ref_nk = counts_of(c.K, c.V[m], c.tokens[m], want.z[m])
+        assert np.array_equal(nk, ref_nk), (what, "n_k", m, np.flatnonzero(nk != ref_nk)[:6])
+        assert np.array_equal(nwk, ref_nwk), (what, "n_wk", m, np.argwhere(nwk != ref_nwk)[:6])
+    a, off = s.get_alpha()
+    assert a.tobytes() == want.alpha.tobytes(), (what, "alpha", np.argwhere(a != want.alpha)[:6])
+    assert np.array_equal(off, want.inactive), (what, "inactive")
+
+
+def assert_same_handles(a, b, M, what):
+    for m in range(M):
+        assert np.array_equal(a.get_assignments(m), b.get_assignments(m)), (what, "z", m)
+        ca, cb = a.get_counts(m), b.get_counts(m)
+        assert np.array_equal(ca[0], cb[0]) and np.array_equal(ca[1], cb[1]), (what, "counts", m)
 
 
 def assert_same_state(o, s, M):

@@ -3,34 +3,25 @@
 infrastructure: no GPU, no product code."""
 import ctypes as C
 import math
-import os
-import subprocess
-import tempfile
 from dataclasses import dataclass
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "ltr_ref.c")
+from tests.native_build import ptr, ref_lib
+
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="ltr_ref_"), "libltr_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11", SRC, "-o", so, "-lm"])
-        L = C.CDLL(so)
+        L = ref_lib("ltr_ref")
         vp, i32, i64, u64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double
         L.ltr_evaluate.argtypes = [i32, i32, vp, vp, dbl, vp, dbl, i32, i32, u64, i64, i64, vp, vp, vp, vp, vp, vp]
         L.ltr_evaluate.restype = i32
         L.ltr_philox.argtypes = [vp, vp, vp]
         _lib = L
     return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 @dataclass
@@ -75,8 +66,8 @@ def evaluate(nwk, nk, beta, alpha, alpha_sum, doc_off, tok, particles=10, resamp
     P = np.zeros((particles, N)) if want_P else None
     doc_tokens = np.zeros(D, dtype=np.int64)
     totals = np.zeros(3, dtype=np.int64)
-    rc = lib().ltr_evaluate(K, V, _p(nwk), _p(nk), float(beta), _p(alpha), float(alpha_sum), int(particles), 1 if resample else 0, int(seed), int(doc_base),
-                            D, _p(doc_off), _p(tok), _p(S), _p(P), _p(doc_tokens), _p(totals))
+    rc = lib().ltr_evaluate(K, V, ptr(nwk), ptr(nk), float(beta), ptr(alpha), float(alpha_sum), int(particles), 1 if resample else 0, int(seed), int(doc_base),
+                            D, ptr(doc_off), ptr(tok), ptr(S), ptr(P), ptr(doc_tokens), ptr(totals))
     assert rc == 0
     ll, bound = doc_logs(S, doc_off, particles)
     total = 0.0
@@ -87,5 +78,5 @@ def evaluate(nwk, nk, beta, alpha, alpha_sum, doc_off, tok, particles=10, resamp
 
 def philox(ctr, key):
     c = np.array(ctr, dtype=np.uint32); k = np.array(key, dtype=np.uint32); o = np.zeros(4, dtype=np.uint32)
-    lib().ltr_philox(_p(c), _p(k), _p(o))
+    lib().ltr_philox(ptr(c), ptr(k), ptr(o))
     return [int(x) for x in o]

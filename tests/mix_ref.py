@@ -7,16 +7,13 @@ expDotProductValues [K][V_0] / sumExpValues [K].  lam = 0 switches the mix off (
 the table and runs lam = 0 through the mix expression (0 + 1 * q), which must give the same bits."""
 import ctypes as C
 import os
-import subprocess
-import tempfile
 
 import numpy as np
 
 from oracle import binding as ob
 from oracle.binding import Oracle, Stats, _ptr
+from tests.native_build import ref_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "mix_ref.c")
 _lib = None
 TRACE_PRODUCT = 0x100                                    # MXR_TRACE_PRODUCT
 
@@ -26,10 +23,7 @@ def lib():
     if _lib is None:
         ob.lib()                                        # (builds the oracle's library when it is missing or stale)
         odir = os.path.dirname(ob._SO)
-        so = os.path.join(tempfile.mkdtemp(prefix="mix_ref_"), "libmix_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-fno-fast-math", "-shared", "-fPIC", "-std=gnu11", "-Wall", SRC, "-o", so,
-                               "-L" + odir, "-lmvhdp_oracle", "-Wl,-rpath," + odir, "-lm"])
-        L = C.CDLL(so)
+        L = ref_lib("mix_ref", extra_flags=("-fno-fast-math", "-Wall"), link=("-L" + odir, "-lmvhdp_oracle", "-Wl,-rpath," + odir, "-lm"))
         vp, i32, i64, u32, u64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double
         L.mxr_make_mix.argtypes = [C.c_int, C.c_int, dbl, vp, vp, vp]
         L.mxr_build_trees.argtypes = [vp, C.c_int, vp, dbl]

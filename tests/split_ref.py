@@ -1,17 +1,13 @@
 """ctypes wrapper of tests/native/split_ref.c, the sequential restatement of mvhdp_split_topic as include/mvhdp.h defines it (built once
 per process with gcc -O2 -ffp-contract=off into a temporary directory).  Test infrastructure: no GPU, no product code."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 from dataclasses import dataclass
 
 import numpy as np
 
 from tests.foldin_ref import default_coupling
+from tests.native_build import ptr, ptr_array, ref_lib
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "split_ref.c")
 KEEP_ALPHA = 0x1
 MAXM = 8
 _lib = None
@@ -20,9 +16,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="split_ref_"), "libsplit_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11", SRC, "-o", so, "-lm"])
-        L = C.CDLL(so)
+        L = ref_lib("split_ref")
         vp, i32, i64, u32, u64 = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64
         L.split_run.argtypes = [i32, i32, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, u32, u64, i64, vp, vp, vp, vp, i64, vp]
         L.split_run.restype = i32
@@ -31,14 +25,6 @@ def lib():
         L.split_unit.restype = C.c_double
         _lib = L
     return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
-def _pp(arrays):
-    return (C.c_void_p * len(arrays))(*[None if a is None else a.ctypes.data for a in arrays])
 
 
 def counts_of(K, V, tokens, z):
@@ -92,11 +78,11 @@ def run(K, V, doc_off, tokens, z, hy, source, target=None, iterations=20, seed=0
     cap = n_set * max(int(iterations), 0) if trace else 0
     tr = np.zeros((max(cap, 1), 4)) if trace else None
     ntr = np.zeros(1, dtype=np.int64)
-    keep = (_pp(offs), _pp(toks), _pp(zz), None if hints is None else _pp(hints))
+    keep = (ptr_array(offs), ptr_array(toks), ptr_array(zz), None if hints is None else ptr_array(hints))
     fl = (KEEP_ALPHA if keep_alpha else 0) if flags is None else flags
-    rc = lib().split_run(K, M, _p(Vv), D, keep[0], keep[1], keep[2], _p(nk), _p(beta), _p(beta_sum), _p(gamma), _p(alpha), _p(alpha_sum),
-                         _p(inactive), _p(P), int(source), -1 if target is None else int(target), int(iterations), fl, int(seed),
-                         int(doc_id_base), keep[3], _p(stats), _p(flips), _p(tr), cap, _p(ntr))
+    rc = lib().split_run(K, M, ptr(Vv), D, keep[0], keep[1], keep[2], ptr(nk), ptr(beta), ptr(beta_sum), ptr(gamma), ptr(alpha), ptr(alpha_sum),
+                         ptr(inactive), ptr(P), int(source), -1 if target is None else int(target), int(iterations), fl, int(seed),
+                         int(doc_id_base), keep[3], ptr(stats), ptr(flips), ptr(tr), cap, ptr(ntr))
     if rc != 0:
         return Ref(rc)
     return Ref(0, zz, alpha, inactive, stats[:M].copy(), stats[MAXM:MAXM + M].copy(), int(stats[2 * MAXM]), int(stats[2 * MAXM + 1]),
@@ -105,7 +91,7 @@ def run(K, V, doc_off, tokens, z, hy, source, target=None, iterations=20, seed=0
 
 def philox(ctr, key):
     c = np.array(ctr, dtype=np.uint32); k = np.array(key, dtype=np.uint32); o = np.zeros(4, dtype=np.uint32)
-    lib().split_philox(_p(c), _p(k), _p(o))
+    lib().split_philox(ptr(c), ptr(k), ptr(o))
     return [int(x) for x in o]
 
 

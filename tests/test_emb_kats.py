@@ -179,9 +179,9 @@ def test_sigmoid_cache_keeps_its_unset_last_entry():
     assert c[500] == 0.5 and c[0] == 1.0 / (1.0 + math.exp(6.0))
     assert math.floor((6.0 - -6.0) * (1000 / 12.0)) == 1000
     lr = 0.025
-    assert er.lib().er_residual(6.0, lr, 1, er._p(c), 1000, -6.0, 6.0) == lr                        # lr * (1 - 0.0)
-    assert er.lib().er_residual(6.0, lr, 0, er._p(c), 1000, -6.0, 6.0) == 0.0                       # lr * -0.0
-    assert er.lib().er_residual(5.99, lr, 1, er._p(c), 1000, -6.0, 6.0) < 0.0001
+    assert er.lib().er_residual(6.0, lr, 1, er.ptr(c), 1000, -6.0, 6.0) == lr                        # lr * (1 - 0.0)
+    assert er.lib().er_residual(6.0, lr, 0, er.ptr(c), 1000, -6.0, 6.0) == 0.0                       # lr * -0.0
+    assert er.lib().er_residual(5.99, lr, 1, er.ptr(c), 1000, -6.0, 6.0) < 0.0001
 
 
 @pytest.mark.parametrize("topics", [True, False])

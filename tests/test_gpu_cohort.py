@@ -12,24 +12,13 @@ from mvtopicmodel_amd import MvhdpError, NativeSampler, _lib
 from mvtopicmodel_amd.native import SWEEP_LIVE, SWEEP_NO_APPLY
 from tests import cohort_cases as cc
 from tests import cohort_numpy as cn
+from tests.helpers import INV, STATE, load, untouched
 
 pytestmark = pytest.mark.gpu
-INV, STATE = -1, -2                                                          # MVHDP_ERR_INVALID_ARG, MVHDP_ERR_STATE
 ONE, TWO, AUTO = "one table", "two tables", "auto"
 # (order, n, min_count, scratch): every n, min_count and scratch size with either order
 VARIANTS = [("count", 20, 1, AUTO), ("count", 1, 2, ONE), ("count", 64, 1, TWO), ("count", 20, 5, TWO),
             ("share", 20, 1, TWO), ("share", 64, 2, ONE), ("share", 1, 5, AUTO), ("share", 20, 2, AUTO)]
-
-
-def load(c, counts=True):
-    s = NativeSampler(c.K, c.V)
-    for v in range(c.M):
-        s.set_corpus(v, c.doc_off[v], c.tokens[v])
-        s.set_assignments(v, c.z[v])
-    s.set_hyper(c.hy)
-    if counts:
-        s.build_counts()
-    return s
 
 
 def scratch_of(c, m, which):
@@ -208,7 +197,7 @@ def raw_call(s, args, G, moff, mem, n=3, skip=(), sentinel=-7):
     ptr = [None if k in skip else arr[k].ctypes.data for k in ("types", "counts", "nonzero", "tokens", "docs")]
     rc = s.L.mvhdp_cohort_top_words(s.h, None if args is None else C.byref(args), G, None if moff is None else moff.ctypes.data,
                                     None if mem is None else mem.ctypes.data, *ptr, C.byref(st))
-    clean = all((a == sentinel).all() for a in arr.values()) and (st.listings, st.passes, st.kernel_ms) == (sentinel, sentinel, float(sentinel))
+    clean = untouched(arr, sentinel) and (st.listings, st.passes, st.kernel_ms) == (sentinel, sentinel, float(sentinel))
     return rc, clean
 
 

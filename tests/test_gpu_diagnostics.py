@@ -13,7 +13,7 @@ from mvtopicmodel_amd.java_init import init_assignments
 from mvtopicmodel_amd.native import Hyper, SWEEP_LIVE, java_string_lengths
 from tests import diag_numpy as dn
 from tests import test_diag_kats as kat
-from tests.helpers import make_native, small_corpus
+from tests.helpers import make_native, small_corpus, untouched
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -202,10 +202,6 @@ def _raw_call(s, N, wl=None):
     return s.L.mvhdp_diagnostics(s.h, C.byref(args), C.byref(out)), a
 
 
-def _untouched(a):
-    return all(np.all(v == 7) for v in a.values())
-
-
 def test_errors_leave_the_outputs_untouched():
     K, V = 20, [300, 40]
     c = small_corpus(K, V, 60, [30, 4], 77)
@@ -213,7 +209,7 @@ def test_errors_leave_the_outputs_untouched():
     with native_from(c, Hyper.defaults(K, V), z) as s:
         for n in (0, 65):
             rc, a = _raw_call(s, n)
-            assert rc == -1 and _untouched(a)
+            assert rc == -1 and untouched(a, 7)
             t = np.full((K, 70), 7, np.int32); cc = t.copy(); nz = np.full(K, 7, np.int32)
             assert s.L.mvhdp_top_words(s.h, 0, n, t.ctypes.data, cc.ctypes.data, nz.ctypes.data) == -1
             assert np.all(t == 7) and np.all(cc == 7) and np.all(nz == 7)
@@ -233,7 +229,7 @@ def test_errors_leave_the_outputs_untouched():
         s.set_assignments(0, zz)
         s.build_counts()
         rc, a = _raw_call(s, 20)
-        assert rc == -2 and _untouched(a), rc
+        assert rc == -2 and untouched(a, 7), rc
         s.set_assignments(0, z[0])
         s.build_counts()
         rc, a = _raw_call(s, 20)
@@ -249,7 +245,7 @@ def test_errors_leave_the_outputs_untouched():
         s.set_hyper(Hyper.defaults(K, V))
         s.build_counts()
         rc, a = _raw_call(s, 20)
-        assert rc == -2 and _untouched(a), rc
+        assert rc == -2 and untouched(a, 7), rc
 
 
 def test_c4_full_size_integers():

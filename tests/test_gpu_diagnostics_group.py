@@ -8,12 +8,13 @@ import sys
 import numpy as np
 import pytest
 
-from mvtopicmodel_amd import NativeGroup, NativeSampler, synth
+from mvtopicmodel_amd import NativeGroup, NativeSampler
 from mvtopicmodel_amd.java_init import init_assignments
 from mvtopicmodel_amd.native import Hyper
 from tests import diag_rank_worker as DW
 from tests import rank_worker as W
-from tests.helpers import make_native, small_corpus
+from tests.helpers import make_native, shards_of, small_corpus
+from tests.native_build import fake_rccl  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,11 +46,7 @@ def test_in_process_group_equals_the_single_handle(n):
     hy = Hyper.defaults(K, V)
     z = init_assignments(K, c.doc_off, seed=4)
     one = make_native(c, hy, z)
-    tot = sum(np.diff(c.doc_off[m]) for m in range(c.M))
-    shards = []
-    for lo, hi in synth.shard_bounds(tot, n):
-        sub = c.slice_docs(lo, hi)
-        shards.append(make_native(sub, hy, [z[m][c.doc_off[m][lo]:c.doc_off[m][hi]] for m in range(c.M)], doc_id_base=lo))
+    shards = [make_native(sub, hy, zs, doc_id_base=lo) for lo, sub, zs in shards_of(c, z, n)]
     with NativeGroup(shards) as g:
         g.build_counts()
         g.sweep(0, 13)
@@ -61,14 +58,6 @@ def test_in_process_group_equals_the_single_handle(n):
         assert np.array_equal(shards[-1].discr_weights(), one.discr_weights())       # any member's
     for s in shards + [one]:
         s.close()
-
-
-@pytest.fixture(scope="module")
-def fake_rccl(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("fake_rccl") / "libfake_rccl.so")
-    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "native", "fake_rccl.c"), "-o", out,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lrt", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"])
-    return out
 
 
 @pytest.mark.parametrize("nranks", [2, 4])

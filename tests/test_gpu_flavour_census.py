@@ -44,7 +44,7 @@ def debug_rows_as_the_oracle(ro, rs, M, where):
 
 def run_against_the_oracle(r, c, hy):
     from oracle.binding import SWEEP_FROZEN as ORC_FROZEN
-    from tests.test_gpu_live import _longest_first
+    from tests.near_ties import longest_first
     from tests.test_gpu_segmented import oracle_segmented_sweep
     o = make_oracle(c, hy)
     s = make_native(c, hy, [o.get_assignments(m) for m in range(c.M)])
@@ -52,7 +52,7 @@ def run_against_the_oracle(r, c, hy):
     s.sweep_census(enable=True, reset=True)
     if r.mode == "frozen":
         o.build_trees(); s.build_trees()
-    order = _longest_first(c.doc_off)
+    order = longest_first(c.doc_off)
     sampled = 0
     for it in range(SWEEPS):
         where = f"{r.name} sweep {it}"

@@ -13,19 +13,15 @@ from mvtopicmodel_amd import MvhdpError, NativeSampler, _lib, synth
 from mvtopicmodel_amd.native import Hyper, NativeGroup
 from tests import foldin_cases as fc
 from tests import foldin_ref as fr
+from tests.helpers import INV, STATE, uneven_hyper
 
 pytestmark = pytest.mark.gpu
-INV, STATE = -1, -2                                                          # MVHDP_ERR_INVALID_ARG, MVHDP_ERR_STATE
 KS = [5, 64, 65, 100, 130, 1000]
 
 
 def hyper(K, V, seed):
-    """alpha_k uneven, gamma != 1 and alphaSum != sum(alpha_k); a zero in p_a: the default coupling has a zero entry"""
-    rng = np.random.default_rng(seed)
-    hy = Hyper.defaults(K, V)
-    hy.alpha[:, :K] = rng.uniform(0.05, 0.15, (len(V), K))
-    hy.alpha_sum = hy.alpha[:, :K].sum(1) * 1.25
-    hy.gamma = np.linspace(0.8, 0.9, len(V))
+    """uneven_hyper with a zero in p_a: the default coupling has a zero entry"""
+    hy = uneven_hyper(K, V, seed)
     if len(V) > 1:
         hy.p_a[0, len(V) - 1] = 0.0
         hy.p_a[1, 0] = 0.5

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 from mvtopicmodel_amd.native import Hyper
+from tests.helpers import recount
 
 pytestmark = pytest.mark.gpu
 
@@ -27,10 +28,6 @@ def _fingerprint(s, M):
         out.append(int((nk.astype(np.int64) * w).sum()))
         out.append(int((nwk.astype(np.int64).sum(axis=0) * w).sum()))
     return out
-
-
-def _recount(tokens, z, V, K):
-    return np.bincount(tokens.astype(np.int64) * K + z, minlength=V * K).reshape(V, K)
 
 
 def _oracle_prefix(c, hy_arrays, z_prefix, counts, lo=0, hi=PREFIX):
@@ -74,7 +71,7 @@ def test_config_at_full_size(name):
         counts_before = [one.get_counts(m) for m in range(M)]
         if it == 0:                                                    # PTM:600-652 against an independent recount
             for m in range(M):
-                assert np.array_equal(counts_before[m][0], _recount(c.tokens[m], z0[m], V[m], K))
+                assert np.array_equal(counts_before[m][0], recount(c.tokens[m], z0[m], V[m], K))
         alpha_before, inactive_before = one.get_alpha()
         st = one.sweep(it, 1)
         assert st.tokens == c.total_tokens and st.aborted_docs == 0 and st.oov_skipped == 0
@@ -112,7 +109,7 @@ def test_config_at_full_size(name):
         assert np.array_equal(nwk.astype(np.int64).sum(axis=0), nk.astype(np.int64))           # PTM:640-643
         assert int(nk.astype(np.int64).sum()) == int(c.doc_off[m][-1])                          # PTM:511 totalTokens
         assert z_one[m].min() >= 0 and z_one[m].max() < K
-        assert np.array_equal(nwk, _recount(c.tokens[m], z_one[m], V[m], K))                    # n_wk is the count of z
+        assert np.array_equal(nwk, recount(c.tokens[m], z_one[m], V[m], K))                    # n_wk is the count of z
     want = _fingerprint(one, M)
     alpha_one = one.get_alpha()
     one.close()
@@ -263,7 +260,7 @@ def test_the_kernels_that_carry_the_number_at_full_size(name):
         z = one.get_assignments(m)
         nwk, nk = one.get_counts(m)
         assert nwk.min() >= 0 and nk.min() >= 0
-        assert np.array_equal(nwk, _recount(c.tokens[m], z, V[m], K)), f"{name}: after a live sweep n_wk is not the count of z in view {m}"
+        assert np.array_equal(nwk, recount(c.tokens[m], z, V[m], K)), f"{name}: after a live sweep n_wk is not the count of z in view {m}"
         assert np.array_equal(nwk.astype(np.int64).sum(axis=0), nk.astype(np.int64))
         assert np.array_equal(nwk.astype(np.int64).sum(axis=1), type_totals[m])
     one.close()

@@ -8,20 +8,14 @@ import pytest
 from mvtopicmodel_amd import NativeGroup, synth
 from mvtopicmodel_amd._lib import MvhdpError
 from mvtopicmodel_amd.native import Hyper, SWEEP_LIVE, SWEEP_LIVE_SEGMENTS, SWEEP_NO_APPLY
-from tests.helpers import assert_same_state, make_native, make_oracle, small_corpus
+from tests.helpers import assert_same_state, make_native, make_oracle, shards_of, small_corpus
 
 pytestmark = pytest.mark.gpu
 
 
 def _shards(c, hy, z, n):
     """n NativeSamplers over contiguous entity ranges balanced by token count (synth.shard_bounds), global entity ids kept."""
-    tot = sum(np.diff(c.doc_off[m]) for m in range(c.M))
-    out = []
-    for lo, hi in synth.shard_bounds(tot, n):
-        sub = c.slice_docs(lo, hi)
-        zs = [z[m][c.doc_off[m][lo]:c.doc_off[m][hi]] for m in range(c.M)]
-        out.append(make_native(sub, hy, zs, doc_id_base=lo))
-    return out
+    return [make_native(sub, hy, zs, doc_id_base=lo) for lo, sub, zs in shards_of(c, z, n)]
 
 
 def _assert_group_equals_oracle(o, shards, c):

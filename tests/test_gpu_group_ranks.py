@@ -20,17 +20,10 @@ from mvtopicmodel_amd import NativeGroup, NativeSampler, synth
 from mvtopicmodel_amd.native import SWEEP_LIVE_SEGMENTS, SWEEP_SEGMENT_APPLY
 from tests import rank_worker as W
 from tests.helpers import make_native
+from tests.native_build import fake_rccl  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def fake_rccl(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("fake_rccl") / "libfake_rccl.so")
-    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "native", "fake_rccl.c"), "-o", out,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lrt", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"])
-    return out
 
 
 def run_ranks(tmp_path, fake, nranks, scenario, timeout=240, slot_bytes=None, collective_timeout_ms=20000, exchange16=None):

@@ -14,20 +14,11 @@ from mvtopicmodel_amd.native import SWEEP_NO_APPLY, Hyper, NativeGroup
 from tests import jni_harness as H
 from tests import ltr_cases as lc
 from tests import ltr_ref as lr
+from tests.helpers import INV, STATE, uneven_hyper as hyper
+from tests.native_build import jvm  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-INV, STATE = -1, -2                                                          # MVHDP_ERR_INVALID_ARG, MVHDP_ERR_STATE
 KS = [5, 64, 100, 130, 1000]
-
-
-def hyper(K, V, seed):
-    """alpha_k uneven, gamma != 1 and alphaSum != sum(alpha_k): alphaSum' = gamma * alphaSum is a number of its own"""
-    rng = np.random.default_rng(seed)
-    hy = Hyper.defaults(K, V)
-    hy.alpha[:, :K] = rng.uniform(0.05, 0.15, (len(V), K))
-    hy.alpha_sum = hy.alpha[:, :K].sum(1) * 1.25
-    hy.gamma = np.linspace(0.8, 0.9, len(V))
-    return hy
 
 
 class Model:
@@ -279,12 +270,6 @@ def test_group_of_two_members_equals_one_handle(models):
 
 # ---- the Java path: the four shim sources as one library, under the test-side JNIEnv (tests/jni_harness.py) ---------------------------
 IAE = "java/lang/IllegalArgumentException"
-
-
-@pytest.fixture(scope="module")
-def jvm(tmp_path_factory):
-    _lib.load_library()
-    return H.Jvm(H.build_shim(tmp_path_factory.mktemp("heldout_jni"), _lib.LIB_PATH, one_tu=True))       # the four shim sources as one translation unit
 
 
 def test_the_java_entry_equals_the_binding(jvm):

@@ -22,9 +22,10 @@ from mvtopicmodel_amd.native import (SWEEP_LIVE, SWEEP_LIVE_SEGMENTS, SWEEP_NO_A
 from tests import diag_numpy as dn
 from tests import emb_ref as er
 from tests import jni_harness as H
-from tests.helpers import make_native, make_oracle, small_corpus
+from tests.helpers import make_native, make_oracle, shards_of, small_corpus
 from tests.jni_harness import JavaException, JniGroup, JniSampler
 from tests.mix_cases import make_ref, same_state, same_stats, table
+from tests.native_build import fake_rccl  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -45,14 +46,6 @@ def jni_lib(tmp_path_factory):
 @pytest.fixture(scope="module")
 def jvm(jni_lib):
     return H.Jvm(jni_lib)
-
-
-@pytest.fixture(scope="module")
-def fake_rccl(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("fake_rccl") / "libfake_rccl.so")
-    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "native", "fake_rccl.c"), "-o", out,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lrt", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"])
-    return out
 
 
 class Java:
@@ -477,14 +470,6 @@ def test_set_tuning_of_get_tuning_keeps_the_live_rows_form(jvm):
 
 
 # ---- groups ----
-def shards_of(c, z, n):
-    tot = sum(np.diff(c.doc_off[m]) for m in range(c.M))
-    out = []
-    for lo, hi in synth.shard_bounds(tot, n):
-        out.append((lo, c.slice_docs(lo, hi), [z[m][c.doc_off[m][lo]:c.doc_off[m][hi]] for m in range(c.M)]))
-    return out
-
-
 def test_a_group_of_two_members_in_one_process_equals_the_single_handle(jvm):
     from tests.test_gpu_diagnostics import assert_matches, reference
     K, V = 48, [700, 90, 70]

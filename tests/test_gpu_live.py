@@ -9,23 +9,15 @@ import pytest
 
 from mvtopicmodel_amd.native import Hyper, SWEEP_FROZEN, SWEEP_LIVE, SWEEP_LIVE_SEGMENTS, SWEEP_NO_APPLY
 from mvtopicmodel_amd._lib import MvhdpError
-from tests.helpers import assert_same_state, make_native, make_oracle, small_corpus
+from tests.helpers import assert_same_state, make_native, make_oracle, recount, small_corpus
+from tests.near_ties import longest_first
 
 pytestmark = pytest.mark.gpu
 
 
-def _recount(c, z, K):
-    out = []
-    for m in range(c.M):
-        nwk = np.zeros((c.V[m], K), dtype=np.int64)
-        np.add.at(nwk, (c.tokens[m], z[m]), 1)
-        out.append(nwk)
-    return out
-
-
 def _check_counts_are_counts_of_z(c, s, K):
     z = [s.get_assignments(m) for m in range(c.M)]
-    want = _recount(c, z, K)
+    want = [recount(c.tokens[m], z[m], c.V[m], K) for m in range(c.M)]
     for m in range(c.M):
         nwk, nk = s.get_counts(m)
         assert nwk.min() >= 0 and nk.min() >= 0
@@ -269,12 +261,6 @@ def test_live_sweep_over_unassigned_tokens_stays_off_the_16_bit_mirror():
     s.close()
 
 
-def _longest_first(doc_off):
-    """the product's work-queue order: entities by decreasing token count over all views, ties in entity order (mvhdp_api.hip)"""
-    tot = sum(np.diff(np.asarray(o)) for o in doc_off)
-    return np.argsort(-tot, kind="stable").astype(np.int64)
-
-
 def _one_wave_against_the_oracle(o, s, order, M, sweeps, nseg, rows, live16, seed):
     for it in range(sweeps):
         ro = o.sweep_live_seq(it, seed, order, nseg=nseg, rows=rows, cell16=live16)["stats"]
@@ -302,7 +288,7 @@ def test_one_wave_live_sweep_equals_the_sequential_oracle(K, V, D, lam, cseed, f
     s = make_native(c, hy, [o.get_assignments(m) for m in range(c.M)])
     # one kernel per segment (a class kernel's end is where its block's tokensPerTopic lands): the primary variant holds every list
     s.set_tuning(live16=live16, single_wave=1, live_rows=rows, force_primary=force)
-    _one_wave_against_the_oracle(o, s, _longest_first(c.doc_off), c.M, 3, nseg, rows, live16, 13)
+    _one_wave_against_the_oracle(o, s, longest_first(c.doc_off), c.M, 3, nseg, rows, live16, 13)
     s.close()
 
 
@@ -329,7 +315,7 @@ def test_one_wave_live_sweep_with_a_heavy_row_equals_the_oracle(live16):
     s.set_corpus(0, off, tok); s.set_assignments(0, z0)
     s.set_hyper(hy); s.build_counts()
     s.set_tuning(live16=live16, single_wave=1, force_primary=1)
-    _one_wave_against_the_oracle(o, s, _longest_first([off]), 1, 2, 2, 1, live16, 17)
+    _one_wave_against_the_oracle(o, s, longest_first([off]), 1, 2, 2, 1, live16, 17)
     s.close()
 
 
@@ -350,7 +336,7 @@ def test_one_wave_live_sweep_with_unassigned_tokens_and_an_inactive_topic_equals
     o.build_counts()
     s = make_native(c, hy, z)
     s.set_tuning(live16=1, single_wave=1, force_primary=1)               # (asked for, and refused by the plan while a token is unassigned)
-    order = _longest_first(c.doc_off)
+    order = longest_first(c.doc_off)
     acts = 0
     for it in range(3):
         ro = o.sweep_live_seq(it, 21, order, nseg=2, rows=1, cell16=0 if it == 0 else 1)["stats"]
@@ -384,7 +370,7 @@ def test_one_wave_live_sweep_fuzz_against_the_sequential_oracle(case):
     o = make_oracle(c, hy)
     s = make_native(c, hy, [o.get_assignments(m) for m in range(c.M)])
     s.set_tuning(live16=live16, single_wave=1, live_rows=1, force_primary=force)
-    _one_wave_against_the_oracle(o, s, _longest_first(c.doc_off), c.M, 2, nseg, 1, live16, 100 + case)
+    _one_wave_against_the_oracle(o, s, longest_first(c.doc_off), c.M, 2, nseg, 1, live16, 100 + case)
     s.close()
 
 

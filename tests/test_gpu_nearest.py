@@ -5,7 +5,6 @@ returns for the same handle; rows with chosen contents come from a one-view mode
 (alpha = 0: theta_d is counts[d] / (len_d + alpha_sum), one division per entry).  The screen is held to its contract -- it never decides
 -- by forcing every block, stripe and capacity border through the three knobs, and by the condition that it does screen."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -14,10 +13,9 @@ from mvtopicmodel_amd import NativeSampler, _lib
 from mvtopicmodel_amd.native import SWEEP_LIVE, Hyper, NativeGroup, nearest_probe
 from tests import nearest_numpy as nn
 from tests import xview_cases as xc
+from tests.helpers import INV, STATE, golden_sampler
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
-INV, STATE = -1, -2
 W1 = np.array([1.0])
 KS, CS, NQS = [1, 2, 33, 100, 400], [1, 127, 128, 129, 300], [1, 64, 130]
 
@@ -330,26 +328,10 @@ def test_topic_top_entities_shapes_ties_threshold_and_chunk_borders(K):
                 assert (s.topic_top_entities(W1, 3, d0=9, d1=9)[2] == 0).all()
 
 
-def golden_sampler(name):
-    g = np.load(os.path.join(HERE, "golden", name + ".npz"))
-    K, V = int(g["K"]), [int(v) for v in g["V"]]
-    hy = Hyper(alpha=g["alpha"], alpha_sum=g["alpha_sum"], beta=g["beta"], beta_sum=g["beta_sum"], gamma=g["gamma"],
-               p_a=g["p_a"], p_b=g["p_b"], inactive=g["inactive"])
-    smp = NativeSampler(K, V)
-    for m in range(len(V)):
-        smp.set_corpus(m, g[f"doc_off{m}"], g[f"tokens{m}"])
-        smp.set_assignments(m, g[f"z0_{m}"])
-    smp.set_hyper(hy)
-    smp.build_counts()
-    for it in range(2):
-        smp.sweep(it, int(g["sweep_seed"]))
-    return smp
-
-
 @pytest.mark.parametrize("name", ["m3_k20", "m3_k100_inactive"])
 def test_both_entry_points_on_the_goldens(name):
     w = np.array([1.0, 0.7, 0.4])
-    with golden_sampler(name) as s:
+    with golden_sampler(name)[0] as s:
         prop = s.doc_topic_proportions(w)
         for n, t in ((1, -np.inf), (20, -np.inf), (20, 0.03), (s.D + 1, 0.03)):
             same_top(s.topic_top_entities(w, n, t), nn.topic_top_entities(prop, n, t), (name, n, t))

@@ -11,9 +11,10 @@ from mvtopicmodel_amd import MvhdpError, NativeSampler, _lib
 from mvtopicmodel_amd.native import Hyper, NativeGroup, merge_topic_phrases
 from tests import jni_harness as H
 from tests import phrases_numpy as pn
+from tests.helpers import INV, STATE, untouched
+from tests.native_build import jvm  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-INV, STATE = -1, -2                                                          # MVHDP_ERR_INVALID_ARG, MVHDP_ERR_STATE
 LENGTHS = [0, 1, 2, 3, 63, 64, 65, 127, 128, 129]
 
 
@@ -213,10 +214,6 @@ def raw_call(s, max_n, cap_p, cap_w, sentinel=-7):
     return rc, arr, n.value, w.value
 
 
-def untouched(arr, sentinel=-7):
-    return all((a == sentinel).all() for a in arr.values())
-
-
 def test_capacity_protocol(base):
     s, K, V0, off, tok, z, ph = base
     want = pn.topic_phrases(K, off, tok, z, 20)
@@ -338,12 +335,6 @@ def test_merge_over_two_handles_equals_one_handle():
 
 # ---- the Java path: the four shim sources as one library, under the test-side JNIEnv (tests/jni_harness.py) ---------------------------
 IAE = "java/lang/IllegalArgumentException"
-
-
-@pytest.fixture(scope="module")
-def jvm(tmp_path_factory):
-    _lib.load_library()
-    return H.Jvm(H.build_shim(tmp_path_factory.mktemp("phrases_jni"), _lib.LIB_PATH, one_tu=True))       # the four shim sources as one translation unit
 
 
 def test_the_java_entry_equals_the_binding(jvm, base):

@@ -10,56 +10,9 @@ from mvtopicmodel_amd.native import (SWEEP_ASYNC_EXCHANGE, SWEEP_LIVE, SWEEP_LIV
                                      EmbConfig)
 from tests import remap_cases as rc
 from tests import remap_numpy as rn
+from tests.helpers import INV, STATE, UNSUPPORTED, assert_holds, assert_same_handles, hyper_with, load, state_of
 
 pytestmark = pytest.mark.gpu
-INV, STATE, UNSUPPORTED = -1, -2, -6                                         # MVHDP_ERR_INVALID_ARG, _STATE, _UNSUPPORTED
-
-
-def load(c, z=None, hy=None, counts=True, doc_id_base=0):
-    s = NativeSampler(c.K, c.V, doc_id_base=doc_id_base)
-    for m in range(c.M):
-        s.set_corpus(m, c.doc_off[m], c.tokens[m])
-        s.set_assignments(m, c.z[m] if z is None else z[m])
-    s.set_hyper(c.hy if hy is None else hy)
-    if counts:
-        s.build_counts()
-    return s
-
-
-def hyper_with(c, alpha, inactive):
-    hy = type(c.hy)(**{k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in vars(c.hy).items()})
-    hy.alpha, hy.inactive = alpha.copy(), inactive.copy()
-    return hy
-
-
-def state_of(s):
-    """everything the call may move, as bytes"""
-    parts = [s.get_assignments(m).tobytes() for m in range(s.M)]
-    for m in range(s.M):
-        nwk, nk = s.get_counts(m)
-        parts += [nwk.tobytes(), nk.tobytes()]
-    a, off = s.get_alpha()
-    return b"".join(parts + [a.tobytes(), off.tobytes()])
-
-
-def assert_is(s, c, want, what):
-    """the handle holds the restatement's z', the recount of it, alpha' bit for bit and inactive'"""
-    for m in range(c.M):
-        assert np.array_equal(s.get_assignments(m), want.z[m]), (what, "z", m)
-        nwk, nk = s.get_counts(m)
-        ref_nwk, ref_nk = rn.counts_of(c.K, c.V[m], c.tokens[m], want.z[m])
-        assert np.array_equal(nk, ref_nk), (what, "n_k", m, np.flatnonzero(nk != ref_nk)[:6])
-        assert np.array_equal(nwk, ref_nwk), (what, "n_wk", m, np.argwhere(nwk != ref_nwk)[:6])
-    a, off = s.get_alpha()
-    assert a.tobytes() == want.alpha.tobytes(), (what, "alpha", np.argwhere(a != want.alpha)[:6])
-    assert np.array_equal(off, want.inactive), (what, "inactive")
-
-
-def assert_same(a, b, M, what):
-    for m in range(M):
-        assert np.array_equal(a.get_assignments(m), b.get_assignments(m)), (what, "z", m)
-        ca, cb = a.get_counts(m), b.get_counts(m)
-        assert np.array_equal(ca[0], cb[0]) and np.array_equal(ca[1], cb[1]), (what, "counts", m)
 
 
 # ---- 1. every integer and bit ---------------------------------------------------------------------------------------------------------
@@ -78,14 +31,14 @@ def test_every_integer_and_bit_equals_the_restatement(K, M):
                 s.build_counts()
                 want = rn.remap(K, c.z, alpha0, off0, tm, rn.RETIRE if retire else 0)
                 st = s.remap_topics(tm, retire=retire)
-                assert_is(s, c, want, what)
+                assert_holds(s, c, want, rn.counts_of, what)
                 assert np.array_equal(st.moved, want.moved) and np.array_equal(st.dropped, want.dropped), (what, st, want.moved, want.dropped)
                 assert (st.vacated, st.retired) == (want.vacated, want.retired) and st.kernel_ms > 0.0, (what, st)
                 if not retire:                                               # the counts are those mvhdp_build_counts makes of z'
                     for m in range(M):
                         second.set_assignments(m, want.z[m])
                     second.build_counts()
-                    assert_same(s, second, M, what)
+                    assert_same_handles(s, second, M, what)
         assert want.retired > 0 or K == 1                                    # (the last map vacates something)
 
 
@@ -103,7 +56,7 @@ def chain(c, tm, retire, expect_births):
         assert st.dropped.sum() > 0 and st.moved.sum() > 0 and np.array_equal(st.moved, want.moved)
         assert (st.vacated, st.retired) == (want.vacated, want.retired) and (st.retired > 0) == retire
         with load(c, z=want.z, hy=hyper_with(c, want.alpha, want.inactive)) as b:
-            assert_same(a, b, M, "before the sweeps")
+            assert_same_handles(a, b, M, "before the sweeps")
             births = 0
             for idx, flags, name in sweeps:
                 offs = [x.get_alpha()[1] for x in (a, b)]
@@ -115,7 +68,7 @@ def chain(c, tm, retire, expect_births):
                         assert e.value.code == UNSUPPORTED
                     continue
                 sa, sb = a.sweep(idx, 17, flags=flags), b.sweep(idx, 17, flags=flags)
-                assert_same(a, b, M, name)
+                assert_same_handles(a, b, M, name)
                 assert (sa.tokens, sa.changed, sa.activations, sa.activated_topic) == (sb.tokens, sb.changed, sb.activations, sb.activated_topic), name
                 assert a.model_log_likelihood().tobytes() == b.model_log_likelihood().tobytes(), name
                 assert a.get_alpha()[0].tobytes() == b.get_alpha()[0].tobytes(), name

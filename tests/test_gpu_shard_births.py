@@ -5,11 +5,12 @@ A shard's NO_APPLY live sweep does the same chunk by chunk, activates nothing, a
 import numpy as np
 import pytest
 
-from mvtopicmodel_amd import NativeGroup, synth
+from mvtopicmodel_amd import NativeGroup
 from mvtopicmodel_amd._lib import MvhdpError
 from mvtopicmodel_amd.native import (ACT_KEY_NONE, BUF_BIRTH_KEYS, BUF_DELTA, Hyper, SWEEP_FROZEN, SWEEP_LIVE, SWEEP_LIVE_SEGMENTS,
                                      SWEEP_NO_APPLY, SWEEP_ONLY_SEGMENT, SWEEP_SHARD_BIRTHS)
-from tests.helpers import assert_same_state, make_native, make_oracle, small_corpus
+from tests.helpers import assert_same_state, make_native, make_oracle, recount, shards_of, small_corpus
+from tests.near_ties import longest_first
 
 pytestmark = pytest.mark.gpu
 
@@ -30,11 +31,6 @@ def _model():
         o.set_assignments(m, z[m])
     o.build_counts()
     return c, hy, o, z
-
-
-def _longest_first(doc_off):
-    tot = sum(np.diff(np.asarray(o)) for o in doc_off)
-    return np.argsort(-tot, kind="stable").astype(np.int64)
 
 
 def _key_topic(k):
@@ -66,15 +62,11 @@ def _recount_ok(c, z_by_view, samplers):
 
 def _shards(c, hy, z, n):
     """n NativeSamplers over contiguous entity ranges balanced by token count, each holding the GLOBAL counts (a full replica)"""
-    tot = sum(np.diff(c.doc_off[m]) for m in range(c.M))
     out = []
-    for lo, hi in synth.shard_bounds(tot, n):
-        sub = c.slice_docs(lo, hi)
-        zs = [z[m][c.doc_off[m][lo]:c.doc_off[m][hi]] for m in range(c.M)]
+    for lo, sub, zs in shards_of(c, z, n):
         s = make_native(sub, hy, zs, doc_id_base=lo)
         for m in range(c.M):
-            nwk = np.zeros((c.V[m], K), dtype=np.int64)
-            np.add.at(nwk, (c.tokens[m], z[m]), 1)
+            nwk = recount(c.tokens[m], z[m], c.V[m], K)
             s.set_counts(m, nwk, nwk.sum(axis=0))
         out.append(s)
     return out
@@ -88,7 +80,7 @@ def test_one_handle_shard_births_then_activation_equal_the_plain_live_sweep_and_
     b = make_native(c, hy, z)
     for s in (a, b):
         s.set_tuning(live16=0, single_wave=1, live_rows=1, force_primary=1)
-    order = _longest_first(c.doc_off)
+    order = longest_first(c.doc_off)
     born = []
     for it in range(3):
         ina_before = b.get_alpha()[1].copy()

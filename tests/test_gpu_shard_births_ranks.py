@@ -11,18 +11,11 @@ import numpy as np
 import pytest
 
 from tests import shard_births_worker as W
+from tests.native_build import fake_rccl  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def fake_rccl(tmp_path_factory):
-    out = str(tmp_path_factory.mktemp("fake_rccl") / "libfake_rccl.so")
-    subprocess.check_call(["gcc", "-O2", "-shared", "-fPIC", "-I/opt/rocm/include", os.path.join(ROOT, "tests", "native", "fake_rccl.c"), "-o", out,
-                           "-L/opt/rocm/lib", "-lamdhip64", "-lrt", "-lpthread", "-Wl,-rpath,/opt/rocm/lib"])
-    return out
 
 
 def _run(tmp_path, fake, nranks, single_wave, timeout=240):

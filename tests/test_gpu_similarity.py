@@ -5,22 +5,21 @@ fp32 screen is held to its contract -- it never decides: whatever it lets throug
 by the derived margin -- through the call's own statistics.  Shapes: one k-step, an odd k tail, the BASELINE topic counts; n at and
 around the 32- and 128-wide tile edges; ragged stripes; the regrow path of the candidate buffer."""
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 
 from mvtopicmodel_amd import MvhdpError, NativeSampler, _lib
-from mvtopicmodel_amd.native import Hyper, round_similarity, sim_probe
+from mvtopicmodel_amd.native import round_similarity, sim_probe
 from tests import jni_harness as H
 from tests import sim_numpy as sn
+from tests.helpers import INV, golden_sampler
+from tests.native_build import jvm  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 DIMS = [1, 2, 3, 33, 100, 400, 1000]
 NS = [1, 2, 31, 32, 33, 127, 128, 129, 300]
 THRESHOLDS = [0.0, 0.15, 0.3, 0.9]
-INV = -1                                                                    # MVHDP_ERR_INVALID_ARG
 
 
 @pytest.fixture(scope="module")
@@ -216,22 +215,6 @@ W3 = np.array([1.0, 0.7, 0.4])
 CUTS = [(0.0, -1), (0.03, -1), (0.03, 3), (0.5, 1)]
 
 
-def golden_sampler(name):
-    g = np.load(os.path.join(HERE, "golden", name + ".npz"))
-    K, V = int(g["K"]), [int(v) for v in g["V"]]
-    hy = Hyper(alpha=g["alpha"], alpha_sum=g["alpha_sum"], beta=g["beta"], beta_sum=g["beta_sum"], gamma=g["gamma"],
-               p_a=g["p_a"], p_b=g["p_b"], inactive=g["inactive"])
-    smp = NativeSampler(K, V)
-    for m in range(len(V)):
-        smp.set_corpus(m, g[f"doc_off{m}"], g[f"tokens{m}"])
-        smp.set_assignments(m, g[f"z0_{m}"])
-    smp.set_hyper(hy)
-    smp.build_counts()
-    for it in range(2):
-        smp.sweep(it, int(g["sweep_seed"]))
-    return smp, g, hy
-
-
 def groups_of(D, prop):
     rng = np.random.default_rng(D)
     return [[d] for d in range(D)] + [list(range(D)), list(range(0, D, 2)), list(range(D // 3, D)), [], list(rng.permutation(D)[:9]) + [4, 4]]
@@ -281,12 +264,6 @@ def test_topic_lists_and_entity_distributions_on_the_goldens(s, name):
 
 # ---- the Java path: the four shim sources as one library, under the test-side JNIEnv (tests/jni_harness.py) ---------------------------
 IAE = "java/lang/IllegalArgumentException"
-
-
-@pytest.fixture(scope="module")
-def jvm(tmp_path_factory):
-    _lib.load_library()
-    return H.Jvm(H.build_shim(tmp_path_factory.mktemp("sim_jni"), _lib.LIB_PATH, one_tu=True))       # the four shim sources as one translation unit
 
 
 def test_the_java_entries_equal_the_binding(jvm):

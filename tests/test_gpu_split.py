@@ -17,20 +17,9 @@ from mvtopicmodel_amd._lib import SplitArgsC
 from mvtopicmodel_amd.native import SWEEP_LIVE, SWEEP_LIVE_SEGMENTS, SWEEP_NO_APPLY, SWEEP_SEGMENT_APPLY, EmbConfig
 from tests import split_cases as sc
 from tests import split_ref as sr
+from tests.helpers import INV, STATE, UNSUPPORTED, assert_holds, assert_same_handles, hyper_with, load, state_of
 
 pytestmark = pytest.mark.gpu
-INV, STATE, UNSUPPORTED = -1, -2, -6                                         # MVHDP_ERR_INVALID_ARG, _STATE, _UNSUPPORTED
-
-
-def load(c, z=None, hy=None, counts=True, doc_id_base=0):
-    s = NativeSampler(c.K, c.V, doc_id_base=doc_id_base)
-    for m in range(c.M):
-        s.set_corpus(m, c.doc_off[m], c.tokens[m])
-        s.set_assignments(m, c.z[m] if z is None else z[m])
-    s.set_hyper(c.hy if hy is None else hy)
-    if counts:
-        s.build_counts()
-    return s
 
 
 def reset(s, c):
@@ -40,47 +29,10 @@ def reset(s, c):
     s.build_counts()
 
 
-def hyper_with(c, alpha, inactive):
-    hy = type(c.hy)(**{k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in vars(c.hy).items()})
-    hy.alpha, hy.inactive = alpha.copy(), inactive.copy()
-    return hy
-
-
-def state_of(s):
-    """everything the call may move, as bytes"""
-    parts = [s.get_assignments(m).tobytes() for m in range(s.M)]
-    for m in range(s.M):
-        nwk, nk = s.get_counts(m)
-        parts += [nwk.tobytes(), nk.tobytes()]
-    a, off = s.get_alpha()
-    return b"".join(parts + [a.tobytes(), off.tobytes()])
-
-
-def assert_is(s, c, want, what):
-    """the handle holds the restatement's z', the recount of it, alpha' bit for bit and inactive'"""
-    for m in range(c.M):
-        got = s.get_assignments(m)
-        assert np.array_equal(got, want.z[m]), (what, "z", m, np.flatnonzero(got != want.z[m])[:6])
-        nwk, nk = s.get_counts(m)
-        ref_nwk, ref_nk = sr.counts_of(c.K, c.V[m], c.tokens[m], want.z[m])
-        assert np.array_equal(nk, ref_nk), (what, "n_k", m, np.flatnonzero(nk != ref_nk)[:6])
-        assert np.array_equal(nwk, ref_nwk), (what, "n_wk", m, np.argwhere(nwk != ref_nwk)[:6])
-    a, off = s.get_alpha()
-    assert a.tobytes() == want.alpha.tobytes(), (what, "alpha", np.argwhere(a != want.alpha)[:6])
-    assert np.array_equal(off, want.inactive), (what, "inactive")
-
-
 def assert_stats(st, want, what):
     assert np.array_equal(st.split, want.split) and np.array_equal(st.moved, want.moved), (what, st, want.split, want.moved)
     assert np.array_equal(st.flips, want.flips) and st.flips_last == want.flips_last, (what, st.flips, want.flips)
     assert (st.target, int(st.activated)) == (want.target, want.activated) and st.kernel_ms > 0.0, (what, st)
-
-
-def assert_same(a, b, M, what):
-    for m in range(M):
-        assert np.array_equal(a.get_assignments(m), b.get_assignments(m)), (what, "z", m)
-        ca, cb = a.get_counts(m), b.get_counts(m)
-        assert np.array_equal(ca[0], cb[0]) and np.array_equal(ca[1], cb[1]), (what, "counts", m)
 
 
 # ---- 1. every integer and bit ---------------------------------------------------------------------------------------------------------
@@ -100,12 +52,12 @@ def test_every_integer_and_bit_equals_the_restatement(K, M):
             want = sr.run(K, c.V, c.doc_off, c.tokens, c.z, c.hy, c.source, doc_id_base=base, **kw)
             assert want.rc == 0 and 0 < want.moved.sum() < want.split.sum()
             st = s.split_topic(c.source, **kw)
-            assert_is(s, c, want, what)
+            assert_holds(s, c, want, sr.counts_of, what)
             assert_stats(st, want, what)
             for m in range(M):                                               # the counts are those mvhdp_build_counts makes of z'
                 second.set_assignments(m, want.z[m])
             second.build_counts()
-            assert_same(s, second, M, what)
+            assert_same_handles(s, second, M, what)
             if first:                                                        # the same call on another handle: the same bytes
                 reset(second, c)
                 st2 = second.split_topic(c.source, **kw)
@@ -135,12 +87,12 @@ def test_the_chain_goes_on_as_on_a_fresh_handle():
         assert_stats(st, want, "chain")
         assert st.activated and st.target == free[0] and 0 < st.moved.sum() < st.split.sum()
         with load(c, z=want.z, hy=hyper_with(c, want.alpha, want.inactive)) as b:
-            assert_same(a, b, M, "before the sweeps")
+            assert_same_handles(a, b, M, "before the sweeps")
             for idx, flags, name in sweeps:
                 offs = [x.get_alpha()[1] for x in (a, b)]
                 assert np.array_equal(offs[0], offs[1])
                 sa, sb = a.sweep(idx, 17, flags=flags), b.sweep(idx, 17, flags=flags)
-                assert_same(a, b, M, name)
+                assert_same_handles(a, b, M, name)
                 assert (sa.tokens, sa.changed, sa.activations, sa.activated_topic) == (sb.tokens, sb.changed, sb.activations, sb.activated_topic), name
                 assert a.model_log_likelihood().tobytes() == b.model_log_likelihood().tobytes(), name
                 assert a.get_alpha()[0].tobytes() == b.get_alpha()[0].tobytes(), name

@@ -14,30 +14,9 @@ from mvtopicmodel_amd.native import SWEEP_LIVE, SWEEP_NO_APPLY, NativeGroup, mer
 from tests import gram_cases as gc
 from tests import gram_ref as gr
 from tests import xview_ref as xr
+from tests.helpers import INV, STATE, bits, load
 
 pytestmark = pytest.mark.gpu
-INV, STATE = -1, -2                                                          # MVHDP_ERR_INVALID_ARG, MVHDP_ERR_STATE
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
-
-
-def load(c, lo=0, hi=None, counts=None):
-    """a sampler holding entities [lo, hi) of the case; counts: built from its own assignments, or given (a group's replicated counts)"""
-    hi = c.D if hi is None else hi
-    s = NativeSampler(c.K, c.V)
-    for v in range(c.M):
-        off = c.doc_off[v]
-        s.set_corpus(v, off[lo:hi + 1] - off[lo], c.tokens[v][off[lo]:off[hi]])
-        s.set_assignments(v, c.z[v][off[lo]:off[hi]])
-    s.set_hyper(c.hy)
-    if counts is None:
-        s.build_counts()
-    else:
-        for v in range(c.M):
-            s.set_counts(v, *counts[v])
-    return s
 
 
 def check(got, x, transform="identity", threshold=None, what=""):

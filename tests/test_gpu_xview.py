@@ -13,26 +13,9 @@ from mvtopicmodel_amd import MvhdpError, NativeSampler, _lib
 from mvtopicmodel_amd.native import SWEEP_LIVE, SWEEP_NO_APPLY, NativeGroup
 from tests import xview_cases as xc
 from tests import xview_ref as xr
+from tests.helpers import INV, STATE, load
 
 pytestmark = pytest.mark.gpu
-INV, STATE = -1, -2                                                          # MVHDP_ERR_INVALID_ARG, MVHDP_ERR_STATE
-
-
-def load(c, lo=0, hi=None, counts=None):
-    """a sampler holding entities [lo, hi) of the case; counts: built from its own assignments, or given (a group's replicated counts)"""
-    hi = c.D if hi is None else hi
-    s = NativeSampler(c.K, c.V)
-    for v in range(c.M):
-        off = c.doc_off[v]
-        s.set_corpus(v, off[lo:hi + 1] - off[lo], c.tokens[v][off[lo]:off[hi]])
-        s.set_assignments(v, c.z[v][off[lo]:off[hi]])
-    s.set_hyper(c.hy)
-    if counts is None:
-        s.build_counts()
-    else:
-        for v in range(c.M):
-            s.set_counts(v, *counts[v])
-    return s
 
 
 class Loaded:

@@ -12,6 +12,7 @@ import pytest
 
 from tests import gram_cases as gc
 from tests import gram_ref as gr
+from tests.helpers import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAME = "mvhdp_topic_gram"
@@ -21,10 +22,6 @@ STATS_FIELDS = ["rows", "blocks", "passes", "kernel_ms"]
 
 def read(*parts):
     return open(os.path.join(ROOT, *parts)).read()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_the_entry_exists_in_every_layer():

@@ -13,6 +13,7 @@ from tests import xview_cases as xc
 from tests import xview_entities_cases as ec
 from tests import xview_entities_ref as er
 from tests import xview_ref as xr
+from tests.helpers import bits
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("mvhdp_predict_entities", "mvhdp_rank_entities")
@@ -22,10 +23,6 @@ STATS_FIELDS = ["cells", "excluded", "blocks", "kernel_ms"]
 
 def read(*parts):
     return open(os.path.join(ROOT, *parts)).read()
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
 
 
 def test_the_entries_exist_in_every_layer():

@@ -2,24 +2,19 @@
 (built once per process with gcc -O2 -ffp-contract=off, together with tests/native/xview_ref.c whose xview_phi it calls, into a temporary
 directory).  Test infrastructure: no GPU, no product code."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 from dataclasses import dataclass
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRCS = [os.path.join(HERE, "native", "xview_entities_ref.c"), os.path.join(HERE, "native", "xview_ref.c")]
+from tests.native_build import ptr, ref_lib
+
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="xview_entities_ref_"), "libxview_entities_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11", *SRCS, "-o", so, "-lm"])
-        L = C.CDLL(so)
+        L = ref_lib("xview_entities_ref", "xview_ref.c")
         vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
         L.xve_psi_from_counts.argtypes = [i32, i32, vp, vp, vp, dbl, dbl, i64, vp, vp, vp, vp]
         L.xve_psi_from_counts.restype = i32
@@ -33,10 +28,6 @@ def lib():
         L.xve_rank.restype = None
         _lib = L
     return _lib
-
-
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
 def flatten(items, weights=None):
@@ -60,7 +51,7 @@ def psi_rows(nwk, nk, beta, beta_sum, inactive, items, weights=None):
     off, flat, fw = flatten(items, weights)
     assert len(flat) == 0 or (flat.min() >= 0 and flat.max() < V)
     out = np.zeros((len(off) - 1, K))
-    assert lib().xve_psi_from_counts(K, V, _p(nwk), _p(nk), _p(ina), float(beta), float(beta_sum), len(off) - 1, _p(off), _p(flat), _p(fw), _p(out)) == 0
+    assert lib().xve_psi_from_counts(K, V, ptr(nwk), ptr(nk), ptr(ina), float(beta), float(beta_sum), len(off) - 1, ptr(off), ptr(flat), ptr(fw), ptr(out)) == 0
     return out
 
 
@@ -72,7 +63,7 @@ def scores(theta, psi):
     nq = psi.shape[0]
     assert psi.shape == (nq, K)
     out = np.zeros((nq, Cn))
-    lib().xve_scores(K, nq, Cn, _p(theta), _p(psi), _p(out))
+    lib().xve_scores(K, nq, Cn, ptr(theta), ptr(psi), ptr(out))
     return out
 
 
@@ -84,7 +75,7 @@ def excluded(doc_off, tok, items):
     assert len(tok) == doc_off[-1]
     off, flat, _ = flatten(items)
     out = np.zeros((len(off) - 1, len(doc_off) - 1), dtype=np.uint8)
-    lib().xve_excluded(len(doc_off) - 1, _p(doc_off), _p(tok), len(off) - 1, _p(off), _p(flat), _p(out))
+    lib().xve_excluded(len(doc_off) - 1, ptr(doc_off), ptr(tok), len(off) - 1, ptr(off), ptr(flat), ptr(out))
     return out
 
 
@@ -97,7 +88,7 @@ def predict(S, n, ex=None, id0=0):
     ids = np.zeros((nq, n), dtype=np.int64)
     sc = np.zeros((nq, n))
     counts = np.zeros(nq, dtype=np.int32)
-    assert lib().xve_predict(nq, Cn, _p(S), _p(ex), int(n), int(id0), _p(ids), _p(sc), _p(counts)) == 0
+    assert lib().xve_predict(nq, Cn, ptr(S), ptr(ex), int(n), int(id0), ptr(ids), ptr(sc), ptr(counts)) == 0
     return ids, sc, counts
 
 
@@ -111,7 +102,7 @@ def rank(S, query, cand, ex=None):
     assert query.shape == cand.shape and (len(query) == 0 or (query.min() >= 0 and query.max() < nq and cand.min() >= 0 and cand.max() < Cn))
     score = np.zeros(len(query))
     rk = np.zeros(len(query), dtype=np.int64)
-    lib().xve_rank(Cn, _p(S), _p(ex), len(query), _p(query), _p(cand), _p(score), _p(rk))
+    lib().xve_rank(Cn, ptr(S), ptr(ex), len(query), ptr(query), ptr(cand), ptr(score), ptr(rk))
     return score, rk
 
 

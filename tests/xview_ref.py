@@ -1,14 +1,11 @@
 """ctypes wrapper of tests/native/xview_ref.c, the sequential restatement of the cross-view prediction contract of include/mvhdp.h
 (built once per process with gcc -O2 -ffp-contract=off into a temporary directory).  Test infrastructure: no GPU, no product code."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-SRC = os.path.join(HERE, "native", "xview_ref.c")
+from tests.native_build import ptr, ref_lib
+
 ASCENDING, DESCENDING, UNFUSED = 0, 1, 2         # xview_chain's variants: the contract's chain, and two the sensitivity tests run
 _lib = None
 
@@ -16,9 +13,7 @@ _lib = None
 def lib():
     global _lib
     if _lib is None:
-        so = os.path.join(tempfile.mkdtemp(prefix="xview_ref_"), "libxview_ref.so")
-        subprocess.check_call(["gcc", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-std=gnu11", SRC, "-o", so, "-lm"])
-        L = C.CDLL(so)
+        L = ref_lib("xview_ref")
         vp, i32, i64, dbl = C.c_void_p, C.c_int32, C.c_int64, C.c_double
         L.xview_chain.argtypes = [i32, vp, vp, i32]
         L.xview_chain.restype = dbl
@@ -34,15 +29,11 @@ def lib():
     return _lib
 
 
-def _p(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
-
-
 def chain(theta, phi, variant=ASCENDING):
     theta = np.ascontiguousarray(theta, dtype=np.float64)
     phi = np.ascontiguousarray(phi, dtype=np.float64)
     assert theta.shape == phi.shape and theta.ndim == 1
-    return float(lib().xview_chain(len(theta), _p(theta), _p(phi), int(variant)))
+    return float(lib().xview_chain(len(theta), ptr(theta), ptr(phi), int(variant)))
 
 
 def phi_table(nwk, nk, beta, beta_sum, inactive=None):
@@ -52,7 +43,7 @@ def phi_table(nwk, nk, beta, beta_sum, inactive=None):
     assert nk.shape == (K,)
     ina = None if inactive is None else np.ascontiguousarray(inactive, dtype=np.uint8)
     out = np.zeros((V, K))
-    lib().xview_phi(K, V, _p(nwk), _p(nk), _p(ina), float(beta), float(beta_sum), _p(out))
+    lib().xview_phi(K, V, ptr(nwk), ptr(nk), ptr(ina), float(beta), float(beta_sum), ptr(out))
     return out
 
 
@@ -64,7 +55,7 @@ def scores(theta, phi, variant=ASCENDING):
     V = phi.shape[0]
     assert phi.shape == (V, K)
     out = np.zeros((D, V))
-    lib().xview_scores(K, V, D, _p(theta), _p(phi), int(variant), _p(out))
+    lib().xview_scores(K, V, D, ptr(theta), ptr(phi), int(variant), ptr(out))
     return out
 
 
@@ -85,7 +76,7 @@ def predict(S, n, exclude_present=False, doc_off=None, tok=None):
     items = np.zeros((D, n), dtype=np.int32)
     sc = np.zeros((D, n))
     counts = np.zeros(D, dtype=np.int32)
-    assert lib().xview_predict(V, D, _p(S), 1 if exclude_present else 0, _p(doc_off), _p(tok), int(n), _p(items), _p(sc), _p(counts)) == 0
+    assert lib().xview_predict(V, D, ptr(S), 1 if exclude_present else 0, ptr(doc_off), ptr(tok), int(n), ptr(items), ptr(sc), ptr(counts)) == 0
     return items, sc, counts
 
 
@@ -99,5 +90,5 @@ def score_pairs(S, entity, item, exclude_present=False, doc_off=None, tok=None):
     assert entity.shape == item.shape and (len(entity) == 0 or (entity.min() >= 0 and entity.max() < D and item.min() >= 0 and item.max() < V))
     score = np.zeros(len(entity))
     rank = np.zeros(len(entity), dtype=np.int32)
-    assert lib().xview_score_pairs(V, _p(S), 1 if exclude_present else 0, _p(doc_off), _p(tok), len(entity), _p(entity), _p(item), _p(score), _p(rank)) == 0
+    assert lib().xview_score_pairs(V, ptr(S), 1 if exclude_present else 0, ptr(doc_off), ptr(tok), len(entity), ptr(entity), ptr(item), ptr(score), ptr(rank)) == 0
     return score, rank

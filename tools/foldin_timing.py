@@ -19,29 +19,10 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SEED = 20260101                                                              # bench.py's
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import SEED, timed, trained_sampler  # noqa: E402
+
 ITERATIONS = 10
-
-
-def trained_sampler(workload, docs, sweeps):
-    from mvtopicmodel_amd import NativeSampler, synth
-    from mvtopicmodel_amd.java_init import init_assignments
-    from mvtopicmodel_amd.native import Hyper
-    cfg = dict(synth.CONFIGS[workload])
-    D = docs or cfg["D"]
-    K, V = cfg["K"], cfg["V"]
-    corpus = synth.make_config(workload, D=D, doc_lo=0, doc_hi=D)
-    inactive, K_init = synth.config_inactive(workload)
-    z0 = init_assignments(K_init, corpus.doc_off, seed=1)
-    s = NativeSampler(K, V)
-    for m in range(len(V)):
-        s.set_corpus(m, corpus.doc_off[m], corpus.tokens[m])
-        s.set_assignments(m, z0[m])
-    hy = Hyper.defaults(K, V, inactive=inactive)
-    s.set_hyper(hy)
-    s.build_counts()
-    st = [s.sweep(i, SEED) for i in range(sweeps)]
-    return s, hy, [x.total_ms for x in st], st[-1].tokens, D
 
 
 def free_bytes():
@@ -50,15 +31,6 @@ def free_bytes():
         return int(torch.cuda.mem_get_info()[0])
     except Exception:
         return None
-
-
-def timed(f, n):
-    out, r = [], None
-    for _ in range(n):
-        t0 = time.perf_counter()
-        r = f()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return out[0], statistics.median(out[1:]) if n > 1 else out[0], r
 
 
 def second_handle_route(s, hy, K, V, off, tok, w):
@@ -103,7 +75,8 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "foldin.md"))
     args = ap.parse_args()
     from mvtopicmodel_amd import synth
-    s, hy, sweep_ms, sweep_tokens, D = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, hy, _, D, sweeps = trained_sampler(args.workload, args.docs, args.sweeps)
+    sweep_ms, sweep_tokens = [x.total_ms for x in sweeps], sweeps[-1].tokens
     free_bytes()                                                             # (torch's first device query, outside every timed region)
     c = dict(synth.CONFIGS[args.workload])
     K, V, M = c["K"], c["V"], len(c["V"])

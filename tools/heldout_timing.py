@@ -13,47 +13,22 @@ cost does not depend on the count values (every visit reads a whole row), so the
 briefly on a cut of the corpus; no wall time is taken from them.  A child that exits with an error or does not end within its time limit
 ends the profiling: its whole process group is killed, the report says so, and no further run is started on the GPU."""
 import argparse
-import csv
-import glob
 import os
-import re
-import shutil
-import signal
 import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SEED = 20260101                                                              # bench.py's
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import SEED, ChildFailed, profiled, timed, trained_sampler  # noqa: E402
+
 PARTICLES = 10
 MI355X_CUS, MI355X_MAX_GHZ = 256, 2.4                                        # the chip the figures are read against
 COUNTERS = ["SQ_WAVE_CYCLES", "SQ_BUSY_CYCLES", "SQ_ACTIVE_INST_VALU", "SQ_ACTIVE_INST_LDS", "SQ_WAIT_ANY", "SQ_WAIT_INST_ANY", "SQ_INSTS_VALU", "SQ_INSTS_VMEM_RD"]
-
-
-def trained_sampler(workload, docs, sweeps):
-    from mvtopicmodel_amd import NativeSampler, synth
-    from mvtopicmodel_amd.java_init import init_assignments
-    from mvtopicmodel_amd.native import Hyper
-    cfg = dict(synth.CONFIGS[workload])
-    D = docs or cfg["D"]
-    K, V = cfg["K"], cfg["V"]
-    corpus = synth.make_config(workload, D=D, doc_lo=0, doc_hi=D)
-    inactive, K_init = synth.config_inactive(workload)
-    z0 = init_assignments(K_init, corpus.doc_off, seed=1)
-    s = NativeSampler(K, V)
-    for m in range(len(V)):
-        s.set_corpus(m, corpus.doc_off[m], corpus.tokens[m])
-        s.set_assignments(m, z0[m])
-    hy = Hyper.defaults(K, V, inactive=inactive)
-    s.set_hyper(hy)
-    s.build_counts()
-    st = [s.sweep(i, SEED) for i in range(sweeps)]
-    return s, hy, [x.total_ms for x in st], st[-1].tokens, D
+KERNELS = r"heldout_\w+(<[\w, ]+>)?"
 
 
 def heldout_inputs(workload, D, n):
@@ -63,60 +38,6 @@ def heldout_inputs(workload, D, n):
     other = synth.generate(c["K"], c["V"], n, c["lam"], c["seed"] ^ 0x48454C44, power_law_text=c.get("power_law_text", False))
     nxt = synth.generate(c["K"], c["V"], D + n, c["lam"], c["seed"], power_law_text=c.get("power_law_text", False), doc_lo=D, doc_hi=D + n)
     return (other.doc_off[0], other.tokens[0]), (nxt.doc_off[0], nxt.tokens[0])
-
-
-def timed(f, n=4):
-    out, r = [], None
-    for _ in range(n):
-        t0 = time.perf_counter()
-        r = f()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return out[0], statistics.median(out[1:]), r
-
-
-class ChildFailed(RuntimeError):
-    """a profiled child run ended with a non-zero status or ran into its time limit: nothing more is started on the GPU in this call"""
-
-
-def profiled(mode, argv, limit=400):
-    """A child run under rocprofv3, in a process group of its own: mode 'trace' -> {kernel: (calls, total ms)}; 'pmc' -> {counter: sum over
-    the heldout_ltr dispatches}.  None when rocprofv3 is not installed (nothing was started) or its output has no such rows.  ChildFailed
-    when the child exits with a non-zero status (a fault, an abort) or does not end within `limit` seconds; the whole group -- rocprofv3 and
-    the python process under it that holds the GPU -- is killed before that is raised."""
-    if shutil.which("rocprofv3") is None:
-        return None
-    with tempfile.TemporaryDirectory() as d:
-        what = ["--kernel-trace", "--stats"] if mode == "trace" else ["--pmc"] + COUNTERS
-        cmd = ["rocprofv3"] + what + ["-d", d, "-o", "heldout", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__)] + argv + ["--child"]
-        child = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
-        try:
-            rc = child.wait(timeout=limit)
-        except subprocess.TimeoutExpired:
-            rc = None
-        if rc != 0:
-            try:
-                os.killpg(child.pid, signal.SIGKILL)                         # the session leader's pid is the group's
-            except ProcessLookupError:
-                pass
-            child.wait()
-            raise ChildFailed(f"the {mode} run " + ("did not end within %d s" % limit if rc is None else "ended with status %d" % rc))
-        out = {}
-        if mode == "trace":
-            files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-            if not files:
-                return None
-            for row in csv.DictReader(open(files[0])):
-                m = re.search(r"heldout_\w+(<[\w, ]+>)?", row["Name"])
-                if m:
-                    out[m.group(0)] = (int(row["Calls"]), float(row["TotalDurationNs"]) / 1e6)
-        else:
-            files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
-            if not files:
-                return None
-            for row in csv.DictReader(open(files[0])):
-                if "heldout_ltr" in row.get("Kernel_Name", ""):
-                    out[row["Counter_Name"]] = out.get(row["Counter_Name"], 0.0) + float(row["Counter_Value"])
-        return out or None
 
 
 def main():
@@ -131,12 +52,13 @@ def main():
     ap.add_argument("--child", action="store_true", help="(internal) one resampling call, for the profiler")
     args = ap.parse_args()
     if args.child:
-        s, _, _, _, D = trained_sampler(args.workload, 50000, 2)
+        s, _, _, D, _ = trained_sampler(args.workload, 50000, 2)
         (off, tok), _ = heldout_inputs(args.workload, D, args.heldout)
         s.heldout_left_to_right(off, tok, particles=PARTICLES, resample=True, seed=SEED)
         s.close()
         return
-    s, hy, sweep_ms, sweep_tokens, D = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, hy, _, D, sweeps = trained_sampler(args.workload, args.docs, args.sweeps)
+    sweep_ms, sweep_tokens = [x.total_ms for x in sweeps], sweeps[-1].tokens
     print(f"{args.sweeps} sweeps done", file=sys.stderr, flush=True)
     inputs = heldout_inputs(args.workload, D, args.heldout)
     sweep_med = statistics.median(sweep_ms[5:] or sweep_ms)
@@ -150,7 +72,7 @@ def main():
                                  "the generator's next entities under the training seed (unseen documents of the training topics)"], inputs):
         lines += [f"## {name}", "", f"- {len(off) - 1} documents, {len(tok)} tokens, mean length {len(tok) / (len(off) - 1):.1f}, longest {int(np.diff(off).max())}"]
         for rs in (True, False):
-            first, med, r = timed(lambda: s.heldout_left_to_right(off, tok, particles=PARTICLES, resample=rs, seed=SEED))
+            first, med, r = timed(lambda: s.heldout_left_to_right(off, tok, particles=PARTICLES, resample=rs, seed=SEED), n=4)
             lines.append(f"- resample {'on ' if rs else 'off'}: {med:.1f} ms a call (first call {first:.1f} ms); {r.visits} visits = {r.visits / med / 1e6:.3f} G visits/s; "
                          f"log-likelihood {r.log_likelihood:.6e}, {r.tokens} tokens in vocabulary ({r.oov} not), perplexity {r.perplexity:.1f}")
             if rs and visits_per_s is None:
@@ -184,9 +106,9 @@ def main():
         ks = pm = None
         try:                                                                 # a child that fails or hangs ends the profiling: nothing more goes to the GPU
             print("wall times taken; the kernel trace", file=sys.stderr, flush=True)
-            ks = profiled("trace", child_argv)
+            ks = profiled(__file__, child_argv, KERNELS, limit=400)
             print("the counter pass", file=sys.stderr, flush=True)
-            pm = profiled("pmc", child_argv)
+            pm = profiled(__file__, child_argv, "heldout_ltr", mode="pmc", counters=COUNTERS, limit=400)
         except ChildFailed as e:
             lines += [f"- {e}; no further run was started", ""]
             print(f"{e}; no further run was started", file=sys.stderr, flush=True)

@@ -14,48 +14,21 @@ topic_top_entities the same round trip plus numpy.argpartition per topic.  The t
 `rocprofv3 --kernel-trace --stats` on a smaller call (--child-queries handle queries); a child that fails or runs into its time limit
 ends the profiling: its process group is killed and nothing more is started on the GPU."""
 import argparse
-import csv
-import glob
 import os
-import re
-import shutil
-import signal
 import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SEED = 20260101                                                              # bench.py's
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import SEED, ChildFailed, profiled, trained_sampler  # noqa: E402
+
 N_TOP = 20
 PEAK_TF, UNTUNED_TF = 155.0, 122.0                                           # fp32 MFMA: measured peak, and an untuned 4096^3 tile kernel on the same instruction
-
-
-def trained_sampler(workload, docs, sweeps):
-    from mvtopicmodel_amd import NativeSampler, synth
-    from mvtopicmodel_amd.java_init import init_assignments
-    from mvtopicmodel_amd.native import Hyper
-    cfg = dict(synth.CONFIGS[workload])
-    D = docs or cfg["D"]
-    K, V = cfg["K"], cfg["V"]
-    print(f"making {workload} with {D} entities", file=sys.stderr, flush=True)
-    corpus = synth.make_config(workload, D=D, doc_lo=0, doc_hi=D)
-    print("corpus made", file=sys.stderr, flush=True)
-    inactive, K_init = synth.config_inactive(workload)
-    z0 = init_assignments(K_init, corpus.doc_off, seed=1)
-    s = NativeSampler(K, V)
-    for m in range(len(V)):
-        s.set_corpus(m, corpus.doc_off[m], corpus.tokens[m])
-        s.set_assignments(m, z0[m])
-    s.set_hyper(Hyper.defaults(K, V, inactive=inactive))
-    s.build_counts()
-    for i in range(sweeps):
-        s.sweep(i, SEED)
-    return s, D
+KERNELS = r"near_\w+|topk_\w+|sim_prepare_kernel|sim_normalise_kernel|doc_topic_prop_kernel"
 
 
 def timed(f, repeats):
@@ -90,39 +63,6 @@ def host_topic_top(theta, n):
     return (time.perf_counter() - t0) * 1e3
 
 
-class ChildFailed(RuntimeError):
-    """the profiled child run ended with a non-zero status or ran into its time limit: nothing more is started on the GPU in this call"""
-
-
-def kernel_trace(argv, limit=420):
-    """{kernel: (calls, total ms)} of a child run under rocprofv3 in a process group of its own; None without rocprofv3 or kernel rows"""
-    if shutil.which("rocprofv3") is None:
-        return None
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "nearest", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__)] + argv + ["--child"]
-        child = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
-        try:
-            rc = child.wait(timeout=limit)
-        except subprocess.TimeoutExpired:
-            rc = None
-        if rc != 0:
-            try:
-                os.killpg(child.pid, signal.SIGKILL)
-            except ProcessLookupError:
-                pass
-            child.wait()
-            raise ChildFailed("the traced run " + ("did not end within %d s" % limit if rc is None else "ended with status %d" % rc))
-        files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-        if not files:
-            return None
-        out = {}
-        for row in csv.DictReader(open(files[0])):
-            k = re.search(r"near_\w+|topk_\w+|sim_prepare_kernel|sim_normalise_kernel|doc_topic_prop_kernel", row["Name"])
-            if k:
-                out[k.group(0)] = (int(row["Calls"]), float(row["TotalDurationNs"]) / 1e6)
-        return out or None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="C4")
@@ -139,11 +79,11 @@ def main():
     ap.add_argument("--child", action="store_true", help="(internal) one nearest_entities call, for the profiler")
     args = ap.parse_args()
     if args.child:
-        s, D = trained_sampler(args.workload, args.child_docs, 2)
+        s, _, _, D, _ = trained_sampler(args.workload, args.child_docs, 2)
         s.nearest_entities(np.ones(s.M), N_TOP, q0=0, q1=min(args.child_queries, D))
         s.close()
         return
-    s, D = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, _, _, D, _ = trained_sampler(args.workload, args.docs, args.sweeps)
     print(f"{args.sweeps} sweeps done", file=sys.stderr, flush=True)
     K, M = s.K, s.M
     w = np.ones(M)
@@ -190,7 +130,7 @@ def main():
         lines += [f"## the kernels of one nearest_entities call, {cq} handle queries x {cd} candidates (a child run of its own, a model trained for 2 sweeps)", ""]
         try:
             print("wall times taken; the kernel trace", file=sys.stderr, flush=True)
-            ks = kernel_trace(["--workload", args.workload, "--child-queries", str(cq), "--child-docs", str(cd)])
+            ks = profiled(__file__, ["--workload", args.workload, "--child-queries", str(cq), "--child-docs", str(cd)], KERNELS, limit=420)
         except ChildFailed as e:
             ks = None
             lines += [f"- {e}; no further run was started", ""]

@@ -18,13 +18,13 @@ import statistics
 import subprocess
 import sys
 import tempfile
-import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SEED = 20260101                                                              # bench.py's
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import SEED, timed, trained_sampler  # noqa: E402
 
 
 NOTES = ["## Reading the figures", "",
@@ -38,35 +38,6 @@ NOTES = ["## Reading the figures", "",
          "  memsets of the table, five synchronisations -- none of it measured separately.  A host that calls this once after training pays",
          "  it once; a buffer kept on the handle would remove it and was not built (the issue asks for no cache).",
          "- max_per_topic = -1 is host-bound: every distinct phrase crosses and the host sorts them by count and word ids.", ""]
-
-
-def trained_sampler(workload, docs, sweeps):
-    from mvtopicmodel_amd import NativeSampler, synth
-    from mvtopicmodel_amd.java_init import init_assignments
-    from mvtopicmodel_amd.native import Hyper
-    cfg = dict(synth.CONFIGS[workload])
-    D = docs or cfg["D"]
-    K, V = cfg["K"], cfg["V"]
-    corpus = synth.make_config(workload, D=D, doc_lo=0, doc_hi=D)
-    inactive, K_init = synth.config_inactive(workload)
-    z0 = init_assignments(K_init, corpus.doc_off, seed=1)
-    s = NativeSampler(K, V)
-    for m in range(len(V)):
-        s.set_corpus(m, corpus.doc_off[m], corpus.tokens[m])
-        s.set_assignments(m, z0[m])
-    s.set_hyper(Hyper.defaults(K, V, inactive=inactive))
-    s.build_counts()
-    ms = [s.sweep(i, SEED).total_ms for i in range(sweeps)]
-    return s, ms, int(corpus.doc_off[0][-1])
-
-
-def timed(f, n=6):
-    out = []
-    for _ in range(n):
-        t0 = time.perf_counter()
-        f()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return out[0], statistics.median(out[1:])
 
 
 def phrase_call(s, max_n, sizes=None):
@@ -111,18 +82,19 @@ def main():
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--child", action="store_true", help="(internal) one call of each kind, for the kernel trace")
     args = ap.parse_args()
-    s, sweep_ms, n0 = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, _, corpus, _, sweeps = trained_sampler(args.workload, args.docs, args.sweeps)
+    sweep_ms, n0 = [x.total_ms for x in sweeps], int(corpus.doc_off[0][-1])
     print(f"{args.sweeps} sweeps done", file=sys.stderr, flush=True)
     if args.child:
         phrase_call(s, 20)
         s.close()
         return
-    first_q, med_q = timed(lambda: phrase_call(s, 20))
+    first_q, med_q, _ = timed(lambda: phrase_call(s, 20), n=6)
     np_, nw, st = phrase_call(s, 20)
-    first_f, med_f = timed(lambda: phrase_call(s, 20, (np_, nw)))
-    _, med_all = timed(lambda: phrase_call(s, -1), n=3)
-    _, med_diag = timed(lambda: s.diagnostics(20))
-    _, med_z = timed(lambda: s.get_assignments(0))
+    first_f, med_f, _ = timed(lambda: phrase_call(s, 20, (np_, nw)), n=6)
+    _, med_all, _ = timed(lambda: phrase_call(s, -1), n=3)
+    _, med_diag, _ = timed(lambda: s.diagnostics(20), n=6)
+    _, med_z, _ = timed(lambda: s.get_assignments(0), n=6)
     cap = 64
     while cap < 2 * st.occurrences:
         cap *= 2

@@ -18,15 +18,8 @@ The split between the two passes comes from a child run under `rocprofv3 --kerne
 started only after the wall times were taken without an error, runs under its own time limit in a process group of its own, and when it
 fails or runs into the limit the group is killed and nothing more is started on the GPU."""
 import argparse
-import csv
-import glob
 import os
-import re
-import shutil
-import signal
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -34,7 +27,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from xview_timing import SEED, ChildFailed, trained_sampler  # noqa: E402
+from _timing import SEED, ChildFailed, profiled, trained_sampler  # noqa: E402
 
 from mvtopicmodel_amd import surgery  # noqa: E402
 from mvtopicmodel_amd.native import Hyper  # noqa: E402
@@ -104,36 +97,6 @@ def host_route(s, hy, tm):
     return [(b - a) * 1e3 for a, b in zip(t, t[1:])]
 
 
-def profiled(argv, limit=400):
-    """a child run of the two calls under rocprofv3 in a process group of its own -> {kernel: (calls, total ms)}; None without rocprofv3"""
-    if shutil.which("rocprofv3") is None:
-        return None
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "rt", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__)] + argv + ["--child"]
-        child = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
-        try:
-            rc = child.wait(timeout=limit)
-        except subprocess.TimeoutExpired:
-            rc = None
-        if rc != 0:
-            try:
-                os.killpg(child.pid, signal.SIGKILL)
-            except ProcessLookupError:
-                pass
-            child.wait()
-            raise ChildFailed("the trace run " + ("did not end within %d s" % limit if rc is None else "ended with status %d" % rc))
-        files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-        if not files:
-            return None
-        out = {}
-        for row in csv.DictReader(open(files[0])):
-            k = re.search(KERNELS, row["Name"])
-            if k:
-                calls, ms = out.get(k.group(0), (0, 0.0))
-                out[k.group(0)] = (calls + int(row["Calls"]), ms + float(row["TotalDurationNs"]) / 1e6)
-        return out or None
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="C4")
@@ -144,13 +107,13 @@ def main():
     ap.add_argument("--child", action="store_true", help="(internal) each of the two calls once, for the profiler")
     args = ap.parse_args()
     if args.child:
-        s, _, _, _ = trained_sampler(args.workload, min(args.docs or CHILD_DOCS, CHILD_DOCS), 2)
+        s = trained_sampler(args.workload, min(args.docs or CHILD_DOCS, CHILD_DOCS), 2)[0]
         w = weights(s)
         s.remap_topics(merge_pairs_map(s, w))
         s.remap_topics(surgery.order_map(weights(s), s.get_alpha()[1]))
         s.close()
         return
-    s, hy, corpus, D = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, hy, corpus, D, _ = trained_sampler(args.workload, args.docs, args.sweeps)
     print(f"{args.sweeps} sweeps done", file=sys.stderr, flush=True)
     K, V, M = s.K, s.V, s.M
     N = [int(corpus.doc_off[m][-1]) for m in range(M)]
@@ -204,7 +167,7 @@ def main():
         ks = None
         try:
             print("wall times taken; the kernel trace", file=sys.stderr, flush=True)
-            ks = profiled(["--workload", args.workload] + (["--docs", str(args.docs)] if args.docs else []))
+            ks = profiled(__file__, ["--workload", args.workload] + (["--docs", str(args.docs)] if args.docs else []), KERNELS, limit=400)
         except ChildFailed as e:
             lines += [f"- {e}; no further run was started", ""]
         if ks:

@@ -26,7 +26,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from xview_timing import SEED, trained_sampler  # noqa: E402
+from _timing import SEED, trained_sampler  # noqa: E402
 
 from mvtopicmodel_amd import surgery  # noqa: E402
 from mvtopicmodel_amd.native import Hyper  # noqa: E402
@@ -73,7 +73,7 @@ def main():
     ap.add_argument("--child", action="store_true", help="one split after 2 sweeps and nothing else: the run to put under a kernel trace")
     args = ap.parse_args()
     if args.child:
-        s, _, _, _ = trained_sampler(args.workload, args.docs, 2)
+        s = trained_sampler(args.workload, args.docs, 2)[0]
         w = weights(s)
         light = np.argsort(w, kind="stable")[:2]
         tm = surgery.identity_map(s.K)
@@ -83,7 +83,7 @@ def main():
         print(f"split {int(st.split.sum())} tokens, kernel_ms {st.kernel_ms:.3f}")
         s.close()
         return
-    s, hy, corpus, D = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, hy, corpus, D, _ = trained_sampler(args.workload, args.docs, args.sweeps)
     print(f"{args.sweeps} sweeps done", file=sys.stderr, flush=True)
     K, V, M = s.K, s.V, s.M
     N = [int(corpus.doc_off[m][-1]) for m in range(M)]

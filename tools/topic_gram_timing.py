@@ -12,15 +12,8 @@ The kernels' own times come from a child run under `rocprofv3 --kernel-trace --s
 the ENTITIES call once; it is started only after the wall times were taken without an error, runs under its own time limit in a process
 group of its own, and when it fails or runs into the limit the group is killed and nothing more is started on the GPU."""
 import argparse
-import csv
-import glob
 import os
-import re
-import shutil
-import signal
-import subprocess
 import sys
-import tempfile
 import time
 
 os.environ.setdefault("OMP_NUM_THREADS", "16")                               # the host baselines: at most 16 threads
@@ -32,7 +25,7 @@ import numpy as np  # noqa: E402
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from xview_timing import SEED, ChildFailed, timed, trained_sampler  # noqa: E402
+from _timing import SEED, ChildFailed, profiled, resource_lines, timed, trained_sampler  # noqa: E402
 
 PARENT_SCORE_RATE = 21.0                                                     # T fp64 FMA/s of xview_score_kernel in profiles/xview_entities.md
 KERNELS = r"gram_\w+?_kernel|xview_phi_kernel|doc_topic_prop_kernel"
@@ -81,61 +74,6 @@ def host_words(s, hy, m, transform):
     return (t1 - t0) * 1e3, (t2 - t1) * 1e3, g
 
 
-def profiled(argv, limit=400):
-    """a child run of the ENTITIES call under rocprofv3 in a process group of its own -> {kernel: (calls, total ms)}; None without rocprofv3"""
-    if shutil.which("rocprofv3") is None:
-        return None
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "tg", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__)] + argv + ["--child"]
-        child = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
-        try:
-            rc = child.wait(timeout=limit)
-        except subprocess.TimeoutExpired:
-            rc = None
-        if rc != 0:
-            try:
-                os.killpg(child.pid, signal.SIGKILL)
-            except ProcessLookupError:
-                pass
-            child.wait()
-            raise ChildFailed("the trace run " + ("did not end within %d s" % limit if rc is None else "ended with status %d" % rc))
-        files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-        if not files:
-            return None
-        out = {}
-        for row in csv.DictReader(open(files[0])):
-            k = re.search(KERNELS, row["Name"])
-            if k:
-                calls, ms = out.get(k.group(0), (0, 0.0))
-                out[k.group(0)] = (calls + int(row["Calls"]), ms + float(row["TotalDurationNs"]) / 1e6)
-        return out or None
-
-
-def resource_lines():
-    """registers, LDS, scratch and occupancy of the unit's kernels, from a device-only compile of its source"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "mvtopicmodel_amd", "csrc", "mvhdp_gram.hip")
-    if not os.path.exists(hipcc):
-        return []
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-structurizecfg-skip-uniform-regions=1",
-                        "-S", "--cuda-device-only", "-o", os.devnull, src, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    lines, name, got = [], None, {}
-    for l in r.stderr.split("\n"):
-        f = re.search(r"Function Name: (\S+)", l)
-        if f:
-            k = re.search(r"gram_\w+?_kernel", f.group(1))
-            name = k.group(0) if k else None
-            got = {}
-        elif name:
-            v = re.search(r"(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", l)
-            if v:
-                got[v.group(1)] = v.group(2)
-                if v.group(1).startswith("LDS"):
-                    lines.append(f"{name}: " + ", ".join(f"{a} {b}" for a, b in got.items()))
-                    name = None
-    return lines
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="C4")
@@ -146,11 +84,11 @@ def main():
     ap.add_argument("--child", action="store_true", help="(internal) one ENTITIES call without counts, for the profiler")
     args = ap.parse_args()
     if args.child:
-        s, _, _, _ = trained_sampler(args.workload, CHILD_DOCS, 2)
+        s = trained_sampler(args.workload, CHILD_DOCS, 2)[0]
         s.topic_gram("entities", view_weights=np.ones(s.M))
         s.close()
         return
-    s, hy, corpus, D = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, hy, corpus, D, _ = trained_sampler(args.workload, args.docs, args.sweeps)
     print(f"{args.sweeps} sweeps done", file=sys.stderr, flush=True)
     K, V, M = s.K, s.V, s.M
     w = np.ones(M)
@@ -186,13 +124,13 @@ def main():
             report(f"WORDS, view {m} ({V[m]} types), {transform}", lambda: s.topic_gram("words", m=m, transform=transform), host_words(s, hy, m, transform), V[m])
     s.close()
     lines += ["", "Slower than its host route: " + (", ".join(slower) if slower else "none"), ""]
-    lines += ["## the kernels as compiled", ""] + [f"- {l}" for l in resource_lines()] + [""]
+    lines += ["## the kernels as compiled", ""] + [f"- {l}" for l in resource_lines("mvhdp_gram.hip", r"gram_\w+?_kernel")] + [""]
     if not args.no_profile:
         lines += [f"## the kernels of one ENTITIES call (identity, no counts) on {CHILD_DOCS} entities (a child run of its own, a model trained for 2 sweeps)", ""]
         ks = None
         try:
             print("wall times taken; the kernel trace", file=sys.stderr, flush=True)
-            ks = profiled(["--workload", args.workload])
+            ks = profiled(__file__, ["--workload", args.workload], KERNELS, limit=400)
         except ChildFailed as e:
             lines += [f"- {e}; no further run was started", ""]
         if ks:

@@ -14,15 +14,8 @@ is linear in it.  The kernels' own times come from a child run under `rocprofv3 
 same shape running case (a).  A child that fails or runs into its time limit ends the profiling: its process group is killed and
 nothing more is started on the GPU."""
 import argparse
-import csv
-import glob
 import os
-import re
-import shutil
-import signal
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
@@ -30,10 +23,12 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from xview_timing import CHILD_DOCS, N_TOP, SEED, ChildFailed, timed, trained_sampler, weights_without  # noqa: E402
+from _timing import SEED, ChildFailed, profiled, resource_lines, timed, trained_sampler, weights_without  # noqa: E402
 
 PARENT_SCORE_RATE = 20.9                                                     # T fp64 FMA/s of xview_score_kernel in profiles/xview.md
 KERNELS = r"xe_\w+|xview_score_kernel|doc_topic_prop_kernel"
+COMPILED = r"xe_\w+?_kernel|xview_score_kernel|xview_phi_kernel"
+CHILD_DOCS, N_TOP = 50000, 20                                               # tools/xview_timing.py's
 
 
 def three_word_queries(V, nq, seed=1):
@@ -72,59 +67,8 @@ def host_path(s, hy, m, w, n_ent, items, pairs=None):
     return (t1 - t0) * 1e3, (t2 - t1) * 1e3
 
 
-def profiled(argv, limit=300):
-    """a child run of case (a) under rocprofv3 in a process group of its own -> {kernel: (calls, total ms)}; None without rocprofv3"""
-    if shutil.which("rocprofv3") is None:
-        return None
-    with tempfile.TemporaryDirectory() as d:
-        cmd = ["rocprofv3", "--kernel-trace", "--stats", "-d", d, "-o", "xe", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__)] + argv + ["--child"]
-        child = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
-        try:
-            rc = child.wait(timeout=limit)
-        except subprocess.TimeoutExpired:
-            rc = None
-        if rc != 0:
-            try:
-                os.killpg(child.pid, signal.SIGKILL)
-            except ProcessLookupError:
-                pass
-            child.wait()
-            raise ChildFailed("the trace run " + ("did not end within %d s" % limit if rc is None else "ended with status %d" % rc))
-        files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-        if not files:
-            return None
-        out = {}
-        for row in csv.DictReader(open(files[0])):
-            k = re.search(KERNELS, row["Name"])
-            if k:
-                calls, ms = out.get(k.group(0), (0, 0.0))
-                out[k.group(0)] = (calls + int(row["Calls"]), ms + float(row["TotalDurationNs"]) / 1e6)
-        return out or None
-
-
-def resource_lines():
-    """registers, LDS, scratch and occupancy of the unit's kernels, from a device-only compile of its source"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "mvtopicmodel_amd", "csrc", "mvhdp_xview_entities.hip")
-    if not os.path.exists(hipcc):
-        return []
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-structurizecfg-skip-uniform-regions=1",
-                        "-S", "--cuda-device-only", "-o", os.devnull, src, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    lines, name, got = [], None, {}
-    for l in r.stderr.split("\n"):
-        f = re.search(r"Function Name: (\S+)", l)
-        if f:
-            k = re.search(r"xe_\w+?_kernel|xview_score_kernel|xview_phi_kernel", f.group(1))
-            name = k.group(0) + ("<LDS>" if "ILb1E" in f.group(1) else "<memory>" if "ILb0E" in f.group(1) else "") if k else None
-            got = {}
-        elif name:
-            v = re.search(r"(TotalSGPRs|VGPRs|AGPRs|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (\d+)", l)
-            if v:
-                got[v.group(1)] = v.group(2)
-                if v.group(1).startswith("LDS"):
-                    lines.append(f"{name}: " + ", ".join(f"{a} {b}" for a, b in got.items()))
-                    name = None
-    return lines
+def pick_variant(name, mangled):
+    return name + ("<LDS>" if "ILb1E" in mangled else "<memory>" if "ILb0E" in mangled else "")
 
 
 def main():
@@ -139,12 +83,12 @@ def main():
     ap.add_argument("--child", action="store_true", help="(internal) one predict_entities call of case (a), for the profiler")
     args = ap.parse_args()
     if args.child:
-        s, _, _, _ = trained_sampler(args.workload, CHILD_DOCS, 2)
+        s = trained_sampler(args.workload, CHILD_DOCS, 2)[0]
         m1 = 1 if s.M > 1 else 0
         s.predict_entities(m1, weights_without(s.M, m1), N_TOP, items=np.arange(s.V[m1], dtype=np.int32))
         s.close()
         return
-    s, hy, corpus, D = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, hy, corpus, D, _ = trained_sampler(args.workload, args.docs, args.sweeps)
     print(f"{args.sweeps} sweeps done", file=sys.stderr, flush=True)
     K, V, M = s.K, s.V, s.M
     m1 = 1 if M > 1 else 0
@@ -180,13 +124,13 @@ def main():
                lambda: s.rank_entities(m1, w1, pq, pe, items=all_types), host_path(s, hy, m1, w1, nb, all_types, (pq, pe)), nqp * D * K)
     lines += [f"- those pairs: recall@{N_TOP} {r.recall_at(N_TOP):.4f}, MRR {r.mrr():.6f} (the entity itself is excluded for its item and still ranked)", ""]
     s.close()
-    lines += ["## the kernels as compiled", ""] + [f"- {l}" for l in resource_lines()] + [""]
+    lines += ["## the kernels as compiled", ""] + [f"- {l}" for l in resource_lines("mvhdp_xview_entities.hip", COMPILED, pick_variant)] + [""]
     if not args.no_profile:
         lines += [f"## the kernels of one call of case (a) on {CHILD_DOCS} entities (a child run of its own, a model trained for 2 sweeps)", ""]
         ks = None
         try:
             print("wall times taken; the kernel trace", file=sys.stderr, flush=True)
-            ks = profiled(["--workload", args.workload])
+            ks = profiled(__file__, ["--workload", args.workload], KERNELS)
         except ChildFailed as e:
             lines += [f"- {e}; no further run was started", ""]
         if ks:

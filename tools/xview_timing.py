@@ -13,65 +13,22 @@ times come from a child run under `rocprofv3 --kernel-trace --stats`, the counte
 `rocprofv3 --pmc` (never together with a trace); both on a 50 000-entity model of the same shape, predicting view 1.  A child that
 fails or runs into its time limit ends the profiling: its process group is killed and nothing more is started on the GPU."""
 import argparse
-import csv
-import glob
 import os
-import re
-import shutil
-import signal
-import statistics
-import subprocess
 import sys
-import tempfile
 import time
 
 import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-SEED = 20260101                                                              # bench.py's
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from _timing import SEED, ChildFailed, profiled, resource_usage, timed, trained_sampler, weights_without  # noqa: E402
+
 N_TOP = 20
 MI355X_CUS, MI355X_MAX_GHZ = 256, 2.4
 COUNTERS = ["SQ_WAVE_CYCLES", "SQ_BUSY_CYCLES", "SQ_ACTIVE_INST_VALU", "SQ_ACTIVE_INST_LDS", "SQ_LDS_BANK_CONFLICT", "SQ_WAIT_INST_ANY", "SQ_INSTS_VALU", "SQ_INSTS_LDS"]
 CHILD_DOCS = 50000
-
-
-def trained_sampler(workload, docs, sweeps):
-    from mvtopicmodel_amd import NativeSampler, synth
-    from mvtopicmodel_amd.java_init import init_assignments
-    from mvtopicmodel_amd.native import Hyper
-    cfg = dict(synth.CONFIGS[workload])
-    D = docs or cfg["D"]
-    K, V = cfg["K"], cfg["V"]
-    corpus = synth.make_config(workload, D=D, doc_lo=0, doc_hi=D)
-    inactive, K_init = synth.config_inactive(workload)
-    z0 = init_assignments(K_init, corpus.doc_off, seed=1)
-    s = NativeSampler(K, V)
-    for m in range(len(V)):
-        s.set_corpus(m, corpus.doc_off[m], corpus.tokens[m])
-        s.set_assignments(m, z0[m])
-    hy = Hyper.defaults(K, V, inactive=inactive)
-    s.set_hyper(hy)
-    s.build_counts()
-    for i in range(sweeps):
-        s.sweep(i, SEED)
-    return s, hy, corpus, D
-
-
-def weights_without(M, m):
-    w = np.ones(M)
-    if M > 1:
-        w[m] = 0.0
-    return w
-
-
-def timed(f, n=3):
-    out, r = [], None
-    for _ in range(n):
-        t0 = time.perf_counter()
-        r = f()
-        out.append((time.perf_counter() - t0) * 1e3)
-    return out[0], statistics.median(out[1:]), r
+KERNELS = r"xview_\w+|doc_topic_prop_kernel"
 
 
 def held_pairs(corpus, m, D, V):
@@ -110,66 +67,6 @@ def host_path(s, hy, corpus, m, w, n_ent, pairs=None):
     return (t1 - t0) * 1e3, (t2 - t1) * 1e3
 
 
-class ChildFailed(RuntimeError):
-    """a profiled child run ended with a non-zero status or ran into its time limit: nothing more is started on the GPU in this call"""
-
-
-def profiled(mode, argv, limit=300):
-    """A child run under rocprofv3 in a process group of its own: 'trace' -> {kernel: (calls, total ms)}, 'pmc' -> {counter: sum over the
-    xview_score_kernel dispatches}; None without rocprofv3 or without such rows."""
-    if shutil.which("rocprofv3") is None:
-        return None
-    with tempfile.TemporaryDirectory() as d:
-        what = ["--kernel-trace", "--stats"] if mode == "trace" else ["--pmc"] + COUNTERS
-        cmd = ["rocprofv3"] + what + ["-d", d, "-o", "xview", "--output-format", "csv", "--", sys.executable, os.path.abspath(__file__)] + argv + ["--child"]
-        child = subprocess.Popen(cmd, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, start_new_session=True)
-        try:
-            rc = child.wait(timeout=limit)
-        except subprocess.TimeoutExpired:
-            rc = None
-        if rc != 0:
-            try:
-                os.killpg(child.pid, signal.SIGKILL)
-            except ProcessLookupError:
-                pass
-            child.wait()
-            raise ChildFailed(f"the {mode} run " + ("did not end within %d s" % limit if rc is None else "ended with status %d" % rc))
-        out = {}
-        if mode == "trace":
-            files = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)
-            if not files:
-                return None
-            for row in csv.DictReader(open(files[0])):
-                k = re.search(r"xview_\w+|doc_topic_prop_kernel", row["Name"])
-                if k:
-                    out[k.group(0)] = (int(row["Calls"]), float(row["TotalDurationNs"]) / 1e6)
-        else:
-            files = glob.glob(os.path.join(d, "**", "*counter_collection.csv"), recursive=True)
-            if not files:
-                return None
-            for row in csv.DictReader(open(files[0])):
-                if "xview_score_kernel" in row.get("Kernel_Name", ""):
-                    out[row["Counter_Name"]] = out.get(row["Counter_Name"], 0.0) + float(row["Counter_Value"])
-        return out or None
-
-
-def resource_lines():
-    """the score kernel's register, LDS, scratch and occupancy lines, from a device-only compile of its source"""
-    hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    src = os.path.join(ROOT, "mvtopicmodel_amd", "csrc", "mvhdp_xview.hip")
-    if not os.path.exists(hipcc):
-        return []
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "-mllvm", "-structurizecfg-skip-uniform-regions=1",
-                        "-S", "--cuda-device-only", "-o", os.devnull, src, "-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True)
-    lines, on = [], False
-    for l in r.stderr.split("\n"):
-        if "Function Name" in l:
-            on = "xview_score_kernel" in l
-        elif on and re.search(r"VGPRs:|AGPRs|ScratchSize|Occupancy|LDS Size|SGPRs:", l):
-            lines.append(l.split("remark:")[1].split("[-R")[0].strip())
-    return lines
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--workload", default="C4")
@@ -181,11 +78,11 @@ def main():
     ap.add_argument("--child", action="store_true", help="(internal) one predict_items call of view 1, for the profiler")
     args = ap.parse_args()
     if args.child:
-        s, _, _, D = trained_sampler(args.workload, CHILD_DOCS, 2)
+        s = trained_sampler(args.workload, CHILD_DOCS, 2)[0]
         s.predict_items(1 if s.M > 1 else 0, weights_without(s.M, 1 if s.M > 1 else 0), N_TOP)
         s.close()
         return
-    s, hy, corpus, D = trained_sampler(args.workload, args.docs, args.sweeps)
+    s, hy, corpus, D, _ = trained_sampler(args.workload, args.docs, args.sweeps)
     print(f"{args.sweeps} sweeps done", file=sys.stderr, flush=True)
     K, V, M = s.K, s.V, s.M
     m1 = 1 if M > 1 else 0
@@ -220,15 +117,15 @@ def main():
     lines += [f"- those pairs: mean log score {r.mean_log_score():.4f}, recall@{N_TOP} {r.recall_at(N_TOP):.4f}, MRR {r.mrr():.4f} "
               f"(a uniform guess over {V[m1]} types: log score {-np.log(V[m1]):.4f})", ""]
     s.close()
-    lines += ["## the score kernel as compiled", ""] + [f"- {l}" for l in resource_lines()] + [""]
+    lines += ["## the score kernel as compiled", ""] + [f"- {a}: {b}" for _, _, got in resource_usage("mvhdp_xview.hip", "xview_score_kernel") for a, b in got.items()] + [""]
     if not args.no_profile:
         lines += [f"## the kernels of one predict_items(m = {m1}, n = {N_TOP}) call on {CHILD_DOCS} entities (child runs of their own, a model trained for 2 sweeps)", ""]
         ks = pm = None
         try:
             print("wall times taken; the kernel trace", file=sys.stderr, flush=True)
-            ks = profiled("trace", ["--workload", args.workload])
+            ks = profiled(__file__, ["--workload", args.workload], KERNELS)
             print("the counter pass", file=sys.stderr, flush=True)
-            pm = profiled("pmc", ["--workload", args.workload])
+            pm = profiled(__file__, ["--workload", args.workload], "xview_score_kernel", mode="pmc", counters=COUNTERS)
         except ChildFailed as e:
             lines += [f"- {e}; no further run was started", ""]
         score_ms = None
