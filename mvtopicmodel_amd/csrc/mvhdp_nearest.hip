@@ -8,15 +8,15 @@
 //                              block of scores [queries of the block][candidates of the stripe] as an order-preserving 32-bit key, 0 for a
 //                              cell that is not screened (a row that is not tame, padding, the query itself)
 //   near_select_kernel         one wave per query: the stripe's keys in LDS, the n-th largest key over them and the n largest of the
-//                              stripes before (a bitwise descent, as xview_select_kernel does on 64-bit keys, on the few keys that reach
+//                              stripes before (a bitwise descent, as wave_first_n does on 64-bit keys, on the few keys that reach
 //                              the n-th largest of the lanes' maxima where that bound exists), the n largest kept for the next stripe, and the cells that pass appended with ONE atomic per query and stripe
 //   near_group_kernel          the block's candidates placed query by query (integer atomics: the order inside a query is not kept, and
 //                              nothing depends on it)
 //   near_exact_kernel          every candidate recomputed by the fp64 chain
-//   near_pick_kernel           one wave per query: the first n by (sim descending, id ascending), a bitwise descent on the 96-bit
-//                              composite (key of the fp64 bits, ~id), then each placed by the number that precede it
+//   near_pick_kernel           one wave per query: the first n by (sim descending, id ascending): wave_first_n (mvhdp_select.h) on the
+//                              composite (key of the fp64 bits, ~id)
 //   topk_partial_kernel        a thread per (slice of entities, topic), lanes over topics: the n largest proportions of the slice
-//   topk_merge_kernel          one wave per topic: the first n of all slices, by the same descent
+//   topk_merge_kernel          one wave per topic: the first n of all slices, by wave_first_n as well
 // No floating-point atomics: every fp64 value is a chain in a fixed order, integers and exact fp64 values decide every comparison.
 #include "mvhdp_screen.h"
 #include "mvhdp_select.h"
@@ -215,46 +215,6 @@ __global__ __launch_bounds__(256) void near_exact_kernel(const double* __restric
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// One wave: of m entries, entry i the composite (hi, lo) = at(i) with hi == 0 for an entry that does not count, the n_eff = min(n_cap,
-// entries that count) largest composites (hi first, then lo; the composites that count are distinct), in descending order:
-// emit(place, hi, lo).  sel_hi / sel_lo: [n_cap] scratch of this wave in memory.  Returns n_eff.  The block is this one wave.
-template <class At, class Emit>
-__device__ __forceinline__ int wave_first_n(At&& at, int64_t m, int n_cap, int lane, u64* sel_hi, uint32_t* sel_lo, Emit&& emit)
-{
-    const u64 below = lanes_below(lane);
-    auto count = [&](auto&& test) -> int64_t {
-        int c = 0;
-        for (int64_t i = lane; i < m; i += WV) { u64 h; uint32_t l; at(i, h, l); c += (h != 0 && test(h, l)) ? 1 : 0; }
-        return (int64_t)wave_sum(c);
-    };
-    const int64_t nv = count([](u64, uint32_t) { return true; });
-    const int n_eff = (int)(nv < (int64_t)n_cap ? nv : (int64_t)n_cap);
-    if (n_eff == 0) return 0;
-    u64 th = 0; uint32_t tl = 0;                               // the n_eff-th largest composite; (0, 0) takes every entry that counts
-    if (nv > n_eff) {
-        th = key_descent(0ull, 63, [&](u64 trial) { return count([&](u64 h, uint32_t) { return h >= trial; }) >= n_eff; });
-        tl = key_descent(0u, 31, [&](uint32_t trial) { return count([&](u64 h, uint32_t l) { return h > th || (h == th && l >= trial); }) >= n_eff; });
-    }
-    int got = 0;
-    for (int64_t base = 0; base < m; base += WV) {
-        const int64_t i = base + lane;
-        u64 h = 0; uint32_t l = 0;
-        if (i < m) at(i, h, l);
-        const bool sel = h != 0 && (h > th || (h == th && l >= tl));
-        const u64 mk = ballot(sel);
-        if (sel) { const int pos = got + __popcll(mk & below); sel_hi[pos] = h; sel_lo[pos] = l; }
-        got += __popcll(mk);
-    }
-    __syncthreads();                                           // the wave reads what its other lanes wrote
-    for (int i = lane; i < n_eff; i += WV) {
-        const u64 h = sel_hi[i]; const uint32_t l = sel_lo[i];
-        int place = 0;
-        for (int j = 0; j < n_eff; j++) { const u64 hj = sel_hi[j]; const uint32_t lj = sel_lo[j]; place += (hj > h || (hj == h && lj > l)) ? 1 : 0; }
-        emit(place, h, l);
-    }
-    return n_eff;
-}
-
 // One wave per query: the first n_cap of its candidates by (sim descending, local id ascending); a NaN sim does not count.
 __global__ __launch_bounds__(64) void near_pick_kernel(const u64* __restrict__ gkey, const double* __restrict__ gsim, const int64_t* __restrict__ qoff, int nrows, int n_cap,
                                                        u64* __restrict__ sel_hi, uint32_t* __restrict__ sel_lo, int32_t* __restrict__ out_id, double* __restrict__ out_sim,

@@ -1,5 +1,5 @@
-// mvhdp_xview.h — the two kernels that mvhdp_xview.hip (types per entity) and mvhdp_xview_entities.hip (entities per item query) share: the
-// phi table and the tiled fp64 score kernel.  Both operands of the score kernel are K-contiguous row matrices, so either side of the
+// mvhdp_xview.h — what mvhdp_xview.hip (types per entity) and mvhdp_xview_entities.hip (entities per item query) share: the phi table,
+// the tiled fp64 score kernel and the marker of an excluded cell.  Both operands of the score kernel are K-contiguous row matrices, so either side of the
 // product can take either slot: S[r][col0 + w] = the chain over k of theta[row r][k] * phi[w][k].
 //   xview_phi_kernel      phi[w][k] = (n_wk + beta) / (n_k + betaSum), 0 for an inactive topic: one thread per cell of a stripe of types,
 //                         fp64 [types][K], K-contiguous like the count rows.
@@ -14,9 +14,13 @@
 // The kernels live in each including unit's unnamed namespace.
 #pragma once
 #include "mvhdp_ctx.h"
+#include "mvhdp_select.h"
 
 namespace {
 
+// the bits written over an excluded cell of the block of scores: f64_bits_key gives 0, the key of an entry that does not count.  (The
+// scores are read as their bits and ordered by f64_bits_key; the chain never yields -0.0: it starts at +0.0.)
+constexpr u64 XV_EXCLUDED = ~0ull;
 constexpr int XV_TE = 4, XV_TW = 8;                            // a thread's tile: entities x types
 constexpr int XV_BE = 16 * XV_TE, XV_BW = 16 * XV_TW;          // a block's tile: 64 x 128
 constexpr int XV_KS = 16;                                      // topics per slab

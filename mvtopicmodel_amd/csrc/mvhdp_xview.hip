@@ -8,7 +8,9 @@
 //                         by a bitwise descent on an order-preserving 64-bit key (the row's keys in LDS while they fit 64 KiB, every
 //                         lane counting its own share of a pass), compacts the row's first n entries (ascending type id) and a
 //                         second kernel places each by the number that precede it; one wave per pair counts the entries that
-//                         precede the queried one.  Integers and exact fp64 values only.
+//                         precede the queried one (wave_rank_count of mvhdp_select.h).  Integers and exact fp64 values only.
+//                         (The select / order pair is not wave_first_n of mvhdp_select.h, which the other top-n picks call: as one
+//                         pick kernel on it the LDS form measured 18 % slower, profiles/select_refactor.md.)
 // Work is cut on the host: theta in ranges of entities, scores in blocks of rows, phi in stripes of types, each within XVIEW_BLOCK_BYTES.
 // Everything runs on the handle's stream; the shared argument checks, the prologue and wave_blocks are mvhdp_side.h's.
 #include "mvhdp_side.h"
@@ -19,8 +21,6 @@ namespace {
 
 constexpr size_t XVIEW_BLOCK_BYTES = (size_t)256 << 20;        // the block of scores, the phi stripe and the theta range: each at most this
 constexpr size_t XV_SELECT_LDS_BYTES = 64 << 10;                  // a row of keys up to this size is selected from LDS (V_m <= 8192)
-constexpr u64 XV_EXCLUDED = ~0ull;                             // the bits written over an excluded type's score: f64_bits_key gives 0
-// (the scores are read as their bits and ordered by f64_bits_key; the chain never yields -0.0: it starts at +0.0)
 
 // one thread per pair: the score as the block holds it, before any entry is marked
 __global__ __launch_bounds__(256) void xview_pair_score_kernel(const double* __restrict__ S, int64_t V, int64_t n_pairs, const int32_t* __restrict__ pair_row,
@@ -44,8 +44,6 @@ __global__ __launch_bounds__(256) void xview_mark_kernel(u64* __restrict__ S, in
         }
     }
 }
-
-__device__ __forceinline__ int64_t wave_count(bool p) { return (int64_t)__builtin_popcountll(ballot(p)); }
 
 // one wave per row: counts[r] = min(n, entries that are not excluded); the first counts[r] entries of the order (key descending, equal
 // keys by ascending type) go to sel_key / sel_id [r][n_cap] in ascending type id.  The descent reads the row once per bit that the keys
@@ -148,16 +146,8 @@ __global__ __launch_bounds__(256) void xview_rank_kernel(const u64* __restrict__
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
     for (int64_t p = wave; p < n_pairs; p += nwaves) {
-        const u64* __restrict__ row = S + (int64_t)pair_row[p] * V;
-        const int64_t q = pair_item[p];
-        const u64 kq = f64_bits_key(pair_score[p]);
-        int64_t c = 0;
-        for (int64_t base = 0; base < V; base += 64) {
-            const int64_t w = base + lane;
-            const u64 key = w < V ? f64_bits_key(row[w]) : 0;
-            c += wave_count(key != 0 && w != q && (key > kq || (key == kq && w < q)));
-        }
-        if (lane == 0) rank[p] = (int32_t)c;
+        const int c = wave_rank_count(S + (int64_t)pair_row[p] * V, (int)V, 0u, f64_bits_key(pair_score[p]), (uint32_t)pair_item[p], lane);
+        if (lane == 0) rank[p] = c;
     }
 }
 

@@ -10,14 +10,13 @@
 //                         type-to-queries list the host builds per block of queries) get the marker whose key is 0 at S[query][entity].
 //                         An integer exchange, so that a cell marked twice is counted once.
 //   xe_pick_kernel        one wave per query: the first n of (the block's cells that are not marked, the n carried from the blocks
-//                         before) by (score key descending, entity ascending): a bitwise descent on the 64-bit key, on the 32-bit ~id only
-//                         where equal keys straddle the n-th place; the kept entries are compacted and each is placed by the number in
-//                         front of it.  The block's keys are staged in LDS while a row fits 64 KiB (8192 entities); beyond that the
+//                         before) by (score key descending, entity ascending): wave_first_n (mvhdp_select.h) on the composite (key,
+//                         ~candidate).  The block's keys are staged in LDS while a row fits 64 KiB (8192 entities); beyond that the
 //                         passes read the block of scores where it lies.  Once n are carried, only a cell in front of the last carried
 //                         entry can enter: the row is read once, those cells are compacted, and while they and the carried ones are
 //                         at most 256 the wave holds them in registers (four a lane) and places each by counting, without a descent.
 //   xe_rank_kernel        one wave per pair: the cells of its query's row that are not marked, the queried entity apart, and precede
-//                         (score, entity); the counts add over the blocks of entities.
+//                         (score, entity) (wave_rank_count of mvhdp_select.h); the counts add over the blocks of entities.
 // Work is cut on the host: queries in blocks, entities in blocks, the block of scores within 256 MiB.  theta is formed per block of
 // entities (mvhdp_launch_doc_topic_prop) and never leaves the device.  No floating-point atomics; everything runs on the handle's stream.
 #include "mvhdp_side.h"
@@ -33,7 +32,6 @@ constexpr int XE_MAX_N = 1024;
 constexpr int XE_SHORT_T = 4, XE_SHORT = 64 * XE_SHORT_T;      // entries a wave places from registers: four a lane
 constexpr int64_t XE_MAX_QUERY_ITEMS = (int64_t)1 << 20;
 constexpr double XE_MAX_WEIGHT = 9007199254740992.0;           // 2^53
-constexpr u64 XE_EXCLUDED = ~0ull;                             // the bits written over an excluded cell: f64_bits_key gives 0
 
 // q_list: the query of row j (nullptr: q_first + j); q_off / q_items / q_w: the whole call's
 __global__ __launch_bounds__(256) void xe_psi_kernel(const int32_t* __restrict__ rows /*n_wk of view m*/, const int32_t* __restrict__ nk, const uint8_t* __restrict__ inactive,
@@ -81,7 +79,7 @@ __global__ __launch_bounds__(256) void xe_mark_kernel(u64* __restrict__ S, int64
             const int32_t w = tok[i];
             if (w < 0 || (int64_t)w >= V) continue;
             for (int64_t j = inv_off[w]; j < inv_off[w + 1]; j++)
-                c += atomicExch(&S[(int64_t)inv_q[j] * ld + e], XE_EXCLUDED) != XE_EXCLUDED ? 1 : 0;
+                c += atomicExch(&S[(int64_t)inv_q[j] * ld + e], XV_EXCLUDED) != XV_EXCLUDED ? 1 : 0;
         }
     }
     c = wave_sum(c);
@@ -167,56 +165,13 @@ __global__ __launch_bounds__(64) void xe_pick_kernel(const PickArgs p)
             for (int w = lane; w < p.ne; w += 64) s_keys[w] = f64_bits_key(row[w]);
             __syncthreads();
         }
-        auto at = [&](int i, u64& h, uint32_t& l) {
-            if (i < p.ne) { h = IN_LDS ? s_keys[i] : f64_bits_key(row[i]); l = ~(p.e0 + (uint32_t)i); }
-            else { h = ih[i - p.ne]; l = il[i - p.ne]; }
-        };
-        auto count = [&](auto&& test) -> int {
-            int c = 0;
-            for (int i = lane; i < m; i += 64) { u64 h; uint32_t l; at(i, h, l); c += (h != 0 && test(h, l)) ? 1 : 0; }
-            return wave_sum(c);
-        };
-        int nv = 0;
-        u64 all_and = ~0ull, all_or = 0;
-        for (int i = lane; i < m; i += 64) {
-            u64 h; uint32_t l; at(i, h, l);
-            if (h != 0) { nv++; all_and &= h; all_or |= h; }
-        }
-        for (int o = 32; o > 0; o >>= 1) { nv += __shfl_xor(nv, o, 64); all_and &= __shfl_xor(all_and, o, 64); all_or |= __shfl_xor(all_or, o, 64); }
-        nv = __builtin_amdgcn_readfirstlane(nv);
-        const int n_eff = nv < p.n_cap ? nv : p.n_cap;
+        const int n_eff = wave_first_n(
+            [&](int i, u64& h, uint32_t& l) {
+                if (i < p.ne) { h = IN_LDS ? s_keys[i] : f64_bits_key(row[i]); l = ~(p.e0 + (uint32_t)i); }
+                else { h = ih[i - p.ne]; l = il[i - p.ne]; }
+            },
+            m, p.n_cap, lane, sh, sl, [&](int place, u64 h, uint32_t l) { oh[place] = h; ol[place] = l; });
         if (lane == 0) p.out_cnt[r] = n_eff;
-        if (n_eff == 0) continue;
-        u64 th = 0; uint32_t tl = 0;                           // the n_eff-th composite; (0, 0) takes every entry that counts
-        if (nv > n_eff) {
-            // the largest key that at least n_eff keys reach; the bits every key shares are settled
-            const u64 diff = all_and ^ all_or;
-            th = all_and;
-            if (diff) {
-                const int hb = 63 - __builtin_clzll(diff);
-                th = key_descent(hb == 63 ? 0ull : all_and & ~((2ull << hb) - 1), hb, [&](u64 trial) { return count([&](u64 h, uint32_t) { return h >= trial; }) >= n_eff; });
-            }
-            // equal keys across the n-th place: the candidate id decides
-            if (count([&](u64 h, uint32_t) { return h >= th; }) > n_eff)
-                tl = key_descent(0u, 31, [&](uint32_t trial) { return count([&](u64 h, uint32_t l) { return h > th || (h == th && l >= trial); }) >= n_eff; });
-        }
-        int got = 0;
-        for (int base = 0; base < m; base += 64) {
-            const int i = base + lane;
-            u64 h = 0; uint32_t l = 0;
-            if (i < m) at(i, h, l);
-            const bool sel = h != 0 && (h > th || (h == th && l >= tl));
-            const u64 mk = ballot(sel);
-            if (sel) { const int pos = got + __popcll(mk & below); sh[pos] = h; sl[pos] = l; }   // pos < n_eff: exactly n_eff entries pass
-            got += __popcll(mk);
-        }
-        __syncthreads();                                       // the wave reads what its other lanes wrote
-        for (int i = lane; i < n_eff; i += 64) {
-            const u64 h = sh[i]; const uint32_t l = sl[i];
-            int place = 0;
-            for (int j = 0; j < n_eff; j++) { const u64 hj = sh[j]; const uint32_t lj = sl[j]; place += (hj > h || (hj == h && lj > l)) ? 1 : 0; }
-            oh[place] = h; ol[place] = l;
-        }
     }
 }
 
@@ -226,16 +181,7 @@ __global__ __launch_bounds__(256) void xe_rank_kernel(const u64* __restrict__ S,
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (int64_t)gridDim.x * 4;
     for (int64_t p = wave; p < n_pairs; p += nwaves) {
-        const u64* __restrict__ row = S + (int64_t)pair_row[p] * ld;
-        const uint32_t q = pair_ent[p];
-        const u64 kq = f64_bits_key(pair_score[p]);
-        int c = 0;
-        for (int w = lane; w < ne; w += 64) {
-            const u64 key = f64_bits_key(row[w]);
-            const uint32_t id = e0 + (uint32_t)w;
-            c += (key != 0 && id != q && (key > kq || (key == kq && id < q))) ? 1 : 0;
-        }
-        c = wave_sum(c);
+        const int c = wave_rank_count(S + (int64_t)pair_row[p] * ld, ne, e0, f64_bits_key(pair_score[p]), pair_ent[p], lane);
         if (lane == 0) rank[p] += (u64)c;                      // the pair is this wave's; the blocks follow one another on the stream
     }
 }
@@ -447,8 +393,7 @@ int entities_run(mvhdp_ctx* h, const mvhdp_entities_args* a, EntPredict* pr, Ent
                 const int c = c_cnt[(size_t)r];
                 pr->counts[(size_t)(qb0 + r)] = c;
                 for (int i = 0; i < c; i++) {
-                    const u64 key = c_hi[(size_t)r * n_cap + i];
-                    const u64 bits = (key >> 63) ? key ^ (1ull << 63) : ~key;
+                    const u64 bits = f64_key_bits(c_hi[(size_t)r * n_cap + i]);
                     double v; memcpy(&v, &bits, sizeof v);
                     pr->ids[(size_t)(qb0 + r) * pr->n + i] = a->c0 + (int64_t)(uint32_t)~c_lo[(size_t)r * n_cap + i];
                     pr->scores[(size_t)(qb0 + r) * pr->n + i] = v;

@@ -244,6 +244,29 @@ def test_a_theta_override_that_puts_two_types_one_ulp_apart(loaded):
     assert e.value.code == INV
 
 
+def test_rows_whose_scores_are_all_equal_are_listed_by_type_alone(loaded):
+    """a theta row of zeros: every score of the row is +0.0, every key equal, and the selection has no bit to descend on; what is
+    listed is the first types that are not excluded, in ascending id"""
+    x = loaded((100, 128, 65, 3))
+    c = x.c
+    V = c.V[c.m]
+    holder = next(d for d in range(c.D) if d != c.full and x.off[d + 1] - x.off[d] >= 2)
+    rows = [holder, c.full]                                                  # one holds a few types, one every type
+    theta = x.theta.copy()
+    theta[rows] = 0.0
+    S = xr.scores(theta, x.phi)
+    assert (S[rows].view(np.uint64) == 0).all() and (np.delete(S, rows, axis=0) > 0.0).all()
+    for n in (5, V + 5):
+        for excl in (True, False):
+            items, scores, counts = x.check_predict(n, excl, S=S, theta=theta, what=("equal", n, excl))
+            for d in rows:
+                held = set(x.tok[x.off[d]:x.off[d + 1]].tolist()) if excl else set()
+                first = [w for w in range(V) if w not in held][:n]
+                assert counts[d] == len(first) and items[d, :len(first)].tolist() == first and (items[d, len(first):] == -1).all()
+                assert (scores[d].view(np.uint64) == 0).all()
+            assert counts[c.full] == (0 if excl else min(n, V)) and 0 < counts[holder] <= min(n, V)
+
+
 def test_error_paths_leave_every_output_untouched(loaded):
     x = loaded((5, 3, 65, 3))
     s, c = x.s, x.c

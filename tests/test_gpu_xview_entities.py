@@ -191,6 +191,22 @@ def test_ties_across_the_nth_place_and_a_block_border():
         x.s.close()
 
 
+def test_a_host_psi_row_of_zeros_lists_the_first_candidates_by_id(loaded):
+    """every score of the row is +0.0 and every key equal: nothing for the selection to descend on.  129 candidates in blocks of 128: the
+    first block fills the carry (5 of 5), the second meets it full; blocks of 64 and of 3: the carry fills over two blocks"""
+    x = loaded(17)
+    c0, Cn = 7, 129                                                          # the smallest shape of ec.SHAPES that is cut into blocks
+    items, weights = ec.queries(x.c, 3, seed=17)
+    psi = Ref(x, items, weights, c0=c0, c1=c0 + Cn).psi.copy()
+    psi[1] = 0.0
+    h = Ref(x, psi=psi, c0=c0, c1=c0 + Cn)
+    assert (bits(h.S[1]) == 0).all() and (h.S[0] > 0.0).all()
+    for be in (128, 64, 3):
+        got = h.check_predict(5, True, what=("zeros", be), block_entities=be, block_queries=64)
+        assert got.counts[1] == 5 and got.ids[1].tolist() == list(range(c0, c0 + 5)) and (bits(got.scores[1]) == 0).all()
+        assert got.stats.blocks == -(-Cn // be)
+
+
 def test_a_host_psi_one_ulp_away_from_the_device_built_row(loaded):
     x = loaded(64)
     items, weights = ec.queries(x.c, 9)

@@ -2,6 +2,7 @@
 pinned), the pure host function mvhdp_nearest_probe against the same arithmetic in Python, and native.merge_nearest.  No GPU."""
 import ctypes as C
 import math
+import os
 
 import numpy as np
 import pytest
@@ -12,6 +13,13 @@ from tests import nearest_numpy as nn
 from tests import sim_numpy as sn
 
 INF = np.inf
+
+
+def test_the_selection_is_the_shared_one():
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mvtopicmodel_amd", "csrc")
+    unit, header = open(os.path.join(csrc, "mvhdp_nearest.hip")).read(), open(os.path.join(csrc, "mvhdp_select.h")).read()
+    assert header.count("int wave_first_n(") == 1 and "int wave_first_n(" not in unit      # one copy, in the shared header
+    assert unit.count("= wave_first_n(") == 2                                # near_pick_kernel and topk_merge_kernel
 
 
 def test_orthogonal_and_identical_rows():

@@ -55,6 +55,9 @@ def test_the_entries_exist_in_every_layer():
     assert [f for f in native.EntityRanking.__dataclass_fields__] == ["ids", "scores", "counts", "stats"]
     srcs = re.search(r"^SRCS\s*=(.*)$", read("mvtopicmodel_amd", "csrc", "Makefile"), flags=re.M).group(1)
     assert "mvhdp_xview_entities.hip" in srcs and "mvhdp_xview.h" in read("mvtopicmodel_amd", "csrc", "Makefile")
+    unit = read("mvtopicmodel_amd", "csrc", "mvhdp_xview_entities.hip")
+    assert "key_descent(" not in unit and "wave_first_n(" in unit and "XE_EXCLUDED" not in unit      # the selection: one copy, in the shared header
+    assert read("mvtopicmodel_amd", "csrc", "mvhdp_select.h").count("int wave_first_n(") == 1 and "int wave_first_n(" not in unit
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md", "CHANGELOG.md"):
         for n in NAMES:
             assert n in read(doc), (doc, n)

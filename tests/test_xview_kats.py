@@ -1,6 +1,7 @@
 """Known answers for the cross-view prediction contract of include/mvhdp.h, on the host: the restatement (tests/native/xview_ref.c) against
 exact rational arithmetic and hand-derived cases, its order and rank definitions, and how far a reordered or unfused chain moves the
 scores of the GPU test's own inputs -- so that the bit-for-bit GPU test cannot pass on another summation."""
+import os
 from fractions import Fraction
 
 import numpy as np
@@ -13,6 +14,15 @@ from tests import xview_ref as xr
 def fma_exact(a, b, c):
     """a correctly rounded fused multiply-add: the exact rational a * b + c, rounded once by float()"""
     return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def test_the_rank_count_and_the_marker_are_the_shared_ones():
+    """(the select / order pair of this unit stays its own: as one kernel on wave_first_n it was slower, profiles/select_refactor.md)"""
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "mvtopicmodel_amd", "csrc")
+    unit, header = open(os.path.join(csrc, "mvhdp_xview.hip")).read(), open(os.path.join(csrc, "mvhdp_select.h")).read()
+    assert header.count("int wave_first_n(") == 1 and "int wave_first_n(" not in unit                # one copy, in the shared header
+    assert header.count("int wave_rank_count(") == 1 and "= wave_rank_count(" in unit and "wave_count(" not in unit
+    assert "constexpr u64 XV_EXCLUDED" in open(os.path.join(csrc, "mvhdp_xview.h")).read() and "constexpr u64 XV_EXCLUDED" not in unit
 
 
 @pytest.mark.parametrize("K", [1, 2, 3, 5, 8])
