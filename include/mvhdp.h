@@ -829,6 +829,53 @@ int mvhdp_cohort_top_words(mvhdp_handle h, const mvhdp_cohort_args* a, int64_t n
                            int32_t* nonzero /*[G][K] or NULL*/, int64_t* tokens /*[G][K] or NULL*/, int64_t* docs /*[G][K] or NULL*/,
                            mvhdp_cohort_stats* stats /* or NULL */);
 
+/* ---- word-set co-occurrence: in how many windows of a corpus the words of a set occur, alone and in pairs -- the integer counts behind the
+ * UCI, NPMI and UMass coherence measures (Newman 2010, Lau 2014, Roeder 2015) over documents or over a Boolean sliding window, on the
+ * training corpus or on a held-out or reference corpus, for any view, and independent of the assignments.  The coherence inside
+ * mvhdp_diagnostics (codoc, DIAG:209-221) counts a top word only where the token is assigned to the topic, in view 0, per document; this call
+ * gives a merged topic and its parents, the two sides of a split or two models the same yardstick.  The reference has no counterpart; the
+ * definition is ours.  The formulas stay on the host: the device returns integers.
+ * Word sets: n_sets rows of n slots, n in 1..MVHDP_DIAG_MAX_TOP_WORDS -- exactly the types[K][n] that mvhdp_top_words and
+ *   mvhdp_diagnostics.top_types return, -1 slots included.  A slot holds a type of view m or -1; a -1 may sit anywhere in a row, and its row and
+ *   column of co stay 0.  A word may sit in any number of sets, and in several slots of one set: then every such slot counts.
+ * Corpus: the caller's or the handle's.  The caller's is doc_off / tokens / num_docs, host arrays in the CSR form of mvhdp_fold_in for the
+ *   single view m -- a held-out or reference corpus.  With doc_off == NULL the corpus is tokens and doc_off of view m as the handle holds
+ *   them; num_docs and tokens are then ignored.  z is never read; counts and hyper-parameters are never needed.  Only the entities [d0, d1)
+ *   of whichever corpus are read; d1 == -1: to its end.
+ * Tokens: a token with type >= V_m is out of the vocabulary: it occupies its position and matches no slot.  A negative type is an error:
+ *   MVHDP_ERR_INVALID_ARG in the caller's corpus, MVHDP_ERR_STATE in the handle's.
+ * Windows, for an entity whose span has L tokens: L == 0 gives no window.  window == 0 gives one window, the whole span (document
+ *   co-occurrence).  window == W >= 1 is the Boolean sliding window: its starts are i = 0 .. max(L - W, 0), and window i covers the positions
+ *   [i, min(i + W, L)).  So a span no longer than W is one window and a longer one has L - W + 1.  *windows = the windows over the range.
+ * Counts: slot (s, i) is present in a window when some position of the window holds its word.  co[s][i][j] = the windows in which the slots i
+ *   and j of set s are both present; co[s][i][i] = the windows in which slot i is present.  The matrix is symmetric, every cell is int64,
+ *   and a cell never exceeds *windows: nothing can overflow (the device adds into 64-bit cells).
+ * stats (or NULL): entities = the non-empty spans read; tokens = the positions read; hits = the positions whose type sits in at least one
+ *   set; oov = the positions with type >= V_m; distinct_words = the distinct types over all sets; memberships = the filled slots;
+ *   kernel_ms = the stream's time from the first kernel to the last.
+ * MVHDP_ERR_INVALID_ARG, in this order: a NULL a, co or windows, n_sets < 0, sets NULL with n_sets > 0; m out of range, n outside 1..64,
+ *   window < 0; a slot < -1 or >= V_m; with a caller's corpus num_docs < 0, NULL tokens with tokens to read, doc_off not starting at 0 or
+ *   decreasing, a negative token; d0 < 0, d1 < -1, d0 > d1 (after -1 is resolved), d1 beyond the corpus.  MVHDP_ERR_UNSUPPORTED:
+ *   n_sets * n * n > 2^26 cells.  MVHDP_ERR_STATE: the handle's corpus asked for and mvhdp_set_corpus(m) not called.  -1 for a NULL handle.
+ *   n_sets == 0 or an empty range, after the checks: MVHDP_OK, with *windows still counted and co untouched (it has no cells) or all zeros.
+ *   Every output is untouched on any error.
+ * Guarantees: integers only, so two calls with the same arguments return the same bytes (kernel_ms aside); a set's result does not
+ *   depend on which other sets share the call; results are additive over disjoint entity ranges, because a window never crosses an
+ *   entity; nothing of the handle moves: the assignments, the counts, alpha, the tuning and what mvhdp_counts_written /
+ *   mvhdp_trees_current report are what they were.  Pending work on the handle's stream lands first.  Outputs are staged and copied out
+ *   once, after the whole call has succeeded.
+ * On the device: the sets become an inverted index (first[V_m + 1], packed (set, slot) memberships); one wave per entity, longest first,
+ *   lanes over positions.  An entity goes in chunks of 64 window starts with a 64-bit coverage word per present slot: an occurrence at p
+ *   covers the starts [p - W + 1, p], one run of bits, and a pair gets one add of popcount(cov_i & cov_j) per chunk; no window is visited
+ *   on its own.  A caller's corpus goes up in chunks of whole documents with bounded scratch.
+ * mvhdp_cooc_args, in this order: int32 m, n, window (4 bytes of padding); int64 d0, d1 (32 bytes).  mvhdp_cooc_stats: int64 entities,
+ *   tokens, hits, oov; int32 distinct_words, memberships; double kernel_ms (48 bytes).  tests/test_cooc_kats.py pins both. */
+typedef struct { int32_t m, n, window; int64_t d0, d1 /*-1: to the end*/; } mvhdp_cooc_args;
+typedef struct { int64_t entities, tokens, hits, oov; int32_t distinct_words, memberships; double kernel_ms; } mvhdp_cooc_stats;
+int mvhdp_word_cooccurrence(mvhdp_handle h, const mvhdp_cooc_args* a, int64_t n_sets, const int32_t* sets /*[n_sets][n], -1 = empty slot*/,
+                            int64_t num_docs, const int64_t* doc_off /*[num_docs+1], or NULL: the handle's corpus of view m*/,
+                            const int32_t* tokens, int64_t* co /*[n_sets][n][n]*/, int64_t* windows /*[1]*/, mvhdp_cooc_stats* stats /* or NULL */);
+
 /* ---- topic surgery: merge, drop and reorder topics on the trained handle.  mvhdp_topic_gram finds near-duplicate topics, mvhdp_diagnostics
  * junk topics, n_k the topics that have died out; this call acts on them.  It is what the reference's mergeSimilarTopics (PTM:677-843, left
  * commented out there) does with its merge map and delete list -- every z rewritten (PTM:832-834), then a recount -- applied to the

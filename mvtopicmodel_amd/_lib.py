@@ -18,7 +18,7 @@ ABI_SYMBOLS = [
     "mvhdp_doc_topics_top", "mvhdp_entity_topic_distributions", "mvhdp_similar_pairs", "mvhdp_sim_probe",
     "mvhdp_topic_phrases", "mvhdp_heldout_left_to_right", "mvhdp_fold_in", "mvhdp_predict_items", "mvhdp_score_items",
     "mvhdp_nearest_entities", "mvhdp_nearest_probe", "mvhdp_topic_top_entities", "mvhdp_predict_entities", "mvhdp_rank_entities",
-    "mvhdp_topic_gram", "mvhdp_cohort_top_words", "mvhdp_remap_topics", "mvhdp_split_topic",
+    "mvhdp_topic_gram", "mvhdp_cohort_top_words", "mvhdp_word_cooccurrence", "mvhdp_remap_topics", "mvhdp_split_topic",
     "mvhdp_gamma_doc_statistics", "mvhdp_dp_table_statistics", "mvhdp_antoniak_draws",
     "mvhdp_top_words", "mvhdp_discr_weights", "mvhdp_diagnostics",
     "mvhdp_emb_init", "mvhdp_emb_count_words", "mvhdp_emb_train", "mvhdp_emb_get_vectors", "mvhdp_emb_set_vectors",
@@ -217,6 +217,15 @@ class CohortStatsC(C.Structure):
                 ("cohorts_per_pass", C.c_int32), ("kernel_ms", C.c_double)]
 
 
+class CoocArgsC(C.Structure):
+    _fields_ = [("m", C.c_int32), ("n", C.c_int32), ("window", C.c_int32), ("d0", C.c_int64), ("d1", C.c_int64)]
+
+
+class CoocStatsC(C.Structure):
+    _fields_ = [("entities", C.c_int64), ("tokens", C.c_int64), ("hits", C.c_int64), ("oov", C.c_int64),
+                ("distinct_words", C.c_int32), ("memberships", C.c_int32), ("kernel_ms", C.c_double)]
+
+
 REMAP_RETIRE = 0x1                                  # MVHDP_REMAP_RETIRE
 
 
@@ -374,6 +383,7 @@ def load_library():
     L.mvhdp_rank_entities.argtypes = [vp, C.POINTER(EntitiesArgsC), i64, vp, vp, vp, vp]
     L.mvhdp_topic_gram.argtypes = [vp, C.POINTER(TopicGramArgsC), vp, vp, vp, vp, C.POINTER(TopicGramStatsC)]
     L.mvhdp_cohort_top_words.argtypes = [vp, C.POINTER(CohortArgsC), i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(CohortStatsC)]
+    L.mvhdp_word_cooccurrence.argtypes = [vp, C.POINTER(CoocArgsC), i64, vp, i64, vp, vp, vp, vp, C.POINTER(CoocStatsC)]
     L.mvhdp_remap_topics.argtypes = [vp, C.POINTER(RemapArgsC), C.POINTER(RemapStatsC)]
     L.mvhdp_group_remap_topics.argtypes = [vp, C.POINTER(RemapArgsC), C.POINTER(RemapStatsC)]
     L.mvhdp_split_topic.argtypes = [vp, C.POINTER(SplitArgsC), vp, C.POINTER(SplitStatsC)]

@@ -1,5 +1,5 @@
 // mvhdp_side.h — the host side that the side calls on a trained handle share (diagnostics, similarity, nearest entities, cross-view
-// prediction either way, held-out likelihood, fold-in, topic Gram, cohort words, topic remap, topic split): the argument checks, the call prologue, the stream
+// prediction either way, held-out likelihood, fold-in, topic Gram, cohort words, word co-occurrence, topic remap, topic split): the argument checks, the call prologue, the stream
 // timer, the grid sizes and the lane-order choreography of the one-wave-per-document kernels.  Host code only; no kernel lives here.
 #pragma once
 #include <cmath>

@@ -12,7 +12,7 @@ from dataclasses import dataclass, field
 
 import numpy as np
 
-from ._lib import (CensusRowC, COHORT_BY_COUNT, COHORT_BY_SHARE, CohortArgsC, CohortStatsC, DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
+from ._lib import (CensusRowC, COHORT_BY_COUNT, COHORT_BY_SHARE, CohortArgsC, CohortStatsC, CoocArgsC, CoocStatsC, DIAG_MAX_TOP_WORDS, DIAG_PROPORTIONS, DIAG_ROWS, MAX_M, UNIQUE_ID_BYTES, Config, DebugC, DiagArgsC, DiagOutC,
                    EmbConfigC, EmbStatsC, EntitiesArgsC, EntitiesStatsC, FoldinArgsC, FoldinStatsC, GroupInfoC, HeldoutArgsC, HeldoutStatsC, HyperC, MvhdpError, NearestArgsC, NearestStatsC, PhraseArgsC, PredictArgsC,PhraseStatsC, SimArgsC, SimStatsC, SweepStatsC, TopicGramArgsC, TopicGramStatsC, TuningC,
                    REMAP_RETIRE, RemapArgsC, RemapStatsC, SPLIT_KEEP_ALPHA, SplitArgsC, SplitStatsC,
                    load_library,
@@ -421,6 +421,108 @@ class CohortWords:
         if self.types is None:
             raise ValueError("words needs a call that was not trends-only")
         return [(int(t) if vocabulary is None else vocabulary[int(t)], int(c)) for t, c in zip(self.types[g, k], self.counts[g, k]) if t >= 0]
+
+
+@dataclass
+class CoocStats:
+    """mvhdp_cooc_stats: entities = the non-empty spans read, tokens = the positions read, hits = the positions whose type sits in at least
+    one set, oov = the positions with a type outside the vocabulary, distinct_words = the distinct types over all sets, memberships = the
+    filled slots; kernel_ms = the stream's time from the first kernel to the last."""
+    entities: int = 0
+    tokens: int = 0
+    hits: int = 0
+    oov: int = 0
+    distinct_words: int = 0
+    memberships: int = 0
+    kernel_ms: float = 0.0
+
+
+COOC_MEASURES = ("uci", "npmi", "umass")
+
+
+@dataclass
+class WordCooccurrence:
+    """mvhdp_word_cooccurrence: co [S][n][n] (int64) = the windows in which the slots i and j of set s are both present (the diagonal: in
+    which slot i is present), windows = the windows of the entity range, sets [S][n] = the word sets as they were passed (-1 = empty slot).
+    The measures below are host derivations by numpy from these integers.  Their formulas are ours and are stated in full; they are the
+    usual definitions of the literature, but no equality with any toolkit's numbers is claimed."""
+    co: np.ndarray
+    windows: int
+    sets: np.ndarray
+    stats: CoocStats = None
+
+    def occurrences(self):
+        """[S][n]: the windows in which each slot is present (the diagonals of co).  A host derivation."""
+        return np.diagonal(self.co, axis1=1, axis2=2).copy()
+
+    def pair_scores(self, measure, eps=1e-12):
+        """[S][n][n] float64, a host derivation.  With p_i = co_ii / windows and p_ij = co_ij / windows:
+          "uci":   log((p_ij + eps) / (p_i p_j))
+          "npmi":  the same divided by -log(p_ij + eps)
+          "umass": for j < i in slot order log((p_ij + eps) / p_j); the upper triangle and the diagonal are NaN
+        A pair with an empty slot, or with co_ii == 0 or co_jj == 0, is NaN."""
+        if measure not in COOC_MEASURES:
+            raise ValueError('measure must be "uci", "npmi" or "umass"')
+        occ = self.occurrences()
+        ok = (np.asarray(self.sets) >= 0) & (occ > 0)
+        defined = ok[:, :, None] & ok[:, None, :]
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p = occ.astype(np.float64) / float(self.windows) if self.windows > 0 else np.full(occ.shape, np.nan)
+            pij = self.co.astype(np.float64) / float(self.windows) if self.windows > 0 else np.full(self.co.shape, np.nan)
+            if measure == "umass":
+                out = np.log((pij + eps) / p[:, None, :])
+                n = out.shape[1]
+                defined = defined & np.tril(np.ones((n, n), dtype=bool), -1)[None]
+            else:
+                out = np.log((pij + eps) / (p[:, :, None] * p[:, None, :]))
+                if measure == "npmi":
+                    out = out / -np.log(pij + eps)
+        return np.where(defined, out, np.nan)
+
+    def coherence(self, measure, aggregate="mean", eps=1e-12):
+        """[S] float64: per set the mean (or "sum") of pair_scores over the pairs j < i, NaN pairs skipped; NaN for a set without a
+        defined pair.  A host derivation."""
+        if aggregate not in ("mean", "sum"):
+            raise ValueError('aggregate must be "mean" or "sum"')
+        sc = self.pair_scores(measure, eps)
+        n = sc.shape[1]
+        low = np.tril(np.ones((n, n), dtype=bool), -1)[None]
+        use = low & ~np.isnan(sc)
+        cnt = use.sum(axis=(1, 2))
+        tot = np.where(use, sc, 0.0).sum(axis=(1, 2))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            val = tot / cnt if aggregate == "mean" else tot
+        return np.where(cnt > 0, val, np.nan)
+
+
+def _word_sets(sets):
+    """[S][n] int32 from an int array or from a list of lists, the short rows padded with -1"""
+    if isinstance(sets, np.ndarray):
+        out = np.ascontiguousarray(sets, dtype=np.int32)
+    else:
+        rows = [list(r) for r in sets]
+        n = max([len(r) for r in rows], default=0)
+        out = np.full((len(rows), n), -1, dtype=np.int32)
+        for i, r in enumerate(rows):
+            out[i, :len(r)] = r
+    if out.ndim != 2:
+        raise ValueError("sets must be [S][n]")
+    return out
+
+
+def merge_word_cooccurrence(parts):
+    """The WordCooccurrence of a corpus from those of disjoint entity ranges (or document shards) over the same sets: co, windows and the
+    additive stats summed -- exact, because a window never crosses an entity.  Refuses parts whose sets differ.  No device."""
+    parts = list(parts)
+    if not parts:
+        raise ValueError("merge_word_cooccurrence: no parts")
+    for p in parts[1:]:
+        if p.sets.shape != parts[0].sets.shape or not np.array_equal(p.sets, parts[0].sets):
+            raise ValueError("merge_word_cooccurrence: the parts were counted for different sets")
+    st = [p.stats for p in parts if p.stats is not None]
+    stats = CoocStats(sum(s.entities for s in st), sum(s.tokens for s in st), sum(s.hits for s in st), sum(s.oov for s in st),
+                      st[0].distinct_words if st else 0, st[0].memberships if st else 0, sum(s.kernel_ms for s in st))
+    return WordCooccurrence(np.sum([p.co for p in parts], axis=0, dtype=np.int64), sum(int(p.windows) for p in parts), parts[0].sets.copy(), stats)
 
 
 @dataclass
@@ -1248,6 +1350,33 @@ class NativeSampler:
                                                _ptr(nonzero), _ptr(tokens), _ptr(docs), C.byref(st)))
         return CohortWords(types, counts, nonzero, tokens, docs, CohortStats(**{f: getattr(st, f) for f, _ in CohortStatsC._fields_}))
 
+    # -- word-set co-occurrence (include/mvhdp.h mvhdp_word_cooccurrence) --
+    def word_cooccurrence(self, sets, m=0, window=0, d0=0, d1=None, corpus=None) -> WordCooccurrence:
+        """In how many windows the words of each set occur, alone and in pairs: sets is an int array [S][n] or a list of lists (padded
+        with -1 to the longest), e.g. top_words(m, n)[0].  window 0: one window per entity (document co-occurrence); W >= 1: the Boolean
+        sliding window of W positions.  corpus: None for view m as the handle holds it, or (doc_off, tokens) of a held-out or reference
+        corpus of that view; the assignments are never read.  Only the entities [d0, d1) are counted (d1 None: to the end).  The measures
+        (uci, npmi, umass) are methods of the WordCooccurrence returned."""
+        st_sets = _word_sets(sets)
+        S, n = st_sets.shape
+        doc_off = tokens = None
+        num_docs = 0
+        if corpus is not None:
+            doc_off, tokens = _heldout_docs(*corpus)
+            num_docs = len(doc_off) - 1
+        a = CoocArgsC(int(m), int(n), int(window), int(d0), -1 if d1 is None else int(d1))
+        co = np.zeros((S, n, n), dtype=np.int64)
+        windows = np.zeros(1, dtype=np.int64)
+        st = CoocStatsC()
+        self._ck(self.L.mvhdp_word_cooccurrence(self.h, C.byref(a), S, _ptr(st_sets) if st_sets.size else None, num_docs, _ptr(doc_off),
+                                                _ptr(tokens) if tokens is not None and len(tokens) else None, _ptr(co), _ptr(windows), C.byref(st)))
+        return WordCooccurrence(co, int(windows[0]), st_sets, CoocStats(**{f: getattr(st, f) for f, _ in CoocStatsC._fields_}))
+
+    def topic_coherence(self, n=20, m=0, window=0, measure="npmi", corpus=None):
+        """[K] float64: top_words(m, n) into word_cooccurrence into WordCooccurrence.coherence(measure), one value per topic (NaN for a
+        topic without two words that occur).  Needs current counts, as top_words does."""
+        return self.word_cooccurrence(self.top_words(m, n)[0], m, window, corpus=corpus).coherence(measure)
+
     # -- topic diagnostics (FastQMVWVTopicModelDiagnostics; include/mvhdp.h mvhdp_top_words / _discr_weights / _diagnostics) --
     # -- topic surgery (include/mvhdp.h mvhdp_remap_topics; mvtopicmodel_amd/surgery.py builds the maps) --
     def remap_topics(self, topic_map, retire=False) -> RemapStats:
@@ -1738,6 +1867,18 @@ class NativeGroup:
             if lo < hi:
                 out.append((s, int(b), lo - int(b), hi - int(b)))
         return out, d0, d1
+
+    def word_cooccurrence(self, sets, m=0, window=0, d0=0, d1=None, corpus=None) -> WordCooccurrence:
+        """NativeSampler.word_cooccurrence of the sharded corpus, over the LOCAL members: every member counts its own entities of
+        [d0, d1) (entity ids count through the members in their order) and the parts are summed (merge_word_cooccurrence): exact, because
+        a window never crosses an entity.  A caller's corpus is no member's: the first member counts it.  A group of rank processes merges
+        its ranks' results the same way on the host side."""
+        if corpus is not None:
+            return self.members[0].word_cooccurrence(sets, m, window, d0, d1, corpus)
+        parts, d0, d1 = self._member_ranges(d0, d1)
+        if not parts:                                                        # an empty range: the first member answers with its zeros
+            return self.members[0].word_cooccurrence(sets, m, window, 0, 0)
+        return merge_word_cooccurrence([s.word_cooccurrence(sets, m, window, lo, hi) for s, _, lo, hi in parts])
 
     def predict_items(self, m, view_weights, n, d0=0, d1=None, exclude_present=True, theta=None):
         """NativeSampler.predict_items over the LOCAL members: the counts are replicated and the entities partitioned, so every member
