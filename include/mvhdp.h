@@ -1180,6 +1180,9 @@ typedef struct {
     int32_t vectors_mix;                         /* 1: a useVectorsLambda mix is set (mvhdp_set_vectors_mix): the mix flavours of the kernels run -- always the walk
                                                     flavour --, a live sweep takes its stored-tree form.  0: today's plans, bit for bit */
     int32_t kernel_registers_mix[6][3];          /* VGPRs of the mix flavours, as kernel_registers ([.][0] unused); a 0 takes the plain flavour's count */
+    int32_t unassigned;                          /* 1: some token may still be unassigned (z = -1, a handle between mvhdp_set_corpus / mvhdp_set_assignments and its first
+                                                    full sweep): row totals can grow, so no 16-bit delta cells and no live 16-bit mirror.  0: today's plans, bit for bit.
+                                                    (Sits in what was the struct's tail padding: its size has not changed.) */
 } mvhdp_plan_input;
 typedef struct {
     int32_t status;                              /* what mvhdp_sweep would return for these flags (MVHDP_OK or an error) */

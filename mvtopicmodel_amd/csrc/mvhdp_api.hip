@@ -776,6 +776,7 @@ extern "C" int mvhdp_plan_probe(const mvhdp_plan_input* pi, const mvhdp_tuning* 
     for (int b = 0; b < MVHDP_ENT_BINS; b++) in.ent_hist[b] = pi->entities_by_class[b];
     in.flags = pi->flags; in.debug = pi->debug != 0; in.batch = pi->batch != 0; in.trees_current = pi->trees_current != 0;
     in.first_inactive = pi->inactive_topics ? 0 : -1;
+    in.unassigned = pi->unassigned != 0;
     in.num_cus = pi->num_cus > 0 ? pi->num_cus : 256;
     for (int c = 0; c < MVHDP_N_CLASSES; c++) for (int f = 0; f < 3; f++) in.regs.regs[c][f] = pi->kernel_registers[c][f];
     // (a probe that names no register counts for the mix flavours sizes them as the plain ones)

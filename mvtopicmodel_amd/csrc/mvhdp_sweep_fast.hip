@@ -680,7 +680,7 @@ __global__ __launch_bounds__(256, fast_launch_bound(RMAX, WALK, ROOMY, LIVEROWS,
                 // the tree branch has its row loaded at the top of its turn (specm)
                 const bool heavy_l = NARROW && w_l >= 0 && (w_l & W_HEAVY);
                 const bool walk_l = tvalid && w_l >= 0 && (!WALK || u1_l >= walk_theta) && (!LIVEROWS || heavy_l);
-                const unsigned long long walked = WALK ? __ballot(walk_l) : ~0ull;
+                unsigned long long walked = WALK ? __ballot(walk_l) : ~0ull;
                 const unsigned long long specm = LIVEROWS ? __ballot(tvalid && w_l >= 0 && !heavy_l && u1_l >= walk_theta) : 0ull;
                 rowq_t rowq = {0u, 0u, 0u, 0u};
                 if (WALK && tvalid && w_l >= 0 && !walk_l) root_l = mm.root[row0 + W_ROW(w_l)];
@@ -723,10 +723,17 @@ __global__ __launch_bounds__(256, fast_launch_bound(RMAX, WALK, ROOMY, LIVEROWS,
                     }
                     if (act) {
                         zt_l = i - K;                                        // FT:132
-                        const uint32_t wbit = bitmap[zt_l >> 5];
-                        if ((wbit >> (zt_l & 31)) & 1u) st_l = (int)(prefix[zt_l >> 5] + __popc(wbit & ((1u << (zt_l & 31)) - 1u)));
+                        // live-rows form: a heavy word's table read WHILE heavy_refresh_kernel rewrites it is a mixture of two trees; where they are
+                        // far apart (a word whose tokens all change topic in this sweep) the descent can end at a leaf that is zero in both -- a
+                        // topic without alpha, or an inactive one.  Such a token is not walked here: it walks again at its turn.
+                        if (LIVEROWS && !(mm.coef[(int64_t)m * Kp + zt_l] > 0.0f)) zt_l = -1;
+                        if (zt_l >= 0) {
+                            const uint32_t wbit = bitmap[zt_l >> 5];
+                            if ((wbit >> (zt_l & 31)) & 1u) st_l = (int)(prefix[zt_l >> 5] + __popc(wbit & ((1u << (zt_l & 31)) - 1u)));
+                        }
                     }
                 }
+                if (LIVEROWS && WALK) walked &= ~__ballot(walk_l && zt_l < 0);
 
                 MVHDP_TSUB2(tv);                                             // (split 2: heavy flags, roots, the tree walk, the sampled topic's slot)
                 const float root32_l = (float)root_l;

@@ -366,6 +366,10 @@
                             philox4x32_10((uint32_t)(c0 + TOK_T), (uint32_t)m, (uint32_t)dg, sl.sweep_idx,
                                           sl.seed_lo, sl.seed_hi ^ (uint32_t)((unsigned long long)dg >> 32), x);
                             znew = uniform_i(dtab_sample_uniform(mm, row, bits_to_unit(x[2], x[3])));
+                            // (live-rows form, a heavy word: a leaf that is zero whatever the counts cannot come from a tree read whole -- see the
+                            // chunk head; the token then takes its topic from the smoothing parts alone, which heavy_refresh_kernel does not touch)
+                            if (LIVEROWS && NARROW && !(mm.coef[(int64_t)m * Kp + znew] > 0.0f))
+                                znew = uniform_i(smoothing_sample_live(smp_m, K, (float)bits_to_unit(x[2], x[3]) * smS, lane));
                             const uint32_t wbit = bitmap[znew >> 5];
                             slot_new = ((wbit >> (znew & 31)) & 1u) ? (int)(prefix[znew >> 5] + __popc(wbit & ((1u << (znew & 31)) - 1u))) : -1;
                             slot_new = uniform_i(slot_new);

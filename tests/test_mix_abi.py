@@ -19,7 +19,7 @@ def test_declared_listed_and_exported():
     L = _lib.load_library()
     for n in NAMES:
         assert getattr(L, n) is not None
-    assert [f for f, _ in _lib.PlanInputC._fields_][-2:] == ["vectors_mix", "kernel_registers_mix"]
+    assert [f for f, _ in _lib.PlanInputC._fields_][-3:] == ["vectors_mix", "kernel_registers_mix", "unassigned"]
 
 
 def test_python_wrappers():
